@@ -3,6 +3,14 @@
 4096 envs x 1024-pt clouds).
 
     python bench.py [--gpus N --steps K --warmup W] [--workload vision|vision_pn2|state|dagger|depth2pc]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, unit, ms_per_step and
+the roofline of the kernels bracketed inside the timed steps.  `--full` adds everything that needs runs of
+its own: the CPU baseline, the opt-in precision / stream paths, the other configs' `secondary` sub-lines
+and the single-kernel side timings.  `--dump-outputs DIR` writes what the timed path computed in its last
+step (parameters, returns, losses, sampled clouds) as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared array for array.
 
 A "step" is one learner iteration = the reference's `learn_time` window (ppo.py:256-262:
 compute_returns + update + storage.clear) over one synthetic rollout batch that is already
@@ -12,7 +20,7 @@ under torch.distributed.run the ranks come from RANK / LOCAL_RANK / WORLD_SIZE; 
 visible).  Each rank owns its own 4096 envs (weak scaling) and gradients are all-reduced over
 RCCL once per optimiser step.
 
-Rank 0 prints ONE JSON line; every workload's line carries
+Rank 0 prints ONE JSON line; with --full every workload's line carries
   roofline     : live HIP-event timing of the workload's dominant kernel against the roofline that
                  bounds it (fp32-MFMA 157.3 TFLOP/s or HBM 8 TB/s, MI355X_MICROARCH.md)
   cpu_baseline : the CPU oracle (oracle/ref_cpu.py, pinned to the reference) timed on this box's
@@ -52,6 +60,26 @@ PN2_GLUE_GEMMS = {"linear_fwd_524288x128x128": 2.0 * 524288 * 128 * 128, "linear
                   "linear_bwd_data_131072x256x256": 2.0 * 131072 * 256 * 256, "linear_bwd_weight_131072x256x288": 2.0 * 131072 * 256 * 288}
 
 DAGGER = dict(name="dagger_pointnet_student_4096env_x_16buf_x_{P}pt", N=4096, buf=16, O_t=53, A=10)
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(args, rank, arrays):
+    """--dump-outputs DIR: rank 0 writes each array as DIR/<name>.npy (float64 stays float64, everything else float32).
+    Called right after the timed steps, before any side measurement touches the state."""
+    import numpy as np
+    d = getattr(args, "dump_outputs", None)                 # (tools/ call the runners with a Namespace of their own)
+    if not d or rank != 0:
+        return
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        out[name.replace("/", "_")] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------ CPU baseline
@@ -213,6 +241,8 @@ def run_dagger(args, device, rank, world):
     fence()
     dt = time.perf_counter() - t0
     ops.TIMER.disable()
+    dump_outputs(args, rank, {"student_actor_params": run.student.flat()["actor"],
+                              "dagger_loss": torch.tensor([float(run.log_dict["Train/dagger_loss"])], dtype=torch.float64)})
     dt = _max_over_ranks(dt, device, world)
     rows = d["N"] * d["buf"] * 2                        # samples through the student per update
     mb = min(d["N"] * d["buf"] // 16, 2048)
@@ -366,7 +396,14 @@ def run_depth2pc(args, device):
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / n
 
-    dt = timed(lambda: vol.depth2pc(depth), args.steps)
+    metric = "depth2pc seconds per call, 64 envs x 6 views x 180x320 px -> 1024 pts"
+    last = {}
+    dt = timed(lambda: last.update(cloud=vol.depth2pc(depth)), args.steps)
+    dump_outputs(args, 0, last)
+    if not args.full:
+        return dict(metric=metric, value=dt, unit="s",
+                    n_gpus=1, steps=args.steps, warmup=args.warmup, ms_per_step=dt * 1e3, higher_is_better=False,
+                    scaling="weak", dtype="f32", data="synthetic", config=dict(workload="depth2pc_64env_x_6view_x_180x320"))
     lo = vol._vol_origin.cpu().numpy()
     world = ops.depth_backproject(depth, vol.cam_pose, 250.0, 250.0, w_ / 2 - 0.5, h / 2 - 0.5, lo, vol._size + lo)
     ws = ops.Workspace(device)
@@ -384,7 +421,7 @@ def run_depth2pc(args, device):
     plane = (0.75 + 0.0004 * xx + 0.0006 * yy).float().expand(b, m, h, w_).contiguous()
     band = vol.integrate(plane).abs().lt(0.2).flatten(1).sum(-1).float().mean().item()
     dv = timed(lambda: vol.sparse_voxel(plane), args.steps)
-    out = dict(metric="depth2pc seconds per call, 64 envs x 6 views x 180x320 px -> 1024 pts", value=dt, unit="s",
+    out = dict(metric=metric, value=dt, unit="s",
                n_gpus=1, steps=args.steps, warmup=args.warmup, ms_per_step=dt * 1e3, higher_is_better=False,
                scaling="weak", vs_baseline=ds / 0.5, dtype="f32", data="synthetic",
                config=dict(workload="depth2pc_64env_x_6view_x_180x320", sampling_ms=ds * 1e3, in_crop_fraction=valid,
@@ -632,7 +669,11 @@ def run_ppo(args, device, rank, world):
     fence()
     dt = time.perf_counter() - t0
     ops.TIMER.disable()
-    if args.workload == "vision_pn2":
+    fl = ac.flat()
+    dump_outputs(args, rank, dict(actor_params=fl["actor"], critic_params=fl["critic"], returns=st.returns, advantages=st.advantages,
+                                  **{k: torch.tensor([float(v)], dtype=torch.float64) for k, v in run.log_dict.items()
+                                     if k.startswith("Train/")}))
+    if args.workload == "vision_pn2" and args.full:
         # per-kernel durations for the roofline block: ONE more step with actor and critic on one stream (in the timed region
         # they run on two and share the chip, which stretches every launch), outside the timed region
         ov = run.overlap
@@ -673,13 +714,13 @@ def run_ppo(args, device, rank, world):
         out["config"]["workload_note"] = ("PointNet -- the backbone the reference ships for this task (algo_utils/network.py:141-198); BASELINE.json "
                                      "configs[2] words it as PointNet2, which the snapshot does not contain: the same 4096 env x 8 step x 1024-pt "
                                      "rollouts through the PointNet2 plug-in (HIP FPS + ball query + fused set-abstraction kernels) are "
-                                     "`secondary.vision_pn2` of this line (--workload vision_pn2), with their own roofline, traffic and CPU baseline")
+                                     "`secondary.vision_pn2` of this line under --full (--workload vision_pn2), with their own roofline, traffic and CPU baseline")
     if dp is not None:
         out["config"]["data_parallel"] = dp
         out["comm_ms_per_step"] = dp["comm_ms_per_step"]
     gae = ops.TIMER.mean_ms("gae_scan")
     gae_blk = None
-    if gae:
+    if gae and args.full:
         nbytes = 18.0 * w["T"] * w["N"]                    # r, V 8 B + 2 mask B in; ret, adv 8 B out
         # the iteration launches the scan ONCE, between host work: events around that single ~10 us launch mostly time
         # its dispatch.  The kernel's own rate is taken from 32 launches replayed from one hipGraph on scratch outputs.
@@ -748,7 +789,7 @@ def run_ppo(args, device, rank, world):
                      "(DESIGN.md 3.2) eliminates the 256->512 layer's two backward GEMMs algebraically (max-pool gradient = one row "
                      "per channel, layer 3 linear), so a backward EXECUTES 0.4 F instead of 2 F.  `frac` here is executed flops "
                      "/ wall / peak; survey_30F_useful_tflops (> peak) is the same wall time priced the survey's way")
-    if args.workload == "vision_pn2":
+    if args.workload == "vision_pn2" and args.full:
         # the four fused set-abstraction kernels.  They run over each group's DISTINCT rows (ball query pads a short group with
         # copies of its first hit, and a copy never wins the max-pool: DESIGN.md 3.4), so `achieved` counts the MFMA flops of
         # the distinct rows of one 2048-cloud mini-batch -- fwd: layers 2-3; bwd: dH2 + dW2 + dH1 (layer 2 is loaded from what
@@ -856,7 +897,7 @@ def run_ppo(args, device, rank, world):
                                             "term of algorithmic_bytes is what the 2560 steps touch, almost all of it out of L2",
                                flops_per_env_step=per_env_step,
                                note="algorithmic flops of the iteration / its wall time: every launch gap is inside")
-        if rank == 0 and world == 1 and not args.lean and run.use_graphs and run.graph_steps > 1:
+        if args.full and rank == 0 and world == 1 and not args.lean and run.use_graphs and run.graph_steps > 1:
             # What bounds the iteration with TODAY's kernels ("a stated ceiling rather than an open question").  Each
             # network's epoch is a list of 16-step hipGraphs; replayed ALONE on the idle chip they give that network's dependent-launch
             # chain time -- kernel durations + in-graph launch boundaries, no host, no contention.  The iteration cannot beat
@@ -910,7 +951,7 @@ def run_ppo(args, device, rank, world):
                          "pair with both chains sharing the chip; overlap_efficiency = the fraction of the shorter chain hidden under "
                          "the longer one.  Beating ceiling_env_steps_per_s_perfect_overlap needs faster kernels or fewer launch "
                          "boundaries per step, not better scheduling")
-        if rank == 0 and not args.lean:
+        if args.full and rank == 0 and not args.lean:
             # the dominant kernel on its own: a hidden layer (mini-batch x 512 x 512) on gemm2_dma_kernel, 32 dependent launches
             # replayed from a graph on the otherwise idle chip (in the iteration two networks' chains share it)
             Bm, H = 2048, hid[0]
@@ -1045,7 +1086,7 @@ def secondary_lines(args, device):
     for key, kw in (("state", dict(workload="state")), ("dagger_sparse_unet", dict(workload="dagger", student="sparse_unet", points=4096)),
                     ("vision_pn2", dict(workload="vision_pn2")), ("depth2pc", dict(workload="depth2pc"))):
         a = copy.copy(args)
-        a.steps, a.warmup, a.n_steps, a.precision = 3, 1, 0, "f32"
+        a.steps, a.warmup, a.n_steps, a.precision, a.dump_outputs = 3, 1, 0, "f32", None
         for k, v in kw.items():
             setattr(a, k, v)
         gc.collect()
@@ -1153,7 +1194,14 @@ def main():
     ap.add_argument("--points", type=int, default=4096, help="dagger workload: points per student cloud (BASELINE cfg 5: 4096)")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16x3", "bf16x6"],
                     help="vision encoder forward: exact fp32 MFMA (default) or the opt-in split-bf16 path")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs runs of its own: CPU baseline, opt-in paths, secondary sub-lines, single-kernel timings "
+                         "(the --no-* / --lean switches above then select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_optional = args.no_secondary = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))                  # re-exec as N ranks under torch.distributed.run
