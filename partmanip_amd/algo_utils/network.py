@@ -10,6 +10,7 @@ Compute is NOT torch autograd: forward and backward are explicit chains of HIP k
 RCCL all-reduce per step).
 """
 import math
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -72,22 +73,19 @@ class _LinearChain:
             self._cws = ops.Workspace(device)
         return self._cws
 
-    def forward(self, x, out=None, x_w=None):
+    def forward(self, x, out=None, x_w=None, w0p=None):
+        """w0p: the caller's current copy of the first layer's weights in the layout below (PointNet2's operand-copy arena)."""
         n = len(self.linears)
         self.x, self.x_w = x, x_w
         self.h = []
         cur = x
         # rows wider than the first layer's fan-in (the caller zero-filled the extra columns so that K is a multiple of the
         # GEMM's 32-wide K-step: the LDS-DMA kernels instead of the register-staged one): a zero-padded copy of the weights
-        self.w0p = None
-        if x.shape[1] != self.linears[0].in_features or self.col_blocks is not None:
+        self.w0p = w0p
+        if w0p is None and (x.shape[1] != self.linears[0].in_features or self.col_blocks is not None):
             w0 = self.linears[0].weight.data
-            ext = getattr(self, "w0p_ext", None)           # kept current by the owner's operand-copy gather (PointNet2._arena_refresh)
-            if ext is not None and ext.shape == (w0.shape[0], x.shape[1]) and ext.device == x.device:
-                self.w0p = ext
-            else:
-                self.w0p = torch.empty(w0.shape[0], x.shape[1], device=x.device)
-                ops.col_blocks(self.w0p, w0, self.col_blocks or [(0, w0.shape[1], 0)])    # one launch: permuted blocks + zero padding
+            self.w0p = torch.empty(w0.shape[0], x.shape[1], device=x.device)
+            ops.col_blocks(self.w0p, w0, self.col_blocks or [(0, w0.shape[1], 0)])    # one launch: permuted blocks + zero padding
         for i, lin in enumerate(self.linears):
             last = i == n - 1
             y = out if (last and out is not None) else torch.empty(cur.shape[0], lin.out_features, device=cur.device)
@@ -242,6 +240,14 @@ class _HipNet(nn.Module):
             object.__setattr__(self, "_ws", ws)
         return ws
 
+    def _scratch(self, name, n, device):
+        """First n elements of the grow-only fp32 buffer `name`, kept across steps (reallocated when too small or on another device)."""
+        buf = getattr(self, name, None)
+        if buf is None or buf.numel() < n or buf.device != device:
+            buf = torch.empty(n, device=device)
+            object.__setattr__(self, name, buf)
+        return buf[:n]
+
     def set_grad_views(self, views):
         """views: dict param-name -> tensor view into the owner's flat gradient buffer."""
         raise NotImplementedError
@@ -358,12 +364,7 @@ class PointNet(_HipNet):
         backward loads them instead of recomputing layer 2 (2 GB at 2048 clouds x 1024 points; HBM is 288 GB and
         the kernels are MFMA-bound, so the extra 1 KB per point each way is free and a third of the backward's
         matrix work disappears).  `net_cfg['save_h2']: False` restores the recompute path."""
-        n = B * self.point_num * 256
-        buf = getattr(self, "_h2buf", None)
-        if buf is None or buf.numel() < n or buf.device != device:
-            buf = torch.empty(n, device=device)
-            object.__setattr__(self, "_h2buf", buf)
-        return buf[:n].view(B, self.point_num, 256)
+        return self._scratch("_h2buf", B * self.point_num * 256, device).view(B, self.point_num, 256)
 
     def hip_forward(self, x, out=None, save_h2=None):
         B = x.shape[0]
@@ -432,6 +433,41 @@ class _GeomTabs(list):
         self.plans = {}
 
 
+# What PointNet2.hip_forward keeps of a level for hip_backward.  Every record starts with the level's neighbour table `idx` (None:
+# group-all rows the last level wrote in place) and its max-pool arg-max `arg`.
+class _FusedLevel(NamedTuple):
+    idx: torch.Tensor
+    arg: torch.Tensor
+    xyz: torch.Tensor
+    feat: Optional[torch.Tensor]          # None: no input features
+    centers: torch.Tensor
+    Y: Optional[torch.Tensor]
+    packed: torch.Tensor
+    pooled: torch.Tensor
+    h2: Optional[torch.Tensor]
+    plan: object                          # ops.SaPlan, or None: the padded kernels
+    w1f: Optional[torch.Tensor]
+
+
+class _UnfusedLevel(NamedTuple):          # (also the group-all level when it is not fused)
+    idx: torch.Tensor
+    arg: torch.Tensor
+    h: torch.Tensor
+    P: int
+    cf: int
+    ldo: int
+
+
+class _GroupAllLevel(NamedTuple):
+    idx: Optional[torch.Tensor]
+    arg: torch.Tensor
+    h: torch.Tensor
+    P: int
+    cf: int
+    ldo: int
+    pooled: torch.Tensor
+
+
 class PointNet2(_HipNet):
     """PointNet++ (single-scale grouping) encoder as a backbone plug-in (`network.name: PointNet2`).
 
@@ -489,6 +525,7 @@ class PointNet2(_HipNet):
             nn.Linear(32, output_dim),
         )
         object.__setattr__(self, "_chains", chains)
+        object.__setattr__(self, "_dims", [tuple(m) for m in mlps[:-1]])          # each level's layer widths (C1, C2, C3 when fused)
         object.__setattr__(self, "_head", _LinearChain([self.final_mlp[0], self.final_mlp[2], self.final_mlp[4]], code))
         # levels that run as ONE fused kernel per direction (pm_sa_fwd_f32 / pm_sa_bwd_f32); the others use the
         # separate gather / Linear / max-pool kernels (still HIP, just unfused)
@@ -503,16 +540,12 @@ class PointNet2(_HipNet):
             fused_ok and net_cfg.get('fused_groupall', True) and len(ga) >= 2 and act == 'tanh'
             and bool(self.npoints) and ops.sa_groupall_supported(ga[-2], ga[-1], self.npoints[-1])))
         object.__setattr__(self, "_ga_chain", _LinearChain(chains[-1].linears[:-1], code, final_act=True) if self._ga_fused else None)
-        object.__setattr__(self, "_ga_packed", None)
         # ... and the last set-abstraction level then writes its pooled rows straight into the group-all input rows
         # ([features | xyz | 0], the first layer's weight columns permuted alike): no gather copy forward, no scatter copy backward
         object.__setattr__(self, "_ga_direct", bool(self._ga_fused and self.npoints and self._fused[-1]
                                                     and net_cfg.get('groupall_direct_rows', True)))
         if self._ga_direct:
             self._ga_chain.col_blocks = [(3, 3 + mlps[-2][-1], 0), (0, 3, mlps[-2][-1])]
-        object.__setattr__(self, "_sa_packed", [None] * len(self.npoints))
-        object.__setattr__(self, "_sa_h2", [None] * len(self.npoints))
-        object.__setattr__(self, "_save_h2_now", False)
         self.save_h2 = bool(net_cfg.get('save_h2', True))
         # fused levels run over each group's DISTINCT rows (ball query pads short groups with copies of their first hit;
         # a copy never wins the max-pool): same outputs and gradients as the dense kernels, `False` keeps the dense form (A/B)
@@ -520,13 +553,9 @@ class PointNet2(_HipNet):
         # the gradient of a level's per-source-point layer-1 rows summed in a FIXED order over the plan's inverse table (no fp32
         # atomics: every bit of a backward is reproducible run to run); `False` keeps the atomic scatter (A/B)
         self.sa_deterministic = bool(net_cfg.get('sa_deterministic', True))
-        object.__setattr__(self, "_sa_dz1", [None] * len(self.npoints))
         self.sa_fused_dy = bool(net_cfg.get('sa_fused_dy', True))             # False: segmented-sum pass + the two Linear launches (A/B)
-        self.weight_arena = bool(net_cfg.get('weight_arena', True))           # False: one pack / copy launch per operand copy (A/B)
         object.__setattr__(self, "_arena", None)
         object.__setattr__(self, "_arena_views", None)
-        object.__setattr__(self, "_sa_packed_w1f", [None] * len(self.npoints))
-        object.__setattr__(self, "_sa_grads", None)
 
     def set_grad_views(self, views):
         for l, ch in enumerate(self._chains):
@@ -540,111 +569,95 @@ class PointNet2(_HipNet):
     # pack, the aligned W1 feature block, the K-step-padded first group-all layer, the consumer's operand copy): six launches that
     # each queue behind the other network's persistent kernels (6 % of the step's kernel time in rocprofv3).  All of them are
     # gathers of the flat parameter buffer with a layout-fixed table: the table is recorded once by running those same entry
-    # points on index-valued weights, and a forward refreshes the whole arena with pm_gather_copy_f32.
+    # points on an index-valued copy of the buffer, and a forward refreshes the whole arena with pm_gather_copy_f32.  A network
+    # whose parameters are not in one flat buffer (used outside ActorCritic.flat()) fills the same arena through the entry points.
     def _arena_segments(self):
-        """[(key, numel)] of the weight-derived copies this configuration uses (16-byte aligned segments of one buffer)."""
+        """[(key, shape)] of the weight-derived copies this configuration uses (16-byte aligned segments of one buffer)."""
         segs = []
-        for l in range(len(self.npoints)):
+        for l, dims in enumerate(self._dims):
             if not self._fused[l]:
                 continue
-            lin1, lin2, lin3 = self.sa[l][0], self.sa[l][2], self.sa[l][4]
-            dims = (lin1.out_features, lin2.out_features, lin3.out_features)
-            segs.append((("sa_packed", l), int(ops.lib.pm_sa_packed_elems(*dims))))
+            segs.append((("sa_packed", l), (int(ops.lib.pm_sa_packed_elems(*dims)),)))
             cf = self.in_feats[l]
             if cf > 0:
-                segs.append((("w1f", l), dims[0] * cf))
+                segs.append((("w1f", l), (dims[0], cf)))
                 if ops.sa_dy_consume_supported(dims[0], cf):
-                    segs.append((("dyc", l), int(ops.lib.pm_sa_dy_consume_packed_elems(dims[0], cf))))
+                    segs.append((("dyc", l), (int(ops.lib.pm_sa_dy_consume_packed_elems(dims[0], cf)),)))
         if self._ga_fused:
             lin = self._chains[-1].linears[-1]
-            segs.append((("ga_packed",), int(ops.lib.pm_sa_groupall_packed_elems(lin.in_features, lin.out_features))))
+            segs.append((("ga_packed",), (int(ops.lib.pm_sa_groupall_packed_elems(lin.in_features, lin.out_features)),)))
             w0 = self._ga_chain.linears[0].weight
             ldo = (self.sa[-1][0].in_features + 31) // 32 * 32
             if ldo != w0.shape[1] or self._ga_chain.col_blocks is not None:
-                segs.append((("ga_w0p",), w0.shape[0] * ldo))
+                segs.append((("ga_w0p",), (w0.shape[0], ldo)))
         return segs
 
-    def _arena_fill_by_entry_points(self, views):
-        """Every copy through its own entry point (the pre-round-6 path; also what records the gather table)."""
+    def _arena_fill_by_entry_points(self, views, weight):
+        """Every copy through its own entry point, which reads `weight(lin)` as the weight of each nn.Linear: the live weights, or
+        the same parameter's slice of an index-valued buffer (what records the gather table)."""
         for key, v in views.items():
             if key[0] == "sa_packed":
-                ops.sa_pack(self.sa[key[1]][2].weight.data, self.sa[key[1]][4].weight.data, v)
+                ops.sa_pack(weight(self.sa[key[1]][2]), weight(self.sa[key[1]][4]), v)
             elif key[0] == "w1f":
-                cf = self.in_feats[key[1]]
-                ops.col_blocks(v.view(-1, cf), self.sa[key[1]][0].weight.data, [(3, 3 + cf, 0)], zero_other=False)
+                ops.col_blocks(v, weight(self.sa[key[1]][0]), [(3, 3 + self.in_feats[key[1]], 0)], zero_other=False)
             elif key[0] == "dyc":
-                ops.sa_dy_consume_pack(self.sa[key[1]][0].weight.data, self.in_feats[key[1]], v)
+                ops.sa_dy_consume_pack(weight(self.sa[key[1]][0]), self.in_feats[key[1]], v)
             elif key[0] == "ga_packed":
-                ops.sa_groupall_pack(self._chains[-1].linears[-1].weight.data, v)
+                ops.sa_groupall_pack(weight(self._chains[-1].linears[-1]), v)
             elif key[0] == "ga_w0p":
-                w0 = self._ga_chain.linears[0].weight.data
-                ops.col_blocks(v.view(w0.shape[0], -1), w0, self._ga_chain.col_blocks or [(0, w0.shape[1], 0)])
+                w0 = weight(self._ga_chain.linears[0])
+                ops.col_blocks(v, w0, self._ga_chain.col_blocks or [(0, w0.shape[1], 0)])
 
     def _arena_refresh(self, device):
-        """Bring the operand copies up to date with the parameters; returns the views dict, or None when the parameters do not live
-        in one flat buffer (a network used outside ActorCritic.flat()): the callers then pack per copy as before."""
+        """Bring the operand copies up to date with the parameters (the parameters are only read); returns the views dict."""
         pf = getattr(self, "_param_flat", None)
-        first = next(self.parameters())
-        if not self.weight_arena or pf is None or pf.device != device or first.data_ptr() != pf.data_ptr() or pf.numel() >= (1 << 24):
-            return None
-        ar = getattr(self, "_arena", None)
-        if ar is None or ar["src_ptr"] != pf.data_ptr() or ar["buf"].device != device:
-            segs, off, views = self._arena_segments(), 0, {}
-            if not segs:
-                return None
-            offs = []
-            for key, n in segs:
-                offs.append((key, off, n))
-                off += (n + 63) // 64 * 64
+        gather = pf is not None and pf.device == device and pf.numel() < (1 << 24) and all(
+            0 <= p.data_ptr() - pf.data_ptr() <= 4 * (pf.numel() - p.numel()) for p in self.parameters())
+        ar = self._arena
+        if ar is None or ar["buf"].device != device or (gather and ar["src_ptr"] != pf.data_ptr()):
+            offs, off = [], 0
+            for key, shape in self._arena_segments():
+                offs.append((key, off, shape))
+                off += (math.prod(shape) + 63) // 64 * 64
             buf = torch.zeros(off, device=device)
-            views = {key: buf[o:o + n] for key, o, n in offs}
-            # record the table: parameters := their flat index + 1 (exact in fp32 below 2^24), run the entry points, read the indices back
-            saved = pf.clone()
-            pf.copy_(torch.arange(1, pf.numel() + 1, device=device, dtype=torch.float32))
-            self._arena_fill_by_entry_points(views)
-            table = buf.round().to(torch.int32) - 1                      # untouched / padding slots hold 0 -> -1 -> written as 0
-            pf.copy_(saved)
-            ar = dict(buf=buf, table=table.contiguous(), views=views, src_ptr=pf.data_ptr())
+            ar = dict(buf=buf, views={key: buf[o:o + math.prod(s)].view(s) for key, o, s in offs}, table=None, src_ptr=None)
+            if gather:
+                # the table: parameter p's slice of the buffer sits at (p - pf) // 4 and holds its flat index + 1 (exact in fp32 below
+                # 2^24); untouched / padding slots of the arena hold 0 -> -1 -> written as 0
+                idx = torch.arange(1, pf.numel() + 1, device=device, dtype=torch.float32)
+
+                def at(lin):
+                    o = (lin.weight.data_ptr() - pf.data_ptr()) // 4
+                    return idx[o:o + lin.weight.numel()].view(lin.weight.shape)
+                self._arena_fill_by_entry_points(ar["views"], at)
+                ar.update(table=(buf.round().to(torch.int32) - 1).contiguous(), src_ptr=pf.data_ptr())
             object.__setattr__(self, "_arena", ar)
-        ops.gather_copy(ar["buf"], pf, ar["table"])
+        if not gather:
+            self._arena_fill_by_entry_points(ar["views"], lambda lin: lin.weight.data)
+        elif ar["views"]:                                  # (no fused level: nothing to copy)
+            ops.gather_copy(ar["buf"], pf, ar["table"])
         return ar["views"]
 
-    def _sa_forward_fused(self, l, xyz, feat, centers, idx_g, pooled, plan_slot=None, tail_xyz=None):
-        """One fused SA level.  Layer 1's feature part is applied per SOURCE point (Y) by the Linear kernel."""
+    def _sa_forward_fused(self, l, xyz, feat, centers, idx_g, pooled, plan_slot, tail_xyz, save_h2):
+        """One fused SA level -> (its _FusedLevel record, whether the kernel also wrote the [xyz | 0] tail behind `pooled`).  Layer 1's
+        feature part is applied per SOURCE point (Y) by the Linear kernel."""
         B, Pl = xyz.shape[0], xyz.shape[1]
         lin1, lin2, lin3 = self.sa[l][0], self.sa[l][2], self.sa[l][4]
-        dims = (lin1.out_features, lin2.out_features, lin3.out_features)
+        dims = self._dims[l]
         cf = 0 if feat is None else feat.shape[2]
         Y, w1f = None, None
-        av = self._arena_views                              # operand copies refreshed by ONE gather at the top of hip_forward (or None)
+        av = self._arena_views                              # operand copies refreshed at the top of hip_forward
         if cf > 0:
             # the feature columns of W1 start 12 bytes into a row: an aligned copy (64 KB) takes the 16-byte LDS-DMA loaders
-            if av is not None:
-                w1f = av[("w1f", l)].view(dims[0], cf)
-            else:
-                w1f = ops.col_blocks(torch.empty(dims[0], cf, device=xyz.device), lin1.weight.data, [(3, 3 + cf, 0)], zero_other=False)
+            w1f = av[("w1f", l)]
             Y = torch.empty(B * Pl, dims[0], device=xyz.device)
             ops.linear_fwd(feat.reshape(B * Pl, cf), w1f, None, Y, ops.ACT_NONE)
-        if av is not None:
-            packed = av[("sa_packed", l)]
-        else:
-            packed = self._sa_packed[l]
-            if packed is None or packed.device != xyz.device:
-                packed = torch.empty(int(ops.lib.pm_sa_packed_elems(*dims)), device=xyz.device)
-                self._sa_packed[l] = packed
-            ops.sa_pack(lin2.weight.data, lin3.weight.data, packed)
-        h2 = None
-        if self._save_h2_now:                              # training forward: keep layer 2 for the backward (reused buffer)
-            n = idx_g.numel() * dims[1]
-            buf = self._sa_h2[l]
-            if buf is None or buf.numel() < n or buf.device != xyz.device:
-                buf = self._sa_h2[l] = torch.empty(n, device=xyz.device)
-            h2 = buf[:n]
+        packed = av[("sa_packed", l)]
+        # training forward: keep layer 2 for the backward (reused buffer)
+        h2 = self._scratch(f"_sa_h2_{l}", idx_g.numel() * dims[1], xyz.device) if save_h2 else None
         plan = None
         if self._uses_plan(l, centers.shape[1]):               # (more than 1024 groups per cloud: the padded kernels)
-            cache, key = plan_slot if plan_slot is not None else (None, None)
-            if key is not None:
-                key = key + (dims,)                        # tile sizes follow the level's widths: actor and critic share a plan only when theirs agree
+            cache, key = plan_slot or (None, None)
             plan = cache.get(key) if cache is not None else None
             if plan is None:
                 plan = ops.sa_plan(idx_g, xyz, centers, dims, self._workspace(xyz.device), inverse=self._plan_inverse(l))
@@ -659,7 +672,8 @@ class PointNet2(_HipNet):
         else:
             arg = ops.sa_fwd(xyz, centers, idx_g, Y, lin1.weight.data, lin1.bias.data, lin2.bias.data, lin3.bias.data,
                              packed, dims, pooled, h2)
-        return (idx_g, arg, "fused", xyz, feat, centers, Y, packed, dims, pooled, h2, plan, w1f, plan is not None and tail_xyz is not None)
+        rec = _FusedLevel(idx_g, arg, xyz, feat, centers, Y, packed, pooled, h2, plan, w1f)
+        return rec, plan is not None and tail_xyz is not None
 
     PLAN_BATCH = 4                        # mini-batch slices whose plans are built before one host read trims them
 
@@ -671,9 +685,15 @@ class PointNet2(_HipNet):
         """Does level l's plan carry the source point -> packed rows table (its layer-1 rows have a gradient to sum)?"""
         return bool(self.sa_deterministic and self.in_feats[l] > 0)
 
+    def _plan_key(self, l, lo, n):
+        """Key of level l's plan for the (lo, n) row slice in _GeomTabs.plans.  Tile sizes follow the level's widths: actor and
+        critic share a plan only when theirs agree."""
+        return l, lo, n, self._dims[l]
+
     def _sa_backward_fused(self, l, rec, dpooled, ws, need_dfeat):
-        idx_g, arg, _, xyz, feat, centers, Y, packed, dims, pooled, h2, plan, w1f = rec[:13]
+        xyz, feat, plan = rec.xyz, rec.feat, rec.plan
         B, Pl = xyz.shape[0], xyz.shape[1]
+        dims = self._dims[l]
         lin1, lin2, lin3 = self.sa[l][0], self.sa[l][2], self.sa[l][4]
         (dW1, db1), (dW2, db2), (dW3, db3) = self._chains[l].grads
         cf = 0 if feat is None else feat.shape[2]
@@ -681,44 +701,34 @@ class PointNet2(_HipNet):
         fused_dy = det and self.sa_fused_dy and ops.sa_dy_consume_supported(dims[0], cf)
         dY = None if (cf == 0 or fused_dy) else torch.empty(B * Pl, dims[0], device=xyz.device) if det else torch.zeros(B * Pl, dims[0], device=xyz.device)
         if det:
-            n = plan.rowmap.shape[0] * dims[0]             # (R, C1) once the plan is trimmed, its capacity before
-            buf = self._sa_dz1[l]
-            if buf is None or buf.numel() < n or buf.device != xyz.device:
-                buf = self._sa_dz1[l] = torch.empty(n, device=xyz.device)
-            dz1 = buf[:n].view(-1, dims[0])
-            ops.sa_bwd_packed(plan, Y, lin1.weight.data, lin1.bias.data, lin2.bias.data, lin3.weight.data,
-                              packed, dims, pooled, arg, dpooled, dW1, db1, dW2, db2, dW3, db3, None, ws, h2, dz1=dz1)
+            # (R, C1) once the plan is trimmed, its capacity before
+            dz1 = self._scratch(f"_sa_dz1_{l}", plan.rowmap.shape[0] * dims[0], xyz.device).view(-1, dims[0])
+            ops.sa_bwd_packed(plan, rec.Y, lin1.weight.data, lin1.bias.data, lin2.bias.data, lin3.weight.data,
+                              rec.packed, dims, rec.pooled, rec.arg, dpooled, dW1, db1, dW2, db2, dW3, db3, None, ws, rec.h2, dz1=dz1)
             if fused_dy:
                 # the sums are consumed where they are formed: dfeat = dY W1f and dW1[:, 3:3+cf] = dY^T feat in ONE launch, dY in LDS only
-                av = self._arena_views
-                if av is not None:
-                    pw = av[("dyc", l)]
-                else:
-                    pw = self._sa_packed_w1f[l]
-                    if pw is None or pw.device != xyz.device:
-                        pw = self._sa_packed_w1f[l] = torch.empty(int(ops.lib.pm_sa_dy_consume_packed_elems(dims[0], cf)), device=xyz.device)
-                    ops.sa_dy_consume_pack(lin1.weight.data, cf, pw)
                 dfeat = torch.empty(B * Pl, cf, device=xyz.device) if need_dfeat else None
-                return ops.sa_dy_consume(plan, dz1, feat.reshape(B * Pl, cf), pw, dfeat, dW1, ws)
+                return ops.sa_dy_consume(plan, dz1, feat.reshape(B * Pl, cf), self._arena_views[("dyc", l)], dfeat, dW1, ws)
             ops.sa_dy_segsum(plan, dz1, dY)
         elif plan is not None:
-            ops.sa_bwd_packed(plan, Y, lin1.weight.data, lin1.bias.data, lin2.bias.data, lin3.weight.data,
-                              packed, dims, pooled, arg, dpooled, dW1, db1, dW2, db2, dW3, db3, dY, ws, h2, zero_pad_cols=cf == 0)
+            ops.sa_bwd_packed(plan, rec.Y, lin1.weight.data, lin1.bias.data, lin2.bias.data, lin3.weight.data,
+                              rec.packed, dims, rec.pooled, rec.arg, dpooled, dW1, db1, dW2, db2, dW3, db3, dY, ws, rec.h2,
+                              zero_pad_cols=cf == 0)
         else:
-            ops.sa_bwd(xyz, centers, idx_g, Y, lin1.weight.data, lin1.bias.data, lin2.bias.data, lin3.weight.data, packed,
-                       dims, pooled, arg, dpooled, dW1, db1, dW2, db2, dW3, db3, dY, ws, h2)
+            ops.sa_bwd(xyz, rec.centers, rec.idx, rec.Y, lin1.weight.data, lin1.bias.data, lin2.bias.data, lin3.weight.data,
+                       rec.packed, dims, rec.pooled, rec.arg, dpooled, dW1, db1, dW2, db2, dW3, db3, dY, ws, rec.h2)
         if cf == 0:
             if dW1.shape[1] > 3 and plan is None:          # (packed levels: the reduction launch zeroes them)
                 ops.col_blocks(dW1, None, [], col0=3)      # pad columns never receive data (zero-only form)
             return None
         feat2 = feat.reshape(B * Pl, cf)
-        dW1f = torch.empty_like(w1f)
+        dW1f = torch.empty_like(rec.w1f)
         ops.linear_bwd_weight(dY, feat2, dW1f, None, ws)
         ops.col_blocks(dW1, dW1f, [(0, cf, 3)], col0=3)    # the feature columns' gradient in place, zeros in the pad columns
         if not need_dfeat:
             return None
         dfeat = torch.empty(B * Pl, cf, device=xyz.device)
-        ops.linear_bwd_data(dY, w1f, None, dfeat, ops.ACT_NONE)
+        ops.linear_bwd_data(dY, rec.w1f, None, dfeat, ops.ACT_NONE)
         return dfeat
 
     # ---- neighbourhood tables ------------------------------------------------------------------------
@@ -772,13 +782,11 @@ class PointNet2(_HipNet):
             for l, S in enumerate(self.npoints):
                 centers, idx_g = tabs[l][0][lo:lo + n], tabs[l][1][lo:lo + n]
                 if self._uses_plan(l, S):
-                    lin1, lin2, lin3 = self.sa[l][0], self.sa[l][2], self.sa[l][4]
-                    dims = (lin1.out_features, lin2.out_features, lin3.out_features)
-                    key = (l, lo, n, dims)
+                    key = self._plan_key(l, lo, n)
                     if key not in tabs.plans and key not in {k for k, _ in built}:
                         if xyz is None:
                             xyz = obs[lo:lo + n, :P * C].reshape(n, P, C)[..., :3].contiguous() if l == 0 else tabs[l - 1][0][lo:lo + n]
-                        built.append((key, ops.sa_plan(idx_g, xyz, centers, dims, ws, inverse=self._plan_inverse(l))))
+                        built.append((key, ops.sa_plan(idx_g, xyz, centers, self._dims[l], ws, inverse=self._plan_inverse(l))))
                 xyz = centers
             if (k_ + 1) % self.PLAN_BATCH == 0:
                 flush()
@@ -789,7 +797,7 @@ class PointNet2(_HipNet):
         plans = getattr(tabs, "plans", None)
         if isinstance(rows, tuple):
             lo, n = rows
-            sel = [(c[lo:lo + n], i[lo:lo + n], None if plans is None else (plans, (l, lo, n))) for l, (c, i) in enumerate(tabs)]
+            sel = [(c[lo:lo + n], i[lo:lo + n], None if plans is None else (plans, self._plan_key(l, lo, n))) for l, (c, i) in enumerate(tabs)]
         else:
             r = rows.to(tabs[0][0].device, non_blocking=True)
             sel = [(c.index_select(0, r), i.index_select(0, r), None) for c, i in tabs]
@@ -801,7 +809,7 @@ class PointNet2(_HipNet):
 
     def hip_forward(self, x, out=None, save_h2=None):
         B, P, C = x.shape[0], self.point_num, self.in_channels
-        object.__setattr__(self, "_save_h2_now", self.save_h2 if save_h2 is None else save_h2)
+        save_h2 = self.save_h2 if save_h2 is None else save_h2
         ws = self._workspace(x.device)
         pts = x[:, :P * C].reshape(B, P, C)
         xyz = pts[..., :3].contiguous()
@@ -810,14 +818,9 @@ class PointNet2(_HipNet):
         object.__setattr__(self, "_geom_next", None)
         if geom is not None and geom[0][0].shape[0] != B:
             raise ValueError("use_geometry(): table rows do not match the batch")
-        saved, ga_rows = [], None
-        object.__setattr__(self, "_arena_views", self._arena_refresh(x.device))
-        if self._arena_views is not None and ("ga_w0p",) in self._arena_views:
-            w0 = self._ga_chain.linears[0].weight
-            self._ga_chain.w0p_ext = self._arena_views[("ga_w0p",)].view(w0.shape[0], -1)
-        elif self._ga_chain is not None:
-            self._ga_chain.w0p_ext = None
-        tail_done = False
+        saved, ga_rows, tail_done = [], None, False
+        av = self._arena_refresh(x.device)
+        object.__setattr__(self, "_arena_views", av)
         for l, S in enumerate(self.npoints):
             plan_slot = None
             if geom is not None:
@@ -834,9 +837,9 @@ class PointNet2(_HipNet):
                 else:
                     pooled = torch.empty(B * S, c3, device=x.device)
                 direct_rows = self._ga_direct and l == len(self.npoints) - 1
-                saved.append(self._sa_forward_fused(l, xyz, feat, centers, idx_g, pooled, plan_slot,
-                                                    tail_xyz=centers.reshape(B * S, 3) if direct_rows else None))
-                tail_done = tail_done or (direct_rows and saved[-1][13])
+                rec, tail_done = self._sa_forward_fused(l, xyz, feat, centers, idx_g, pooled, plan_slot,
+                                                        centers.reshape(B * S, 3) if direct_rows else None, save_h2)
+                saved.append(rec)
                 xyz, feat = centers, pooled.view(B, S, -1)
                 continue
             ldo = self.sa[l][0].in_features
@@ -844,7 +847,7 @@ class PointNet2(_HipNet):
             h = self._chains[l].forward(rows)
             pooled = torch.empty(B * S, h.shape[1], device=x.device)
             arg = ops.maxpool_rows(h, B * S, self.nsamples[l], pooled)
-            saved.append((idx_g, arg, h, xyz.shape[1], 0 if feat is None else feat.shape[2], ldo))
+            saved.append(_UnfusedLevel(idx_g, arg, h, xyz.shape[1], 0 if feat is None else feat.shape[2], ldo))
             xyz, feat = centers, pooled.view(B, S, -1)
         S = xyz.shape[1]                                   # group-all level: absolute coordinates
         ldo = (self.sa[-1][0].in_features + 31) // 32 * 32     # zero columns up to the GEMM's K-step (the chain pads its weights alike)
@@ -858,22 +861,14 @@ class PointNet2(_HipNet):
             rows = ops.group_concat(xyz, feat, zeros, idx_all, ldo)
         fbuf = torch.empty(B, self.feat_dim + self.proprio_shape, device=x.device)
         if self._ga_fused:
-            h = self._ga_chain.forward(rows)               # (B*S, CK): the layers before the last, tanh applied
-            lin = self._chains[-1].linears[-1]
-            if self._arena_views is not None:
-                packed = self._arena_views[("ga_packed",)]
-            else:
-                packed = self._ga_packed
-                if packed is None or packed.device != x.device:
-                    packed = torch.empty(int(ops.lib.pm_sa_groupall_packed_elems(lin.in_features, lin.out_features)), device=x.device)
-                    object.__setattr__(self, "_ga_packed", packed)
-                ops.sa_groupall_pack(lin.weight.data, packed)
-            arg = ops.sa_groupall_fwd(h, B, S, lin.bias.data, packed, fbuf[:, :self.feat_dim])
-            saved.append((idx_all, arg, "groupall", S, feat.shape[2], ldo, h, fbuf))
+            h = self._ga_chain.forward(rows, w0p=av.get(("ga_w0p",)))     # (B*S, CK): the layers before the last, tanh applied
+            pooled = fbuf[:, :self.feat_dim]
+            arg = ops.sa_groupall_fwd(h, B, S, self._chains[-1].linears[-1].bias.data, av[("ga_packed",)], pooled)
+            saved.append(_GroupAllLevel(idx_all, arg, h, S, feat.shape[2], ldo, pooled))
         else:
             h = self._chains[-1].forward(rows)
             arg = ops.maxpool_rows(h, B, S, fbuf[:, :self.feat_dim])
-            saved.append((idx_all, arg, h, S, feat.shape[2], ldo))
+            saved.append(_UnfusedLevel(idx_all, arg, h, S, feat.shape[2], ldo))
         if self.proprio_shape != 0:
             fbuf[:, self.feat_dim:].copy_(x[:, -self.proprio_shape:])
         object.__setattr__(self, "_saved", saved)
@@ -886,31 +881,22 @@ class PointNet2(_HipNet):
         self._head.backward(dy, ws, dx_out=dfbuf)
         dpooled = dfbuf[:, :self.feat_dim]                 # (G, C) view with row stride feat_dim + proprio
         for l in reversed(range(len(saved))):
-            if isinstance(saved[l][2], str) and saved[l][2] == "groupall":
-                idx_g, arg, _, P_l, cf, ldo, h, fbuf = saved[l]
-                lin = self._chains[-1].linears[-1]
+            rec, need_dx = saved[l], l > 0                # level-0 inputs are data: no gradient flows to them
+            if isinstance(rec, _FusedLevel):
+                dpooled = self._sa_backward_fused(l, rec, dpooled, ws, need_dfeat=need_dx)
+                continue
+            direct = rec.idx is None                       # the rows are [features | xyz | 0]: only the feature block's gradient is wanted
+            drows = torch.empty(rec.h.shape[0], rec.cf if direct else rec.ldo, device=dy.device) if need_dx else None
+            if isinstance(rec, _GroupAllLevel):
                 dW, db = self._chains[-1].grads[-1]
-                dh = torch.empty_like(h)
-                ops.sa_groupall_bwd(dpooled, fbuf[:, :self.feat_dim], arg, lin.weight.data, h, B, P_l, dh, dW, db, ws)
-                direct = idx_g is None                     # the rows are [features | xyz | 0]: only the feature block's gradient is wanted
-                drows = torch.empty(h.shape[0], cf if direct else ldo, device=dy.device) if l > 0 else None     # level-0 inputs are data
-                self._ga_chain.backward(dh, ws, dx_out=drows, dx_cols=cf if (direct and l > 0) else None)
-                if l > 0:
-                    dpooled = drows if direct else ops.group_concat_bwd(drows, idx_g, B, P_l, cf, ldo).view(B * P_l, cf)
-                continue
-            if isinstance(saved[l][2], str):                 # fused level record
-                # level-0 features are data: no gradient flows to them
-                dpooled = self._sa_backward_fused(l, saved[l], dpooled, ws, need_dfeat=l > 0)
-                continue
-            idx_g, arg, h, P_l, cf, ldo = saved[l]
-            ns = idx_g.shape[2]
-            dh = ops.maxpool_rows_bwd(dpooled, arg, ns, y_tanh=h)      # max-pool + tanh' of the chain output
-            need_dx = l > 0                                               # level-0 inputs are data, not activations
-            drows = torch.empty(h.shape[0], ldo, device=dy.device) if need_dx else None
-            self._chains[l].backward(dh, ws, dx_out=drows)
+                dh = torch.empty_like(rec.h)
+                ops.sa_groupall_bwd(dpooled, rec.pooled, rec.arg, self._chains[-1].linears[-1].weight.data, rec.h, B, rec.P, dh, dW, db, ws)
+                self._ga_chain.backward(dh, ws, dx_out=drows, dx_cols=rec.cf if direct else None)
+            else:
+                dh = ops.maxpool_rows_bwd(dpooled, rec.arg, rec.idx.shape[2], y_tanh=rec.h)      # max-pool + tanh' of the chain output
+                self._chains[l].backward(dh, ws, dx_out=drows)
             if need_dx:
-                dpooled = ops.group_concat_bwd(drows, idx_g, B, P_l, cf, ldo).view(B * P_l, cf)
-
+                dpooled = drows if direct else ops.group_concat_bwd(drows, rec.idx, B, rec.P, rec.cf, rec.ldo).view(B * rec.P, rec.cf)
 
 class SparseUNet(_HipNet):
     """3D sparse-voxel U-Net encoder as a backbone plug-in (`network.name: SparseUNet`).

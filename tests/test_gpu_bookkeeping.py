@@ -143,13 +143,14 @@ def test_col_blocks_copies_permuted_blocks_and_zero_fills():
     assert torch.equal(big, before)
 
 
-def test_gather_copy_and_the_pointnet2_weight_arena_equal_the_per_copy_entry_points():
+def test_gather_copy_and_the_pointnet2_weight_arena_equal_the_entry_point_fill():
     """pm_gather_copy_f32 (dst[q] = src[table[q]], 0 where table[q] < 0) and its use: every weight-derived operand copy of a
     PointNet2 network (two pm_sa_pack_weights_f32 outputs, the aligned W1 feature block, the consumer's operand copy, the group-all
     pack, the K-step-padded first group-all layer) refreshed by ONE gather whose table was recorded by running those entry points on
-    index-valued weights.  Outputs, arg-max tables and every parameter gradient of a forward + backward must be BIT-identical to the
-    per-copy path (`weight_arena: False`), before and after the parameters change in place (an optimiser step), and the arena must
-    hold exactly what the entry points write."""
+    an index-valued copy of the flat parameter buffer -- recording it must not write the parameters.  Outputs, arg-max tables and
+    every parameter gradient of a forward + backward must be BIT-identical to the entry-point path (a network whose parameters are
+    not in one flat buffer), before and after the parameters change in place (an optimiser step), and the arena must hold exactly
+    what the entry points write."""
     o = ops()
     g = torch.Generator(device=DEV).manual_seed(3)
     src = torch.randn(1000, device=DEV, generator=g)
@@ -167,22 +168,26 @@ def test_gather_copy_and_the_pointnet2_weight_arena_equal_the_per_copy_entry_poi
     dy = torch.randn(B, A, device=DEV, generator=g)
     res = {}
     for arena in (True, False):
-        net = dict(name="PointNet2", activation="tanh", weight_arena=arena)
+        net = dict(name="PointNet2", activation="tanh")
         sd = cases.actor_critic_state(net, 3 * P, A, 0.5, 21)
         ac = ActorCritic(3 * P, A, dict(action_std=0.5, action_activate="tanh", clipAction=1.0, network=net)).to(DEV)
         ac.load_state_dict({k: t(v.copy()) for k, v in sd.items()})
         f = ac.flat()
+        if not arena:
+            object.__setattr__(ac.actor, "_param_flat", None)       # parameters not known to be in one flat buffer: entry points
         outs = []
         for step in range(2):
+            version = f["actor"]._version
             out = ac.actor.hip_forward(x)
-            assert (ac.actor._arena_views is not None) == arena
+            assert (ac.actor._arena["table"] is not None) == arena
+            assert f["actor"]._version == version                  # the first forward records the table: the parameters are only read
             ac.actor.hip_backward(dy)
             outs.append((out.clone(), [s_[1].clone() for s_ in ac.actor._saved], f["grad_actor"][:f["n_actor"]].clone()))
             if arena:                                          # the arena holds exactly what the entry points write
                 views = ac.actor._arena_views
                 assert {k[0] for k in views} == {"sa_packed", "w1f", "dyc", "ga_packed", "ga_w0p"}
                 ref = {k: torch.full_like(v, float("nan")) for k, v in views.items()}
-                ac.actor._arena_fill_by_entry_points(ref)
+                ac.actor._arena_fill_by_entry_points(ref, lambda lin: lin.weight.data)
                 for k in views:
                     assert torch.equal(views[k], ref[k]), k
             f["actor"][:f["n_actor"]].add_(0.01 * torch.sin(torch.arange(f["n_actor"], device=DEV, dtype=torch.float32)))   # "an optimiser step"
