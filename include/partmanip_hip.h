@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 152 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 153 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -483,6 +483,23 @@ int pm_col2im3d_f32(const float* dcols, int B, int C, int D, int H, int W, int k
  * depth2tsdf.py:41-60).  trunc = 4 voxels; default_tsdf for voxels no view sees. */
 int pm_tsdf_integrate_f32(const float* depth, const int32_t* pix_idx, const float* pix_z, int B, int M, long HW,
                           long V, float trunc, float default_tsdf, float* out, void* stream);
+
+/* ------------------------------------------------------------------ mesh-TSDF observation (observation side)
+ * utils/mesh2sdf.py:119-132, 239-272 `TSDFfromMesh.query_tsdf_parallel` in one launch: for every environment b and workspace
+ * voxel v (centre (i, j, k) * vox_size + origin, k fastest) the signed-distance grids of the parts [p0, p1) are sampled
+ * trilinearly under the parts' poses (q = (c_v - T[b,p]) R[b,p]; valid iff 1 <= (q - bbox_min[p]) / voxel_size[p] <= shape[p] - 2
+ * on all three axes, else the sample is 1), out[b * out_stride + v] = clamp(min(min_p sample, base) / sdf_trunc, -1, 1).
+ * fields: the parts' grids (X, Y, Z row-major, un-padded) concatenated; part_off (M) int64 element offsets into it; part_shape
+ * (M, 3) int32 (every grid < 2^31 cells); part_bbox_min (M, 3); part_voxel_size (M); pose_R (B, M, 3, 3); pose_T (B, M, 3).
+ * base: (res^3) shared by all environments (base_per_env = 0: the ground plane) or (B, res^3) (base_per_env = 1: after
+ * initialize_sdf).  out_stride >= res^3 in elements: the volume can land in the left part of an observation row.  brick_skip != 0
+ * drops a part for a whole 4^3 brick of voxels when the brick cannot reach the part's valid box (bit-identical output, faster).
+ * An environment with a non-finite pose entry (any of its M parts) comes out all-NaN; nothing is ever read out of bounds.
+ * PM_EINVAL: a NULL pointer, B outside [1, 65535], p0 >= p1, p1 > M, res <= 0, out_stride < res^3, sdf_trunc <= 0. */
+int pm_mesh_tsdf_query_f32(const float* fields, const int64_t* part_off, const int32_t* part_shape, const float* part_bbox_min,
+                           const float* part_voxel_size, const float* pose_R, const float* pose_T, int B, int M, int p0, int p1,
+                           int res, float vox_size, float ox, float oy, float oz, float sdf_trunc, const float* base,
+                           int base_per_env, float* out, long out_stride, int brick_skip, void* stream);
 
 /* ------------------------------------------------------------------ K15 fused set-abstraction level
  * One PointNet++ SA level (north_star; not in the reference snapshot, README.md:23,30) as one forward and

@@ -1,0 +1,159 @@
+"""The 'mesh_tsdf' observation (`obs_mode: 'mesh_tsdf'` of cfg/algos/dagger_tsdf.yaml and bc.yaml), mirroring the reference's
+`utils/mesh2sdf.py:TSDFfromMesh` for the part that runs every environment step:
+
+    tsdf = TSDFfromMesh(num_envs, size, resolution, device, vox_origin=...)        # mesh2sdf.py:16-54
+    vol = tsdf.query_tsdf(pose_R (b, m, 3, 3), pose_T (b, m, 3))  -> (b, res, res, res)   # mesh2sdf.py:89-93, 119-139
+    scene, obj = tsdf.query_tsdf_seperately(pose_R, pose_T)                               # mesh2sdf.py:95-117
+
+The pre-baked signed-distance grid of every rigid part (eight Franka links, hand, two fingers, the object) is sampled
+trilinearly at each workspace voxel under the part's pose; the minimum over the parts and the ground plane, divided by the
+truncation distance and clamped to [-1, 1], is the volume.  One launch of pm_mesh_tsdf_query_f32 (csrc/mesh_tsdf.hip) does
+that: the reference's (b, m, n, 3) / (b, m, n) intermediates (6 MB per environment each) never exist, and with `out=` the
+volume is written straight into the left part of an (N, res^3 + proprio) observation buffer (the reference reshapes and
+concatenates, tasks/grasp_cube.py:131,137).
+
+The grids are NOT padded to a common shape (mesh2sdf.py:181-184 pads with 1s that are never read: validity is tested against
+each part's own shape): `merge_sdf_field` keeps one flat buffer of concatenated grids and per-part tables of offset, shape,
+bbox_min and voxel_size.  Baking a grid from a mesh (kaolin, ManifoldPlus: mesh2sdf.py:158-167, 201-237), marching cubes and
+the debug dumps are outside this build's scope: they raise NotImplementedError.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+
+FRANKA_SDF_DIR = os.path.join("assets", "franka_description", "sdf", "visual")       # mesh2sdf.py:43,148-154
+FRANKA_PARTS = [f"link{i}" for i in range(8)] + ["hand", "finger", "finger"]       # mesh2sdf.py:142-145
+OBJ_SDF_PATH = os.path.join("assets", "objs", "cube", "sdf.npy")                     # mesh2sdf.py:48
+
+
+class TSDFfromMesh:
+    """Constructor of the reference plus two keyword extensions: `sdf_dicts` (a list of {'sdf': (X,Y,Z) float32, 'bbox_min':
+    (3,), 'voxel_size': float} used instead of reading the pre-stored files) and `asset_root` (prefix of the reference's relative
+    paths assets/franka_description/sdf/visual/*.npy and assets/objs/cube/sdf.npy).  `vox_origin` may be None, a tensor or the
+    yaml's list (the reference raises TypeError on a list, tasks/hand_base.py passes one).
+    `parallel=False` is served by the same kernel: the reference's own naive path (query_tsdf_naive ->
+    triplet_interpolation_query) indexes a 3-D field with a flat index and cannot run; the parallel path is the specification."""
+
+    def __init__(self, num_envs, size, resolution, device, parallel=True, debug=False, vox_origin=None, sdf_dicts=None,
+                 asset_root='.'):
+        if debug:
+            raise NotImplementedError("debug dumps (surface points / marching cubes) are outside this build's scope (DESIGN.md)")
+        self.num_envs = num_envs
+        self.parallel = parallel
+        self.device = device
+        self.debug = debug
+        self.asset_root = asset_root
+
+        self.resolution = resolution
+        self.size = size
+        self.vox_size = self.size / self.resolution
+        self.sdf_trunc = 4 * self.vox_size
+        if vox_origin is None:
+            self.vox_origin = torch.tensor([-0.25, -0.25, -0.0503], device=self.device)
+        else:
+            self.vox_origin = torch.as_tensor(vox_origin, dtype=torch.float32).to(self.device)
+        self._origin3 = [float(v) for v in self.vox_origin.cpu().tolist()]          # host copy: no device read per query
+
+        # queried points of the workspace, with the reference's own tensor expressions (mesh2sdf.py:29-37)
+        tmp = torch.arange(0, self.resolution)
+        xv, yv, zv = torch.meshgrid(tmp, tmp, tmp, indexing="ij")
+        vox_coords = torch.stack([xv.flatten(), yv.flatten(), zv.flatten()], dim=1).long().to(self.device)
+        self.vox_coords = vox_coords * self.vox_size + self.vox_origin             # [n, 3]
+        self.point_num = self.vox_coords.shape[0]
+        # the ground plane: the voxel's world z.  The reference repeats it per environment (2 GB at 4096); same shape and
+        # values here, as a broadcast view of one row (the kernel takes the row)
+        self._ground = self.vox_coords[:, -1].contiguous()
+        self.init_tsdf = self._ground.unsqueeze(0).expand(self.num_envs, -1)       # [b, n]
+        self.ground_tsdf = self._ground.unsqueeze(0).expand(self.num_envs, -1)     # [b, n]
+        self._init_base = self._ground                                             # (n,) or, after initialize_sdf, (b, n)
+
+        self.pre_store_sdf_trunc = self.sdf_trunc
+        self.pre_store_sdf_voxel_size = 0.002
+        self.sdf_dict_list = []
+        if sdf_dicts is not None:
+            self.sdf_dict_list.extend(sdf_dicts)
+        else:
+            self.load_franka(os.path.join(asset_root, "assets", "franka_description"))
+            self.load_sdf(os.path.join(asset_root, OBJ_SDF_PATH), os.path.join(asset_root, "assets", "objs", "cube", "cube.obj"))
+        self.merge_sdf_field()
+
+    # ------------------------------------------------------------------------------------------------ loading
+    def load_franka(self, hand_base_path):
+        """Parts in the reference's order: link0..link7, hand, finger, finger (mesh2sdf.py:141-156)."""
+        for name in FRANKA_PARTS:
+            self.load_sdf(os.path.join(hand_base_path, "sdf", "visual", name + ".npy"))
+
+    def load_sdf(self, sdf_path, mesh_path=None, preprocess_path=None):
+        """Pre-stored grid -> appended to `sdf_dict_list` (mesh2sdf.py:70-73, 82).  An absent file would be baked from the mesh
+        by the reference (kaolin point_to_mesh_distance / check_sign after ManifoldPlus): not in this build."""
+        if not os.path.exists(sdf_path):
+            raise NotImplementedError(f"{sdf_path} is missing: baking a signed-distance grid from a mesh (kaolin, mesh2sdf.py:201-237) "
+                                      "is outside this build's scope (DESIGN.md); bake it with the reference and pass the file")
+        sdf_dict = np.load(sdf_path, allow_pickle=True).item()
+        self.sdf_dict_list.append(sdf_dict)
+
+    def mesh2sdf(self, mesh_path):
+        raise NotImplementedError("baking a signed-distance grid from a mesh (kaolin) is outside this build's scope (DESIGN.md)")
+
+    def preprocess_mesh(self, input_mesh_path, output_mesh_path):
+        raise NotImplementedError("ManifoldPlus preprocessing is outside this build's scope (DESIGN.md)")
+
+    def visualize(self, sdf_field, voxel_size, bbox_min, save_path):
+        raise NotImplementedError("marching cubes is outside this build's scope (DESIGN.md)")
+
+    def extract_surface_points_from_volume(self, vol, save_path):
+        raise NotImplementedError("debug dumps are outside this build's scope (DESIGN.md)")
+
+    def merge_sdf_field(self):
+        """One flat buffer of the concatenated (un-padded) grids + per-part tables, on `device`:
+        sdf_field (sum X*Y*Z), sdf_field_off (m) int64, sdf_field_res (m, 3) int32, sdf_bbox_min (m, 3), sdf_voxel_size (m)."""
+        self.part_num = len(self.sdf_dict_list)
+        grids = [np.ascontiguousarray(d['sdf'], dtype=np.float32) for d in self.sdf_dict_list]
+        for g in grids:
+            if g.ndim != 3 or g.size >= 2 ** 31:
+                raise ValueError(f"a part's 'sdf' must be a 3-D grid of fewer than 2^31 cells, got shape {g.shape}")
+        sizes = np.array([g.size for g in grids], dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        self.sdf_field = torch.from_numpy(np.concatenate([g.reshape(-1) for g in grids])).to(self.device)
+        self.sdf_field_off = torch.from_numpy(off).to(self.device)
+        self.sdf_field_res = torch.tensor([list(g.shape) for g in grids], dtype=torch.int32).to(self.device)
+        self.sdf_bbox_min = torch.tensor(np.stack([np.asarray(d['bbox_min'], dtype=np.float32).reshape(3) for d in self.sdf_dict_list]),
+                                         dtype=torch.float32).to(self.device)
+        self.sdf_voxel_size = torch.tensor([float(d['voxel_size']) for d in self.sdf_dict_list], dtype=torch.float32).to(self.device)
+
+    # ------------------------------------------------------------------------------------------------ queries
+    def initialize_sdf(self, nerf_pred_tsdf):
+        """pred_tsdf [b, n] in truncation units replaces the ground plane as the scene's base field (mesh2sdf.py:57-61)."""
+        self.init_tsdf = torch.as_tensor(nerf_pred_tsdf, dtype=torch.float32).to(self.device) * self.sdf_trunc
+        self._init_base = self.init_tsdf.reshape(self.num_envs, self.point_num).contiguous()
+
+    def _query(self, pose_R, pose_T, p0, p1, base, out, brick_skip=True):
+        pose_R = pose_R.to(torch.float32).reshape(-1, self.part_num, 3, 3).contiguous()
+        pose_T = pose_T.to(torch.float32).reshape(-1, self.part_num, 3).contiguous()
+        n = self.point_num
+        if base.dim() == 2 and base.shape[0] != pose_R.shape[0]:
+            raise ValueError(f"initialize_sdf was given {base.shape[0]} environments, the poses have {pose_R.shape[0]}")
+        res = ops.mesh_tsdf_query(self.sdf_field, self.sdf_field_off, self.sdf_field_res, self.sdf_bbox_min, self.sdf_voxel_size,
+                                  pose_R, pose_T, self.resolution, self.vox_size, self._origin3, self.sdf_trunc, base,
+                                  p0, p1, out, brick_skip)
+        r = self.resolution
+        return res[:, :n].unflatten(1, (r, r, r))
+
+    def query_tsdf(self, pose_R, pose_T, out=None, brick_skip=True):
+        """pose_R [b, m, 3, 3], pose_T [b, m, 3] -> [b, res, res, res].  out: None, or a 2-D float32 view (b, >= res^3) with
+        unit inner stride (e.g. obs[:, :res^3] of an observation buffer); the result is then a view of its first res^3 columns.
+        brick_skip=False turns the brick-level part rejection off (same bits, slower; for tests)."""
+        return self._query(pose_R, pose_T, 0, self.part_num, self._init_base, out, brick_skip)
+
+    query_tsdf_parallel = query_tsdf
+    query_tsdf_naive = query_tsdf          # the reference's naive path cannot run (class docstring); same kernel
+
+    def query_tsdf_seperately(self, pose_R, pose_T, out_scene=None, out_obj=None):
+        """(scene, obj): the parts before the last against the base field, and the last part (the object) alone against the
+        ground plane (mesh2sdf.py:95-117); min(scene, obj) == query_tsdf bit for bit.  Two launches over part ranges."""
+        scene = self._query(pose_R, pose_T, 0, self.part_num - 1, self._init_base, out_scene)
+        obj = self._query(pose_R, pose_T, self.part_num - 1, self.part_num, self._ground, out_obj)
+        return scene, obj

@@ -1232,6 +1232,50 @@ def tsdf_integrate(depth, pix_idx, pix_z, trunc, default_tsdf):
     return out
 
 
+def mesh_tsdf_query(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, res, vox_size, origin,
+                    sdf_trunc, base, p0=0, p1=None, out=None, brick_skip=True):
+    """The mesh-TSDF observation of parts [p0, p1) (pm_mesh_tsdf_query_f32): fields (flat float32), part_off (M) int64,
+    part_shape (M,3) int32, part_bbox_min (M,3), part_voxel_size (M), pose_R (B,M,3,3), pose_T (B,M,3), origin = 3 floats,
+    base (res^3) or (B, res^3).  out: None (a fresh (B, res^3)) or a 2-D float32 view (B, >= res^3) with unit inner stride --
+    columns past res^3 are left alone.  Returns out."""
+    _req(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, base, out)
+    for t_, name in ((fields, "fields"), (part_bbox_min, "part_bbox_min"), (part_voxel_size, "part_voxel_size"),
+                     (pose_R, "pose_R"), (pose_T, "pose_T"), (base, "base")):
+        _f32c(t_, name)
+    if part_off.dtype != torch.int64 or not part_off.is_contiguous():
+        raise ValueError("part_off: expected a contiguous int64 tensor")
+    _i32c(part_shape, "part_shape")
+    M = part_off.numel()
+    if pose_R.dim() != 4 or tuple(pose_R.shape[1:]) != (M, 3, 3):
+        raise ValueError(f"pose_R: expected (B, {M}, 3, 3), got {tuple(pose_R.shape)}")
+    B = pose_R.shape[0]
+    if tuple(pose_T.shape) != (B, M, 3):
+        raise ValueError(f"pose_T: expected ({B}, {M}, 3), got {tuple(pose_T.shape)}")
+    if tuple(part_shape.shape) != (M, 3) or tuple(part_bbox_min.shape) != (M, 3) or part_voxel_size.numel() != M:
+        raise ValueError("part tables: expected part_shape (M,3), part_bbox_min (M,3), part_voxel_size (M)")
+    n = int(res) ** 3
+    if tuple(base.shape) == (n,):
+        per_env = 0
+    elif tuple(base.shape) == (B, n):
+        per_env = 1
+    else:
+        raise ValueError(f"base: expected ({n},) or ({B}, {n}), got {tuple(base.shape)}")
+    if out is None:
+        out = torch.empty(B, n, dtype=torch.float32, device=pose_R.device)
+    ldo = _rows(out, "out")
+    if out.shape[0] != B or out.shape[1] < n or (B > 1 and ldo < n):
+        raise ValueError(f"out: expected a ({B}, >= {n}) view with row stride >= {n}, got {tuple(out.shape)} {out.stride()}")
+    if any(t_.device != pose_R.device for t_ in (fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_T, base, out)):
+        raise ValueError("mesh_tsdf_query: all tensors must live on one device")
+    ox, oy, oz = (float(v) for v in origin)
+    with TIMER.bracket("mesh_tsdf_query"):
+        check(lib.pm_mesh_tsdf_query_f32(_ptr(fields), _ptr(part_off), _ptr(part_shape), _ptr(part_bbox_min), _ptr(part_voxel_size),
+                                         _ptr(pose_R), _ptr(pose_T), B, M, int(p0), M if p1 is None else int(p1), int(res),
+                                         float(vox_size), ox, oy, oz, float(sdf_trunc), _ptr(base), per_env, _ptr(out),
+                                         max(ldo, n), 1 if brick_skip else 0, _stream()), "pm_mesh_tsdf_query_f32")
+    return out
+
+
 def depth_compact(world):
     """world (B,P,3) cropped cloud -> (compact (B,P,3): non-zero points + the first zero point, order kept; lengths (B) i32)."""
     _req(world)
