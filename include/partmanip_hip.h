@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 153 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 154 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -500,6 +500,20 @@ int pm_mesh_tsdf_query_f32(const float* fields, const int64_t* part_off, const i
                            const float* part_voxel_size, const float* pose_R, const float* pose_T, int B, int M, int p0, int p1,
                            int res, float vox_size, float ox, float oy, float oz, float sdf_trunc, const float* base,
                            int base_per_env, float* out, long out_stride, int brick_skip, void* stream);
+
+/* ------------------------------------------------------------------ mesh bake (producer of the mesh-TSDF part grids)
+ * utils/mesh2sdf.py:201-237 `TSDFfromMesh.mesh2sdf` without kaolin / ManifoldPlus: the signed-distance grid of one triangle mesh.
+ * tri: (F, 3, 3) float32 corner positions (faces with two equal corners already dropped by the caller; a remaining zero-area
+ * triangle counts as its longest edge for the distance and as nothing for the sign).  Voxel (i, j, k) of the (X, Y, Z) grid sits at
+ * (idx - shape / 2) * voxel_size + (cx, cy, cz), multiply and add rounded separately.  sdf[(i * Y + j) * Z + k] =
+ * clamp(s * sqrt(min_f squared distance to triangle f), -trunc, trunc), s = -1 iff |generalised winding number| >= 0.5 (sum of the
+ * van Oosterom-Strackee solid angles / 4 pi), else +1.  tri_cull != 0 skips the distance part of a triangle for a whole 4^3 brick
+ * whose voxels it cannot bring below trunc (bit-identical output, faster).  workspace: pm_mesh_sdf_bake_workspace_bytes(F) bytes of
+ * device memory (per-triangle records; contents undefined afterwards).  Deterministic: no atomics, fixed summation order.
+ * PM_EINVAL: a NULL pointer, F <= 0, a non-positive shape, voxel_size or trunc, X * Y * Z >= 2^31, a workspace that is too small. */
+size_t pm_mesh_sdf_bake_workspace_bytes(int F);
+int pm_mesh_sdf_bake_f32(const float* tri, int F, int X, int Y, int Z, float voxel_size, float cx, float cy, float cz, float trunc,
+                         int tri_cull, float* sdf, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ K15 fused set-abstraction level
  * One PointNet++ SA level (north_star; not in the reference snapshot, README.md:23,30) as one forward and

@@ -14,23 +14,59 @@ concatenates, tasks/grasp_cube.py:131,137).
 
 The grids are NOT padded to a common shape (mesh2sdf.py:181-184 pads with 1s that are never read: validity is tested against
 each part's own shape): `merge_sdf_field` keeps one flat buffer of concatenated grids and per-part tables of offset, shape,
-bbox_min and voxel_size.  Baking a grid from a mesh (kaolin, ManifoldPlus: mesh2sdf.py:158-167, 201-237), marching cubes and
-the debug dumps are outside this build's scope: they raise NotImplementedError.
+bbox_min and voxel_size.
+
+Baking a grid from a mesh (mesh2sdf.py:201-237; kaolin and ManifoldPlus there, neither of which exists for ROCm) is done by
+pm_mesh_sdf_bake_f32 (csrc/mesh_bake.hip) when the object is built with `bake=True`: `mesh2sdf(mesh_path)` returns the reference's
+dict, and `load_sdf` of an absent file bakes the mesh, saves the dict at the reference's path and goes on.  The grid layout is
+the reference's fp32 expressions (`bake_grid_layout`); the magnitude is the exact point-to-triangle distance; the sign is the
+generalised winding number (|w| >= 0.5 is inside), which equals kaolin's ray parity on a closed mesh and needs no manifold
+pre-pass on an open one.  Without `bake=True` an absent grid raises as before.  Marching cubes, ManifoldPlus itself
+and the debug dumps stay outside this build's scope: they raise NotImplementedError.
 """
 import os
 
 import numpy as np
 import torch
 
-from . import ops
+from . import meshio, ops
 
 FRANKA_SDF_DIR = os.path.join("assets", "franka_description", "sdf", "visual")       # mesh2sdf.py:43,148-154
 FRANKA_PARTS = [f"link{i}" for i in range(8)] + ["hand", "finger", "finger"]       # mesh2sdf.py:142-145
 OBJ_SDF_PATH = os.path.join("assets", "objs", "cube", "sdf.npy")                     # mesh2sdf.py:48
+FRANKA_MESHES = [f"link{i}.obj" for i in range(8)] + ["hand.obj", "finger.stl", "finger.stl"]   # mesh2sdf.py:142-145
+
+
+def bake_grid_layout(vertices, trunc, voxel_size):
+    """Shape, centre and bbox_min of the bake grid of a mesh, with the reference's own fp32 tensor expressions (mesh2sdf.py:213-223),
+    evaluated on the CPU: vertices (V, 3) -> ((X, Y, Z) ints, centre (3,) float32 tensor, bbox_min (3,) float32 tensor).
+    Voxel (i, j, k) sits at (idx - shape // 2) * voxel_size + centre; bbox_min is voxel (0, 0, 0)."""
+    v = torch.as_tensor(np.asarray(vertices, dtype=np.float32)).reshape(1, -1, 3)
+    obj_center = (v.max(dim=1)[0] + v.min(dim=1)[0]) / 2
+    max_range = v.max(dim=1)[0] - v.min(dim=1)[0] + 2 * trunc
+    volume_shape = torch.ceil(max_range / voxel_size)
+    shape = (int(volume_shape[0, 0]), int(volume_shape[0, 1]), int(volume_shape[0, 2]))
+    bbox_min = ((torch.zeros(1, 3, dtype=torch.long) - volume_shape // 2) * voxel_size + obj_center)[0]
+    return shape, obj_center[0], bbox_min
+
+
+def bake_mesh(device, trunc, voxel_size, mesh_path=None, vertices=None, faces=None, tri_cull=True):
+    """The bake behind TSDFfromMesh.mesh2sdf: a mesh file, or vertices (V, 3) + faces (F, 3) -> the reference's dict."""
+    if mesh_path is not None:
+        vertices, faces = meshio.load_mesh(mesh_path)
+    vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    faces = meshio.drop_double_corner_faces(vertices, np.asarray(faces, dtype=np.int64).reshape(-1, 3))
+    if len(faces) == 0:
+        raise ValueError(f"{mesh_path or 'mesh'}: no triangle is left to bake")
+    shape, centre, bbox_min = bake_grid_layout(vertices, trunc, voxel_size)
+    tri = torch.from_numpy(vertices[faces]).to(device)                              # (F, 3, 3)
+    sdf = ops.mesh_sdf_bake(tri, shape, voxel_size, centre.tolist(), trunc, tri_cull)
+    return {'sdf': sdf.cpu().numpy(), 'bbox_min': bbox_min.numpy(), 'voxel_size': voxel_size}
 
 
 class TSDFfromMesh:
-    """Constructor of the reference plus two keyword extensions: `sdf_dicts` (a list of {'sdf': (X,Y,Z) float32, 'bbox_min':
+    """Constructor of the reference plus three keyword extensions: `bake` (bake absent grids from their meshes on the GPU, module
+    docstring; default False = an absent grid is an error), `sdf_dicts` (a list of {'sdf': (X,Y,Z) float32, 'bbox_min':
     (3,), 'voxel_size': float} used instead of reading the pre-stored files) and `asset_root` (prefix of the reference's relative
     paths assets/franka_description/sdf/visual/*.npy and assets/objs/cube/sdf.npy).  `vox_origin` may be None, a tensor or the
     yaml's list (the reference raises TypeError on a list, tasks/hand_base.py passes one).
@@ -38,7 +74,7 @@ class TSDFfromMesh:
     triplet_interpolation_query) indexes a 3-D field with a flat index and cannot run; the parallel path is the specification."""
 
     def __init__(self, num_envs, size, resolution, device, parallel=True, debug=False, vox_origin=None, sdf_dicts=None,
-                 asset_root='.'):
+                 asset_root='.', bake=False):
         if debug:
             raise NotImplementedError("debug dumps (surface points / marching cubes) are outside this build's scope (DESIGN.md)")
         self.num_envs = num_envs
@@ -46,6 +82,7 @@ class TSDFfromMesh:
         self.device = device
         self.debug = debug
         self.asset_root = asset_root
+        self.bake = bake
 
         self.resolution = resolution
         self.size = size
@@ -82,21 +119,38 @@ class TSDFfromMesh:
 
     # ------------------------------------------------------------------------------------------------ loading
     def load_franka(self, hand_base_path):
-        """Parts in the reference's order: link0..link7, hand, finger, finger (mesh2sdf.py:141-156)."""
-        for name in FRANKA_PARTS:
-            self.load_sdf(os.path.join(hand_base_path, "sdf", "visual", name + ".npy"))
+        """Parts in the reference's order: link0..link7, hand, finger, finger (mesh2sdf.py:141-156); the mesh of a part is
+        meshes/visual/<name>, its grid the same path with 'meshes' -> 'sdf' and the extension -> '.npy'."""
+        for name in FRANKA_MESHES:
+            mesh_path = os.path.join(hand_base_path, "meshes", "visual", name)
+            preprocess_path = os.path.join(hand_base_path, "manifoldplus", "visual", name) if name.endswith(".obj") else None
+            sdf_path = os.path.join(hand_base_path, "sdf", "visual", name[:-4] + ".npy")
+            self.load_sdf(sdf_path, mesh_path, preprocess_path)
 
     def load_sdf(self, sdf_path, mesh_path=None, preprocess_path=None):
-        """Pre-stored grid -> appended to `sdf_dict_list` (mesh2sdf.py:70-73, 82).  An absent file would be baked from the mesh
-        by the reference (kaolin point_to_mesh_distance / check_sign after ManifoldPlus): not in this build."""
-        if not os.path.exists(sdf_path):
-            raise NotImplementedError(f"{sdf_path} is missing: baking a signed-distance grid from a mesh (kaolin, mesh2sdf.py:201-237) "
-                                      "is outside this build's scope (DESIGN.md); bake it with the reference and pass the file")
-        sdf_dict = np.load(sdf_path, allow_pickle=True).item()
+        """Pre-stored grid -> appended to `sdf_dict_list` (mesh2sdf.py:70-73, 82).  An absent file is baked from `mesh_path`, saved
+        at `sdf_path` and appended (mesh2sdf.py:74-82) if the object was built with bake=True, else an error.  `preprocess_path`
+        (the reference's ManifoldPlus output) is accepted and ignored: the winding-number sign needs no manifold pre-pass."""
+        if os.path.exists(sdf_path):
+            sdf_dict = np.load(sdf_path, allow_pickle=True).item()
+        elif not self.bake:
+            raise NotImplementedError(f"{sdf_path} is missing: the reference bakes it from the mesh with kaolin (mesh2sdf.py:201-237); "
+                                      "here pass bake=True to bake it on the GPU (pm_mesh_sdf_bake_f32), or pass the file")
+        else:
+            if mesh_path is None:
+                raise ValueError(f"{sdf_path} is missing and no mesh path was given to bake it from")
+            sdf_dict = self.mesh2sdf(mesh_path)
+            os.makedirs(os.path.dirname(os.path.abspath(sdf_path)), exist_ok=True)
+            np.save(sdf_path, sdf_dict)
         self.sdf_dict_list.append(sdf_dict)
 
-    def mesh2sdf(self, mesh_path):
-        raise NotImplementedError("baking a signed-distance grid from a mesh (kaolin) is outside this build's scope (DESIGN.md)")
+    def mesh2sdf(self, mesh_path=None, vertices=None, faces=None, tri_cull=True):
+        """The reference's bake (mesh2sdf.py:201-237) of a mesh file, or of `vertices` (V, 3) + `faces` (F, 3), on the GPU:
+        {'sdf': float32 (X, Y, Z), 'bbox_min': float32 (3,), 'voxel_size': pre_store_sdf_voxel_size}."""
+        if not self.bake:
+            raise NotImplementedError("baking a signed-distance grid from a mesh (kaolin in the reference) is off: build the object "
+                                      "with bake=True to bake on the GPU (pm_mesh_sdf_bake_f32)")
+        return bake_mesh(self.device, self.pre_store_sdf_trunc, self.pre_store_sdf_voxel_size, mesh_path, vertices, faces, tri_cull)
 
     def preprocess_mesh(self, input_mesh_path, output_mesh_path):
         raise NotImplementedError("ManifoldPlus preprocessing is outside this build's scope (DESIGN.md)")

@@ -1,0 +1,92 @@
+"""Triangle-mesh readers for the mesh bake (partmanip_amd/mesh2sdf.py: TSDFfromMesh.mesh2sdf), standard library + numpy only.
+
+    vertices (V, 3) float32, faces (F, 3) int64 = load_mesh(path)
+
+Wavefront OBJ: `v x y z` and `f` records; a face corner is `i`, `i/j`, `i/j/k` or `i//k` (only the position index is used), indices
+are 1-based or negative (relative to the vertices read so far), a polygon is fan-triangulated around its first corner; every
+other record is ignored.  Vertices are kept as the file lists them.
+STL: binary when the file is exactly 84 + 50 n bytes long with n the count at offset 80 (a binary STL may begin with the word
+`solid`, so the first bytes decide nothing), ASCII otherwise.  STL stores three corners per triangle; corners at exactly the same
+position become one vertex (numbered in order of first appearance), which is what makes a closed STL surface closed again.
+"""
+import os
+import struct
+
+import numpy as np
+
+
+def load_obj(path):
+    verts, faces = [], []
+    with open(path, "r", errors="replace") as f:
+        for line in f:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == "v" and len(tok) >= 4:
+                verts.append((float(tok[1]), float(tok[2]), float(tok[3])))
+            elif tok[0] == "f" and len(tok) >= 4:
+                idx = []
+                for c in tok[1:]:
+                    i = int(c.split("/")[0])
+                    idx.append(i - 1 if i > 0 else len(verts) + i)
+                for a in range(1, len(idx) - 1):
+                    faces.append((idx[0], idx[a], idx[a + 1]))
+    v = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+    fa = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if fa.size and (fa.min() < 0 or fa.max() >= len(v)):
+        raise ValueError(f"{path}: a face refers to a vertex that does not exist")
+    return v, fa
+
+
+def _merge_corners(corners):
+    """(n, 3, 3) float32 corner positions -> (vertices, faces): one vertex per distinct position, in order of first appearance."""
+    flat = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 3) + np.float32(0.0)     # -0.0 -> +0.0: one position
+    _, first, inv = np.unique(flat.view(np.dtype((np.void, 12))).reshape(-1), return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")                 # unique's (byte-sorted) numbering -> order of first appearance
+    rank = np.empty_like(order)
+    rank[order] = np.arange(len(order))
+    return flat[first[order]], rank[inv.reshape(-1)].reshape(-1, 3).astype(np.int64)
+
+
+def load_stl(path):
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) >= 84:
+        n = struct.unpack_from("<I", data, 80)[0]
+        if len(data) == 84 + 50 * n:
+            rec = np.frombuffer(data, dtype=np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("a", "<u2")]), count=n, offset=84)
+            return _merge_corners(rec["v"])
+    corners = []
+    for line in data.decode("ascii", errors="replace").splitlines():
+        tok = line.split()
+        if len(tok) >= 4 and tok[0] == "vertex":
+            corners.append((float(tok[1]), float(tok[2]), float(tok[3])))
+    if not corners or len(corners) % 3:
+        raise ValueError(f"{path}: neither a binary STL (84 + 50 n bytes) nor an ASCII STL with whole triangles")
+    return _merge_corners(np.asarray(corners, dtype=np.float32).reshape(-1, 3, 3))
+
+
+def load_mesh(path):
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".obj":
+        return load_obj(path)
+    if ext == ".stl":
+        return load_stl(path)
+    raise ValueError(f"{path}: only .obj and .stl meshes are read")
+
+
+def drop_double_corner_faces(vertices, faces):
+    """Faces with two corners at the same position are dropped (the reference's `faces[x1]`, mesh2sdf.py:209-210, which follows
+    trimesh's merge of equal vertices: so positions are compared, not only indices)."""
+    p = np.asarray(vertices, dtype=np.float32)[np.asarray(faces, dtype=np.int64)]              # (F, 3, 3)
+    same = (p[:, 0] == p[:, 1]).all(axis=1) | (p[:, 0] == p[:, 2]).all(axis=1) | (p[:, 1] == p[:, 2]).all(axis=1)
+    return np.asarray(faces, dtype=np.int64)[~same]
+
+
+def save_obj(path, vertices, faces):
+    """Minimal writer (tools and tests): `v` with 9 significant digits (float32 round-trips), 1-based `f`."""
+    with open(path, "w") as f:
+        for v in np.asarray(vertices, dtype=np.float32):
+            f.write("v %.9g %.9g %.9g\n" % (float(v[0]), float(v[1]), float(v[2])))
+        for t in np.asarray(faces, dtype=np.int64):
+            f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))

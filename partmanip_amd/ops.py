@@ -1276,6 +1276,32 @@ def mesh_tsdf_query(fields, part_off, part_shape, part_bbox_min, part_voxel_size
     return out
 
 
+def mesh_sdf_bake(tri, shape, voxel_size, centre, trunc, tri_cull=True):
+    """Signed-distance grid of a triangle mesh (pm_mesh_sdf_bake_f32): tri (F, 3, 3) float32 corner positions, shape = (X, Y, Z),
+    voxel (i, j, k) at (idx - shape // 2) * voxel_size + centre (3 floats; fp32, two roundings).  Returns (X, Y, Z) float32:
+    clamp(+-distance, -trunc, trunc), negative where |generalised winding number| >= 0.5.  tri_cull=False turns the per-brick
+    triangle rejection off (same bits, slower; for tests)."""
+    _req(tri)
+    _f32c(tri, "tri")
+    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or tri.shape[0] == 0:
+        raise ValueError(f"tri: expected (F > 0, 3, 3), got {tuple(tri.shape)}")
+    X, Y, Z = (int(v) for v in shape)
+    if min(X, Y, Z) <= 0 or X * Y * Z >= 2 ** 31:
+        raise ValueError(f"shape: expected three positive sizes with fewer than 2^31 cells, got {(X, Y, Z)}")
+    if not (float(voxel_size) > 0 and float(trunc) > 0):
+        raise ValueError("voxel_size and trunc must be positive")
+    F_ = tri.shape[0]
+    cx, cy, cz = (float(v) for v in centre)
+    nbytes = lib.pm_mesh_sdf_bake_workspace_bytes(F_)
+    with torch.cuda.device(tri.device):
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=tri.device)
+        out = torch.empty(X, Y, Z, dtype=torch.float32, device=tri.device)
+        with TIMER.bracket("mesh_sdf_bake"):
+            check(lib.pm_mesh_sdf_bake_f32(_ptr(tri), F_, X, Y, Z, float(voxel_size), cx, cy, cz, float(trunc), 1 if tri_cull else 0,
+                                           _ptr(out), _ptr(ws), nbytes, _stream()), "pm_mesh_sdf_bake_f32")
+    return out
+
+
 def depth_compact(world):
     """world (B,P,3) cropped cloud -> (compact (B,P,3): non-zero points + the first zero point, order kept; lengths (B) i32)."""
     _req(world)
