@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 154 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 155 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -514,6 +514,22 @@ int pm_mesh_tsdf_query_f32(const float* fields, const int64_t* part_off, const i
 size_t pm_mesh_sdf_bake_workspace_bytes(int F);
 int pm_mesh_sdf_bake_f32(const float* tri, int F, int X, int Y, int Z, float voxel_size, float cx, float cy, float cz, float trunc,
                          int tri_cull, float* sdf, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ posed mesh point cloud (observation side)
+ * utils/mesh2pc.py:56-65 `PCfromMesh.query_pc` in one launch, computing only the selected points.  pts (Q, 3): the canonical
+ * surface points of all parts, concatenated; part_of (Q) int32: each point's part; pose_R (B, M, 3, 3), pose_T (B, M, 3).
+ * sel: NULL = identity (requires K == Q); (K) int32 with sel_stride == 0 = one selection shared by all environments; (B, K) with
+ * sel_stride >= K (in elements) = one selection per environment.  With q = sel[.. k], p = part_of[q], x = pts[q]:
+ *   out[b * out_stride + 3 k + j] = ((x0 R[b,p,j,0] + x1 R[b,p,j,1]) + x2 R[b,p,j,2]) + T[b,p,j]
+ * (the reference's bmm(all_pc, R^T) + T) in fp32, in exactly that association, every operation rounded on its own: the bits are
+ * defined and repeat.  out_stride >= 3 K in elements; columns at and past 3 K of a row are not touched (the proprio tail of an
+ * observation row); rows need 4-byte alignment only.  q outside [0, Q) or p outside [0, M): the point's three outputs are NaN and
+ * nothing is read through that index.  A non-finite pose propagates; no address depends on it.  No workspace, no atomics,
+ * stream-ordered, never synchronises.
+ * PM_EINVAL: a NULL pts / part_of / pose_R / pose_T / out, B, M, Q or K < 1, B > 1048560 (65535 grid rows of 16 environments),
+ * out_stride < 3 K, sel == NULL with K != Q, a non-zero sel_stride < K. */
+int pm_mesh_pc_query_f32(const float* pts, const int32_t* part_of, int Q, const float* pose_R, const float* pose_T, int B, int M,
+                         const int32_t* sel, long sel_stride, int K, float* out, long out_stride, void* stream);
 
 /* ------------------------------------------------------------------ K15 fused set-abstraction level
  * One PointNet++ SA level (north_star; not in the reference snapshot, README.md:23,30) as one forward and

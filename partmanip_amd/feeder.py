@@ -7,18 +7,26 @@ Isaac Gym stepper (tasks/hand_base.py:252-290), so that the hot path is the lear
 Observations are generated on the device from a seeded generator with the shapes and
 distributions of SURVEY.md §8d: state obs ~ N(0,1); clouds = 1024 points ~ U([-1,1]^3) plus a
 per-env translation U(-0.5,0.5); rewards ~ N(0,1); dones ~ Bernoulli(0.02); succ = done & B(0.5).
+
+With `pc_source` = a mesh2pc.PCfromMesh the cloud part of every 3-channel cloud observation is scene-shaped instead of noise: the
+part meshes' surface points under seeded random poses (poses and point selection drawn on the device from the feeder's own
+generator), written by query_pc straight into the observation's first 3 * point_num columns; the tail stays N(0,1).
 """
 import torch
 
 
 class FeederEnv:
     def __init__(self, num_envs, num_obs, num_actions, device, seed=1234, max_episode_length=200, done_p=0.02,
-                 point_num=1024):
+                 point_num=1024, pc_source=None):
         self.num_envs, self.num_obs, self.num_actions = num_envs, dict(num_obs), num_actions
         self.device = torch.device(device)
         self.max_episode_length = max_episode_length
         self.done_p, self.point_num = done_p, point_num
         self.gen = torch.Generator(device=self.device).manual_seed(seed)
+        if pc_source is not None and pc_source.num_points != point_num:
+            raise ValueError(f"pc_source yields {pc_source.num_points} points per cloud, the feeder's point_num is {point_num}")
+        self.pc_source = pc_source
+        self.last_pc_poses = None                            # (pose_R, pose_T) of the latest pc_source cloud
         self.train_test_flag = 'train'
         self.dagger_reward_reset = None
         N = num_envs
@@ -37,6 +45,9 @@ class FeederEnv:
                 out[mode] = self._sparse_voxels(dim)
             elif dim >= self.point_num * 3 and (dim % self.point_num) < 64 and mode != 'normal_state':
                 c, tail = dim // self.point_num, dim % self.point_num
+                if self.pc_source is not None and c == 3:
+                    out[mode] = self._mesh_cloud(dim, tail)
+                    continue
                 pts = torch.rand(N, self.point_num, c, device=self.device, generator=self.gen) * 2 - 1
                 pts = pts + (torch.rand(N, 1, c, device=self.device, generator=self.gen) - 0.5)
                 parts = [pts.reshape(N, -1)]
@@ -46,6 +57,19 @@ class FeederEnv:
             else:
                 out[mode] = torch.randn(N, dim, device=self.device, generator=self.gen)
         return out
+
+    def _mesh_cloud(self, dim, tail):
+        """(N, dim): posed mesh points in the first 3 * point_num columns (pc_source.query_pc writes them in place), N(0,1) tail."""
+        from .mesh2pc import random_poses
+        N, P, src = self.num_envs, self.point_num, self.pc_source
+        obs = torch.empty(N, dim, device=self.device)
+        R, T = random_poses(N, src.part_num, self.gen, self.device)
+        sel = torch.randperm(src.pts.shape[0], device=self.device, generator=self.gen)[:P].to(torch.int32)
+        src.query_pc(R, T, out=obs[:, :3 * P], sel=sel)
+        if tail:
+            obs[:, 3 * P:] = torch.randn(N, tail, device=self.device, generator=self.gen)
+        self.last_pc_poses = (R, T)
+        return obs
 
     def _sparse_voxels(self, dim, grid=50):
         """The 'depth_sparse' observation (tasks/hand_base.py:335-336; utils/depth2tsdf.py:88-120): `point_num` rows

@@ -1,6 +1,9 @@
-"""Triangle-mesh readers for the mesh bake (partmanip_amd/mesh2sdf.py: TSDFfromMesh.mesh2sdf), standard library + numpy only.
+"""Triangle-mesh readers for the mesh bake (partmanip_amd/mesh2sdf.py: TSDFfromMesh.mesh2sdf) and the surface sampler of the posed
+point cloud (partmanip_amd/mesh2pc.py: PCfromMesh), standard library + numpy only (the sampler draws its uniforms from a torch
+generator).
 
     vertices (V, 3) float32, faces (F, 3) int64 = load_mesh(path)
+    points (count, 3) float32, face_index (count,) int64 = sample_surface(vertices, faces, count, generator)
 
 Wavefront OBJ: `v x y z` and `f` records; a face corner is `i`, `i/j`, `i/j/k` or `i//k` (only the position index is used), indices
 are 1-based or negative (relative to the vertices read so far), a polygon is fan-triangulated around its first corner; every
@@ -81,6 +84,33 @@ def drop_double_corner_faces(vertices, faces):
     p = np.asarray(vertices, dtype=np.float32)[np.asarray(faces, dtype=np.int64)]              # (F, 3, 3)
     same = (p[:, 0] == p[:, 1]).all(axis=1) | (p[:, 0] == p[:, 2]).all(axis=1) | (p[:, 1] == p[:, 2]).all(axis=1)
     return np.asarray(faces, dtype=np.int64)[~same]
+
+
+def sample_surface(vertices, faces, count, generator):
+    """Area-proportional surface sample (stands in for trimesh.sample.sample_surface, the reference's mesh2pc.py:37): `count` points
+    -> (points float32 (count, 3), face_index int64 (count,) into the faces that drop_double_corner_faces keeps).  u = torch.rand(count, 3, generator,
+    float64); triangle areas and their inclusive cumulative sum in fp64 in face order; the face is the first i with
+    cdf[i] > u0 * cdf[-1] (a zero-area face is never picked); (a, b) = (u1, u2), reflected to (1 - a, 1 - b) where a + b > 1; the
+    point is v0 + a (v1 - v0) + b (v2 - v0) in fp64, rounded once to float32."""
+    import torch
+    v32 = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    faces = drop_double_corner_faces(v32, np.asarray(faces, dtype=np.int64).reshape(-1, 3))
+    if len(faces) == 0:
+        raise ValueError("sample_surface: no triangle is left to sample")
+    tri = v32.astype(np.float64)[faces]                                                         # (F, 3, 3)
+    e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    area = 0.5 * np.linalg.norm(np.cross(e1, e2), axis=1)
+    cdf = np.cumsum(area)
+    if not (cdf[-1] > 0.0) or not np.isfinite(cdf[-1]):
+        raise ValueError("sample_surface: the mesh has no surface area")
+    u = torch.rand(int(count), 3, generator=generator, dtype=torch.float64).numpy()
+    i = np.searchsorted(cdf, u[:, 0] * cdf[-1], side="right")                                   # first i with cdf[i] > u0 * total
+    i = np.minimum(i, np.flatnonzero(area > 0.0)[-1])                                           # u0 * total rounded up to total
+    a, b = u[:, 1].copy(), u[:, 2].copy()
+    flip = a + b > 1.0
+    a[flip], b[flip] = 1.0 - a[flip], 1.0 - b[flip]
+    pts = tri[i, 0] + a[:, None] * e1[i] + b[:, None] * e2[i]
+    return pts.astype(np.float32), i.astype(np.int64)
 
 
 def save_obj(path, vertices, faces):

@@ -1276,6 +1276,50 @@ def mesh_tsdf_query(fields, part_off, part_shape, part_bbox_min, part_voxel_size
     return out
 
 
+def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None):
+    """The posed mesh point cloud (pm_mesh_pc_query_f32): pts (Q, 3) canonical surface points, part_of (Q) int32, pose_R (B, M, 3, 3),
+    pose_T (B, M, 3); sel: None (every point, K = Q), (K) int32 shared by all environments or (B, K) int32 with unit inner stride.
+    out: None (a fresh (B, 3K)) or a 2-D float32 view (B, >= 3K) with unit inner stride -- columns past 3K are left alone.
+    Returns out; out[b, 3k + j] = coordinate j of point pts[sel[.., k]] under the pose of its part in environment b."""
+    _req(pts, part_of, pose_R, pose_T, sel, out)
+    for t_, name in ((pts, "pts"), (pose_R, "pose_R"), (pose_T, "pose_T")):
+        _f32c(t_, name)
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
+        raise ValueError(f"pts: expected (Q > 0, 3), got {tuple(pts.shape)}")
+    Q = pts.shape[0]
+    if part_of.dtype != torch.int32 or not part_of.is_contiguous() or tuple(part_of.shape) != (Q,):
+        raise ValueError(f"part_of: expected a contiguous int32 tensor ({Q},), got {part_of.dtype} {tuple(part_of.shape)}")
+    if pose_R.dim() != 4 or tuple(pose_R.shape[2:]) != (3, 3) or pose_R.shape[0] == 0 or pose_R.shape[1] == 0:
+        raise ValueError(f"pose_R: expected (B, M, 3, 3), got {tuple(pose_R.shape)}")
+    B, M = pose_R.shape[0], pose_R.shape[1]
+    if tuple(pose_T.shape) != (B, M, 3):
+        raise ValueError(f"pose_T: expected ({B}, {M}, 3), got {tuple(pose_T.shape)}")
+    if sel is None:
+        K, sel_stride = Q, 0
+    else:
+        if sel.dtype != torch.int32 or sel.dim() not in (1, 2) or sel.shape[-1] == 0 or sel.stride(-1) != 1:
+            raise ValueError(f"sel: expected an int32 tensor (K,) or (B, K) with unit inner stride, got {sel.dtype} {tuple(sel.shape)}")
+        K = sel.shape[-1]
+        if sel.dim() == 1:
+            sel_stride = 0
+        else:
+            sel_stride = sel.stride(0) if B > 1 else K
+            if sel.shape[0] != B or sel_stride < K:
+                raise ValueError(f"sel: expected ({B}, K) with row stride >= K, got {tuple(sel.shape)} {sel.stride()}")
+    n = 3 * K
+    if out is None:
+        out = torch.empty(B, n, dtype=torch.float32, device=pose_R.device)
+    ldo = _rows(out, "out")
+    if out.shape[0] != B or out.shape[1] < n or (B > 1 and ldo < n):
+        raise ValueError(f"out: expected a ({B}, >= {n}) view with row stride >= {n}, got {tuple(out.shape)} {out.stride()}")
+    if any(t_ is not None and t_.device != pose_R.device for t_ in (pts, part_of, pose_T, sel, out)):
+        raise ValueError("mesh_pc_query: all tensors must live on one device")
+    with TIMER.bracket("mesh_pc_query"):
+        check(lib.pm_mesh_pc_query_f32(_ptr(pts), _ptr(part_of), Q, _ptr(pose_R), _ptr(pose_T), B, M, _ptr(sel), sel_stride, K,
+                                       _ptr(out), max(ldo, n), _stream()), "pm_mesh_pc_query_f32")
+    return out
+
+
 def mesh_sdf_bake(tri, shape, voxel_size, centre, trunc, tri_cull=True):
     """Signed-distance grid of a triangle mesh (pm_mesh_sdf_bake_f32): tri (F, 3, 3) float32 corner positions, shape = (X, Y, Z),
     voxel (i, j, k) at (idx - shape // 2) * voxel_size + centre (3 floats; fp32, two roundings).  Returns (X, Y, Z) float32:
