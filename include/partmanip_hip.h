@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 155 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 156 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -530,6 +530,52 @@ int pm_mesh_sdf_bake_f32(const float* tri, int F, int X, int Y, int Z, float vox
  * out_stride < 3 K, sel == NULL with K != Q, a non-zero sel_stride < K. */
 int pm_mesh_pc_query_f32(const float* pts, const int32_t* part_of, int Q, const float* pose_R, const float* pose_T, int B, int M,
                          const int32_t* sel, long sel_stride, int K, float* out, long out_stride, void* stream);
+
+/* ------------------------------------------------------------------ grasp_cube task step (simulator side of the learner)
+ * The tensor program of the reference's task layer (tasks/grasp_cube.py, tasks/load_robot.py, tasks/hand_base.py:363-392, 431-441)
+ * as one launch after physics and one before it.  Neither synchronises, allocates or uses float atomics; both are stream-ordered.
+ *
+ * pm_grasp_cube_post_f32 = grasp_cube.compute_observations + franka.update_state + grasp_cube.compute_reward + compute_scene_pose.
+ * Inputs (contiguous): rigid_body (N, nb, 13), dof_state (N, nd, 2), root (N, na, 13) whose actor obj_actor is the object;
+ * ltip / rtip: the two finger-tip bodies; dof_lo / dof_hi (nd); pose_lo / pose_hi (7); goal (3); obj_default_pos (3);
+ * part_body (M) int32 and part_C (M, 3, 3) or NULL (identity) for the pose outputs.  With tip = (rb[ltip] + rb[rtip]) / 2 over all
+ * 7 pose entries, scale(x) = 2 (x - lo) / (hi - lo) - 1, quat_to_mat in the order (i, j, k, r) with two_s = 2 / sum q^2 and no
+ * normalisation, D(q) = the candidate of largest trace among the 24 signed column pairs of quat_to_mat(q) (lowest index on ties):
+ *   normal_state (N, 19 + 2 nd) = [scale(tip[:7]) | scale(obj_pos) | D(obj_quat) row-major | qpos_normalized | qvel]
+ *   proprio (N, 7 + 2 nd)       = [scale(tip[:7]) | qpos_normalized | qvel]
+ *   rew (N) = reaching + 0.5 rot + 5 close + 20 reaching_goal + 3 success;  success, is_reached (N) bytes
+ *   extras (N, 8) = reaching_reward, close_reward, rot_reward, reaching_goal_reward, obj_movement, raw_reward, obj_height, obj_up_flag
+ *   pose_T (N, M, 3) = rb[b, part_body[p], :3];  pose_R (N, M, 3, 3) = quat_to_mat(rb[b, part_body[p], 3:7]) C_p
+ * Every output may be NULL (skipped).  normal_state, proprio and extras take a row stride in elements (column views of a wider
+ * observation buffer; 4-byte alignment only); nothing outside the named columns is written.  A part_body entry outside [0, nb) gives
+ * NaN poses for that part and is never dereferenced.  An environment's outputs depend on its own rows only and do not depend on N.
+ * PM_EINVAL: a NULL input, N, nb, nd, na < 1, an index outside its range, a row stride below the row width, pose outputs without
+ * part_body or with M < 1, nb or nd too large for the kernel's staging (nb * 13 + nd * 2 > 12000).
+ *
+ * pm_franka_control_f32 = franka.control + solve_ik + hand_base.pre_physics_step:365-375 + the buffer part of grasp_cube.reset_idx.
+ * actions (N, A) with a row stride; jac (N, nl, 6, nd), link rows jl and jr (NULL allowed with drive_mode 1).  drive_mode 0 = 'ik'
+ * (A == 7): dpose = 0.005 a[:6], J = (jac[jl] + jac[jr]) / 2 over DOFs [0, nd - 2), arm = qpos + J^T (J J^T + 0.05^2 I)^-1 dpose
+ * (Cholesky, fp32), both fingers = qpos + a[6] dt / 5; drive_mode 1 = 'pos' (A == nd - 1): arm = qpos + a[:nd-2] dt 20, fingers =
+ * qpos + a[nd-2] dt; clamped to [dof_lo, dof_hi] (NaN propagates).  Then, in the reference's order, with rew / success of the
+ * previous post step: train != 0: epis_max_step = rew < epis_max_rew ? epis_max_step : progress; epis_max_rew = max(rew,
+ * epis_max_rew); reset = progress >= epis_max_step + explore_step | success; reset_succ = success.  train == 0: reset = progress >=
+ * max_episode_length.  Environments being reset: pos_act = default_dof_pos, progress = 0, success = 0, epis_max_rew = -100,
+ * epis_max_step = 0.  counters: 4 int32; this call ADDS the number of set success bytes (before the reset) to counters[2 slot] and
+ * the number of resets to counters[2 slot + 1] and ZEROES the other pair, so a caller that starts from zeros and alternates slot =
+ * 0, 1, 0, ... reads this step's two sums from its own pair without a clearing launch.
+ * PM_EINVAL: a NULL pointer (jac with drive_mode 0), N < 1, nd < 3 or > 64, A not as stated, jl / jr outside [0, nl), slot not 0 / 1,
+ * an unknown drive_mode, act_stride < A. */
+int pm_grasp_cube_post_f32(const float* rigid_body, const float* dof_state, const float* root, int N, int nb, int nd, int na,
+                           int obj_actor, int ltip, int rtip, const float* dof_lo, const float* dof_hi, const float* pose_lo,
+                           const float* pose_hi, const float* goal, float goal_thresh, const float* obj_default_pos,
+                           const int32_t* part_body, const float* part_C, int M, float* normal_state, long ns_stride,
+                           float* proprio, long pr_stride, float* rew, uint8_t* success, uint8_t* is_reached, float* extras,
+                           long ex_stride, float* pose_R, float* pose_T, void* stream);
+int pm_franka_control_f32(const float* actions, long act_stride, int A, const float* dof_state, const float* jac, int N, int nd,
+                          int nl, int jl, int jr, const float* dof_lo, const float* dof_hi, const float* default_dof_pos, float dt,
+                          int drive_mode, const float* rew, uint8_t* success, int64_t* progress, int explore_step,
+                          int max_episode_length, int train, float* pos_act, float* epis_max_rew, int64_t* epis_max_step,
+                          uint8_t* reset, uint8_t* reset_succ, int32_t* counters, int slot, void* stream);
 
 /* ------------------------------------------------------------------ K15 fused set-abstraction level
  * One PointNet++ SA level (north_star; not in the reference snapshot, README.md:23,30) as one forward and

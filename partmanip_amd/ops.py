@@ -1320,6 +1320,144 @@ def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None):
     return out
 
 
+def _vec(t_, name, n, dtype=torch.float32):
+    if t_.dtype != dtype or not t_.is_contiguous() or t_.numel() != n:
+        raise ValueError(f"{name}: expected a contiguous {dtype} tensor of {n} elements, got {t_.dtype} {tuple(t_.shape)}")
+
+
+def _row_view(t_, name, N, width):
+    """Row stride (in elements) of a 2-D float32 output view (N, width) with unit inner stride."""
+    if t_.dtype != torch.float32 or t_.dim() != 2 or tuple(t_.shape) != (N, width) or t_.stride(1) != 1:
+        raise ValueError(f"{name}: expected a float32 view ({N}, {width}) with unit inner stride, got {t_.dtype} {tuple(t_.shape)} "
+                         f"{t_.stride()}")
+    ld = t_.stride(0) if N > 1 else width
+    if ld < width:
+        raise ValueError(f"{name}: row stride {ld} below the row width {width}")
+    return ld
+
+
+def grasp_cube_post(rigid_body, dof_state, root, obj_actor, ltip, rtip, dof_lo, dof_hi, pose_lo, pose_hi, goal, goal_thresh,
+                    obj_default_pos, part_body=None, part_C=None, normal_state=None, proprio=None, rew=None, success=None,
+                    is_reached=None, extras=None, pose_R=None, pose_T=None):
+    """Everything after physics of the grasp_cube task in one launch (pm_grasp_cube_post_f32, include/partmanip_hip.h): rigid_body
+    (N, nb, 13), dof_state (N, nd, 2), root (N, na, 13), all contiguous float32.  Outputs are written in place and every one may be
+    None (skipped): normal_state (N, 19 + 2 nd), proprio (N, 7 + 2 nd) and extras (N, 8) may be column views of a wider buffer;
+    rew (N) float32; success, is_reached (N) bool or uint8; pose_R (N, M, 3, 3), pose_T (N, M, 3) with part_body (M) int32 and
+    part_C (M, 3, 3) or None."""
+    _req(rigid_body, dof_state, root, dof_lo, dof_hi, pose_lo, pose_hi, goal, obj_default_pos, part_body, part_C, normal_state,
+         proprio, rew, success, is_reached, extras, pose_R, pose_T)
+    for t_, name in ((rigid_body, "rigid_body"), (dof_state, "dof_state"), (root, "root")):
+        _f32c(t_, name)
+    if rigid_body.dim() != 3 or rigid_body.shape[2] != 13 or rigid_body.shape[0] == 0 or rigid_body.shape[1] == 0:
+        raise ValueError(f"rigid_body: expected (N, nb, 13), got {tuple(rigid_body.shape)}")
+    N, nb = rigid_body.shape[0], rigid_body.shape[1]
+    if dof_state.dim() != 3 or dof_state.shape[0] != N or dof_state.shape[2] != 2 or dof_state.shape[1] == 0:
+        raise ValueError(f"dof_state: expected ({N}, nd, 2), got {tuple(dof_state.shape)}")
+    nd = dof_state.shape[1]
+    if root.dim() != 3 or root.shape[0] != N or root.shape[2] != 13 or root.shape[1] == 0:
+        raise ValueError(f"root: expected ({N}, na, 13), got {tuple(root.shape)}")
+    na = root.shape[1]
+    if not (0 <= obj_actor < na and 0 <= ltip < nb and 0 <= rtip < nb):
+        raise ValueError(f"obj_actor {obj_actor} / ltip {ltip} / rtip {rtip} outside ({na} actors, {nb} bodies)")
+    for t_, name, n in ((dof_lo, "dof_lo", nd), (dof_hi, "dof_hi", nd), (pose_lo, "pose_lo", 7), (pose_hi, "pose_hi", 7),
+                        (goal, "goal", 3), (obj_default_pos, "obj_default_pos", 3)):
+        _vec(t_, name, n)
+    M = 0
+    if pose_R is not None or pose_T is not None:
+        if part_body is None or part_body.dim() != 1 or part_body.numel() == 0:
+            raise ValueError("pose_R / pose_T need part_body (M) int32")
+        M = part_body.numel()
+        _vec(part_body, "part_body", M, torch.int32)
+        if part_C is not None:
+            _f32c(part_C, "part_C")
+            if tuple(part_C.shape) != (M, 3, 3):
+                raise ValueError(f"part_C: expected ({M}, 3, 3), got {tuple(part_C.shape)}")
+        for t_, name, shape in ((pose_R, "pose_R", (N, M, 3, 3)), (pose_T, "pose_T", (N, M, 3))):
+            if t_ is not None:
+                _f32c(t_, name)
+                if tuple(t_.shape) != shape:
+                    raise ValueError(f"{name}: expected {shape}, got {tuple(t_.shape)}")
+    lns = _row_view(normal_state, "normal_state", N, 19 + 2 * nd) if normal_state is not None else 0
+    lpr = _row_view(proprio, "proprio", N, 7 + 2 * nd) if proprio is not None else 0
+    lex = _row_view(extras, "extras", N, 8) if extras is not None else 0
+    if rew is not None:
+        _vec(rew, "rew", N)
+    for t_, name in ((success, "success"), (is_reached, "is_reached")):
+        if t_ is not None and (t_.dtype not in (torch.bool, torch.uint8) or not t_.is_contiguous() or t_.numel() != N):
+            raise ValueError(f"{name}: expected a contiguous bool / uint8 tensor of {N} elements, got {t_.dtype} {tuple(t_.shape)}")
+    dev = rigid_body.device
+    if any(t_ is not None and t_.device != dev for t_ in (dof_state, root, dof_lo, dof_hi, pose_lo, pose_hi, goal, obj_default_pos,
+                                                          part_body, part_C, normal_state, proprio, rew, success, is_reached,
+                                                          extras, pose_R, pose_T)):
+        raise ValueError("grasp_cube_post: all tensors must live on one device")
+    with TIMER.bracket("grasp_cube_post"):
+        check(lib.pm_grasp_cube_post_f32(_ptr(rigid_body), _ptr(dof_state), _ptr(root), N, nb, nd, na, int(obj_actor), int(ltip),
+                                         int(rtip), _ptr(dof_lo), _ptr(dof_hi), _ptr(pose_lo), _ptr(pose_hi), _ptr(goal),
+                                         float(goal_thresh), _ptr(obj_default_pos), _ptr(part_body), _ptr(part_C), M,
+                                         _ptr(normal_state), lns, _ptr(proprio), lpr, _ptr(rew), _ptr(success), _ptr(is_reached),
+                                         _ptr(extras), lex, _ptr(pose_R), _ptr(pose_T), _stream()), "pm_grasp_cube_post_f32")
+
+
+DRIVE_MODES = {"ik": 0, "pos": 1}                            # drive_mode of pm_franka_control_f32
+
+
+def franka_control(actions, dof_state, jac, jl, jr, dof_lo, dof_hi, default_dof_pos, dt, drive_mode, rew, success, progress,
+                   explore_step, max_episode_length, train, pos_act, epis_max_rew, epis_max_step, reset, reset_succ, counters, slot):
+    """Everything before physics in one launch (pm_franka_control_f32): joint targets from the actions ('ik': damped least squares
+    over jac (N, nl, 6, nd), link rows jl and jr; 'pos': scaled actions; jac may be None there) and the reference's episode
+    bookkeeping, in place: success (N) bool / uint8, progress and epis_max_step (N) int64, epis_max_rew (N), pos_act (N, nd), reset
+    and reset_succ (N) bool / uint8, counters (4) int32 (this call adds to pair `slot` and zeroes the other).  Returns pos_act."""
+    _req(actions, dof_state, jac, dof_lo, dof_hi, default_dof_pos, rew, success, progress, pos_act, epis_max_rew, epis_max_step,
+         reset, reset_succ, counters)
+    if drive_mode not in DRIVE_MODES:
+        raise ValueError(f"drive_mode: expected one of {tuple(DRIVE_MODES)}, got {drive_mode!r}")
+    _f32c(dof_state, "dof_state")
+    if dof_state.dim() != 3 or dof_state.shape[2] != 2 or dof_state.shape[0] == 0 or dof_state.shape[1] < 3:
+        raise ValueError(f"dof_state: expected (N, nd >= 3, 2), got {tuple(dof_state.shape)}")
+    N, nd = dof_state.shape[0], dof_state.shape[1]
+    A = 7 if drive_mode == "ik" else nd - 1
+    if actions.dtype != torch.float32 or actions.dim() != 2 or tuple(actions.shape) != (N, A) or actions.stride(1) != 1:
+        raise ValueError(f"actions: expected a float32 ({N}, {A}) tensor with unit inner stride for drive mode {drive_mode!r}, got "
+                         f"{actions.dtype} {tuple(actions.shape)}")
+    lda = actions.stride(0) if N > 1 else A
+    if lda < A:
+        raise ValueError(f"actions: row stride {lda} below {A}")
+    nl = 0
+    if drive_mode == "ik":
+        if jac is None:
+            raise ValueError("drive mode 'ik' needs the Jacobian")
+        _f32c(jac, "jac")
+        if jac.dim() != 4 or jac.shape[0] != N or tuple(jac.shape[2:]) != (6, nd) or jac.shape[1] == 0:
+            raise ValueError(f"jac: expected ({N}, nl, 6, {nd}), got {tuple(jac.shape)}")
+        nl = jac.shape[1]
+        if not (0 <= jl < nl and 0 <= jr < nl):
+            raise ValueError(f"link rows {jl}, {jr} outside the {nl} links of the Jacobian")
+    else:
+        jac = None
+    for t_, name, n in ((dof_lo, "dof_lo", nd), (dof_hi, "dof_hi", nd), (default_dof_pos, "default_dof_pos", nd), (rew, "rew", N),
+                        (epis_max_rew, "epis_max_rew", N), (pos_act, "pos_act", N * nd)):
+        _vec(t_, name, n)
+    _vec(progress, "progress", N, torch.int64)
+    _vec(epis_max_step, "epis_max_step", N, torch.int64)
+    _vec(counters, "counters", 4, torch.int32)
+    for t_, name in ((success, "success"), (reset, "reset"), (reset_succ, "reset_succ")):
+        if t_.dtype not in (torch.bool, torch.uint8) or not t_.is_contiguous() or t_.numel() != N:
+            raise ValueError(f"{name}: expected a contiguous bool / uint8 tensor of {N} elements, got {t_.dtype} {tuple(t_.shape)}")
+    if slot not in (0, 1):
+        raise ValueError(f"slot: expected 0 or 1, got {slot}")
+    dev = dof_state.device
+    if any(t_ is not None and t_.device != dev for t_ in (actions, jac, dof_lo, dof_hi, default_dof_pos, rew, success, progress,
+                                                          pos_act, epis_max_rew, epis_max_step, reset, reset_succ, counters)):
+        raise ValueError("franka_control: all tensors must live on one device")
+    with TIMER.bracket("franka_control"):
+        check(lib.pm_franka_control_f32(_ptr(actions), lda, A, _ptr(dof_state), _ptr(jac), N, nd, nl, int(jl), int(jr), _ptr(dof_lo),
+                                        _ptr(dof_hi), _ptr(default_dof_pos), float(dt), DRIVE_MODES[drive_mode], _ptr(rew),
+                                        _ptr(success), _ptr(progress), int(explore_step), int(max_episode_length),
+                                        1 if train else 0, _ptr(pos_act), _ptr(epis_max_rew), _ptr(epis_max_step), _ptr(reset),
+                                        _ptr(reset_succ), _ptr(counters), int(slot), _stream()), "pm_franka_control_f32")
+    return pos_act
+
+
 def mesh_sdf_bake(tri, shape, voxel_size, centre, trunc, tri_cull=True):
     """Signed-distance grid of a triangle mesh (pm_mesh_sdf_bake_f32): tri (F, 3, 3) float32 corner positions, shape = (X, Y, Z),
     voxel (i, j, k) at (idx - shape // 2) * voxel_size + centre (3 floats; fp32, two roundings).  Returns (X, Y, Z) float32:

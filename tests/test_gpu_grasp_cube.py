@@ -1,0 +1,412 @@
+"""The grasp_cube task step on the GPU: partmanip_amd.tasks.GraspCubeTensors (pm_grasp_cube_post_f32, pm_franka_control_f32,
+csrc/task_grasp_cube.hip) against the REFERENCE's own task code (fixtures of tests/golden/make_grasp_cube_golden.py) and against
+the numpy restatement of the contract (tests/grasp_cube_ref.py).
+
+Tolerance of the parity tests: e_ref = max |out32 - out64| of a fixture's output group is what the reference's own float32 run
+loses against its float64 run; the kernel must stay within 4 e_ref of out64 (this project's margin convention).  Flags and
+integers must be equal; pose_T and pose_R (default signed-permutation C) must equal the reference's float32 numbers.
+Where a test compares shapes the fixtures do not cover against the float64 restatement, the bound is stated at the comparison.
+Observed 2026-10-17 on 1x MI355X: every group within 1.68 e_ref (profiles/grasp_cube_margins.json)."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import grasp_cube_ref as G
+from tests.helpers import GOLDEN, ROOT, record_margin
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SENTINEL = -777.25
+EPS = float(np.finfo(np.float32).eps)
+GROUPS = ("normal_state", "proprio", "rew", "pose_R", "pose_T")
+
+
+def load(name):
+    with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+def t(x, dtype=None):
+    return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype).to(DEV)
+
+
+def bits(x):
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def npy(x):
+    return x.detach().cpu().numpy()
+
+
+def fixture_task(fx, drive="ik"):
+    from partmanip_amd.tasks import GraspCubeTensors
+    N = fx["rigid_body"].shape[0]
+    cfg = {"robot": {"driveMode": drive, "dof": fx["default_dof_pos"].tolist()}, "explore_step": int(fx["explore_step"]),
+           "maxEpisodeLength": 200}
+    return GraspCubeTensors(N, DEV, cfg, float(fx["dt"]))
+
+
+def within(name, key, got, fx):
+    """max |got - out64| <= 4 e_ref of the fixture's group `key`; the ratio is recorded."""
+    want64, want32 = fx["out64_" + key], fx["out32_" + key]
+    e_ref = float(np.abs(want32.astype(np.float64) - want64).max())
+    err = float(np.abs(np.asarray(got, dtype=np.float64) - want64).max())
+    print(f"{name} {key}: e_ref = {e_ref:.3e}; max |hip - out64| = {err:.3e}" + (f" = {err / e_ref:.2f} e_ref" if e_ref > 0 else ""))
+    if e_ref > 0:
+        record_margin(f"{name}: {key} max |hip - out64| / e_ref", err / e_ref, 4.0, e_ref=e_ref)
+    assert err <= 4 * e_ref, (name, key, err, e_ref)
+
+
+def after_post(task, fx):
+    """One end_step on the fixture's state with the progress counter arriving at before_progress."""
+    task.progress_buf.copy_(t(fx["before_progress"] - 1))
+    task.end_step(t(fx["rigid_body"]), t(fx["dof_state"]), t(fx["root"]))
+    task.epis_max_rew.copy_(t(fx["before_epis_max_rew"]))
+    task.epis_max_step.copy_(t(fx["before_epis_max_step"]))
+
+
+# ------------------------------------------------------------------------------------------- 1. the reference
+@pytest.mark.parametrize("name", ["grasp_cube_ref_small", "grasp_cube_ref_64"])
+def test_reference_parity_after_physics(name):
+    fx = load(name)
+    task = fixture_task(fx)
+    after_post(task, fx)
+    obs, rew, _, extras = task.end_step(t(fx["rigid_body"]), t(fx["dof_state"]), t(fx["root"]))
+    rot, pos = task.compute_scene_pose()
+    got = dict(normal_state=npy(obs["normal_state"]), proprio=npy(obs["proprio_state"]), rew=npy(rew), pose_R=npy(rot), pose_T=npy(pos))
+    for k in GROUPS:
+        assert got[k].dtype == np.float32 and got[k].shape == fx["out64_" + k].shape, k
+        within(name, k, got[k], fx)
+    for i, col in enumerate(G.EXTRAS):
+        sub = {"out64_x": fx["out64_extras"][:, i], "out32_x": fx["out32_extras"][:, i]}
+        e = npy(extras[col])
+        print(col, end=": ")
+        within(name + " extras." + col, "x", e, sub)
+    assert np.array_equal(npy(task.success), fx["out64_success"]) and np.array_equal(npy(task.is_reached), fx["out64_is_reached"])
+    assert np.array_equal(npy(extras["is_reached"]), fx["out64_is_reached"])
+    assert np.array_equal(npy(extras["obj_up_flag"]), fx["out64_extras"][:, 7].astype(np.float32))
+    assert np.array_equal(npy(extras["raw_reward"]), got["rew"])
+    assert np.array_equal(got["pose_T"], fx["out32_pose_T"])              # equal as numbers (-0 == 0)
+    assert np.array_equal(got["pose_R"], fx["out32_pose_R"])
+    assert np.array_equal(npy(task.progress_buf), fx["before_progress"] + 1)
+
+
+@pytest.mark.parametrize("name", ["grasp_cube_ref_small", "grasp_cube_ref_64"])
+def test_reference_parity_before_physics(name):
+    from partmanip_amd import ops
+    fx = load(name)
+    N = fx["rigid_body"].shape[0]
+    for mode, prefix in (("train", ""), ("test", "test_")):
+        task = fixture_task(fx)
+        task.train_test_flag = mode
+        if mode == "test":
+            task.max_episode_length = int(fx["max_episode_length_test"])
+        after_post(task, fx)
+        rew = task.rew_buf.clone()
+        pos_act, reset = task.begin_step(t(fx["actions"]), t(fx["dof_state"]), t(fx["jac"]))
+        o = lambda k: fx["out64_" + prefix + k]               # noqa: E731
+        sub = {"out64_pos_act": o("pos_act"), "out32_pos_act": fx["out32_" + prefix + "pos_act"]}
+        within(f"{name} {mode}", "pos_act", npy(pos_act), sub)
+        assert np.array_equal(npy(reset), o("reset")) and np.array_equal(npy(task.progress_buf), o("after_progress"))
+        assert np.array_equal(npy(task.success), o("after_success"))
+        assert np.array_equal(npy(task.epis_max_step), o("after_epis_max_step"))
+        # epis_max_rew: the kernel's own reward or the value before, bit for bit; -100 where the episode starts over
+        emr = torch.where(reset, torch.full_like(rew, -100.0),
+                          torch.maximum(rew, t(fx["before_epis_max_rew"])) if mode == "train" else t(fx["before_epis_max_rew"]))
+        assert np.array_equal(bits(task.epis_max_rew), bits(emr))
+        slot = task._counters[2 * task._slot:2 * task._slot + 2].cpu().numpy()
+        assert int(slot[0]) == int(fx["out64_success"].sum()) and int(slot[1]) == int(o("reset").sum())
+        assert task._counters[2 * (1 - task._slot):][:2].abs().sum().item() == 0
+        if mode == "train":
+            assert np.array_equal(npy(task.reset_succ), o("reset_succ"))
+            assert int(slot[0]) == int(o("n_succ")) and int(slot[1]) == int(o("n_reset"))
+            sr = task.extras["succ_rate"]
+            assert sr.dtype == torch.float32 and tuple(sr.shape) == (1,) and np.array_equal(npy(sr), o("succ_rate").reshape(1))
+    # the solve alone on every environment (no episode ends: test mode with an unreachable length), both drive modes
+    for drive, key, act in (("ik", "pos_act_ik", "actions"), ("pos", "pos_act_pos", "actions_pos")):
+        task = fixture_task(fx, drive)
+        task.train_test_flag, task.max_episode_length = "test", 10 ** 6
+        after_post(task, fx)
+        pos_act, reset = task.begin_step(t(fx[act]), t(fx["dof_state"]), t(fx["jac"]))
+        assert not bool(reset.any()) and tuple(pos_act.shape) == (N, 9)
+        within(name, key, npy(pos_act), fx)
+    assert ops.DRIVE_MODES == {"ik": 0, "pos": 1}
+
+
+# ------------------------------------------------------------------------------------------- 2. shapes and layouts
+def make_state(N, nb, nd, seed, nl=None):
+    """Seeded raw state (float32 numpy): half the environments within reach of the object, a quarter at the goal; object
+    quaternions with a clear best candidate; DOF positions inside limits drawn with the state."""
+    rng = np.random.RandomState(seed)
+    nl = nb - 2 if nl is None else nl
+    ltip, rtip = nb - 4, nb - 2
+    rb = rng.uniform(-0.5, 0.5, size=(N, nb, 13))
+    q = rng.normal(size=(N, nb, 4))
+    rb[..., 3:7] = q / np.linalg.norm(q, axis=-1, keepdims=True)
+    kind = np.arange(N) % 4
+    obj = np.stack([rng.uniform(-0.14, 0.14, size=N), rng.uniform(-0.14, 0.14, size=N), rng.uniform(0.02, 0.3, size=N)], axis=1)
+    d = rng.normal(size=(N, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    obj[kind == 0] = np.array([0, 0, 0.2]) + d[kind == 0] * 0.01
+    d2 = rng.normal(size=(N, 3))
+    d2 /= np.linalg.norm(d2, axis=1, keepdims=True)
+    tip = obj + d2 * np.where(kind <= 1, 0.01, 0.1)[:, None]
+    half = rng.normal(size=(N, 3)) * 0.01
+    rb[:, ltip, :3], rb[:, rtip, :3] = tip + half, tip - half
+    rb[:, rtip, 3:7] = rb[:, ltip, 3:7]
+    root = rng.normal(size=(N, 2, 13)) * 0.1
+    root[:, 1, :3] = obj
+    for b in range(N):
+        while True:
+            qq = rng.normal(size=4)
+            qq /= np.linalg.norm(qq)
+            tr = np.sort(G.candidates(qq[None])[1][0])
+            if tr[-1] - tr[-2] >= 2e-3:
+                break
+        root[b, 1, 3:7] = qq
+    rb[:, nb - 1] = root[:, 1]
+    lo = -rng.uniform(0.5, 3.0, size=nd)
+    hi = rng.uniform(0.5, 3.0, size=nd)
+    dof = np.stack([rng.uniform(lo * 0.9, hi * 0.9, size=(N, nd)), rng.normal(size=(N, nd))], axis=-1)
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)   # noqa: E731
+    return dict(rigid_body=f(rb), dof_state=f(dof), root=f(root), jac=f(rng.normal(size=(N, nl, 6, nd))),
+                actions=f(rng.uniform(-1, 1, size=(N, 7))), dof_lo=f(lo), dof_hi=f(hi), default=f((lo + hi) / 2), ltip=ltip, rtip=rtip,
+                progress=rng.randint(0, 100, size=N).astype(np.int64), epis_max_rew=f(rng.uniform(-3, 8, size=N)),
+                epis_max_step=rng.randint(0, 60, size=N).astype(np.int64))
+
+
+def build_task(st, lo, hi, nb, nd, M):
+    """A task over environments [lo, hi) of a state."""
+    from partmanip_amd.tasks import Franka, GraspCubeTensors
+    n = hi - lo
+    cfg = {"robot": {"driveMode": "ik", "dof": st["default"].tolist()}, "explore_step": 40}
+    robot = Franka(cfg["robot"], 1 / 60, n, DEV, num_dofs=nd, num_rigid_body=nb - 1, dof_lower=st["dof_lo"], dof_upper=st["dof_hi"],
+                   ltip_rb_index=st["ltip"], rtip_rb_index=st["rtip"])
+    kw = {} if M == 12 else dict(part_body=[nb - 1])
+    return GraspCubeTensors(n, DEV, cfg, 1 / 60, num_bodies=nb, robot=robot, **kw)
+
+
+def run_slice(st, lo, hi, nb, nd, M):
+    """end_step then begin_step over environments [lo, hi); every output as numpy."""
+    task = build_task(st, lo, hi, nb, nd, M)
+    s = lambda k: t(st[k][lo:hi])                             # noqa: E731
+    task.progress_buf.copy_(s("progress"))
+    obs, rew, _, extras = task.end_step(s("rigid_body"), s("dof_state"), s("root"))
+    out = dict(normal_state=npy(obs["normal_state"]), proprio=npy(obs["proprio_state"]), rew=npy(rew), extras=npy(task._extras),
+               success=npy(task.success), is_reached=npy(task.is_reached), pose_R=npy(task.pose_R), pose_T=npy(task.pose_T))
+    task.epis_max_rew.copy_(s("epis_max_rew"))
+    task.epis_max_step.copy_(s("epis_max_step"))
+    pos_act, reset = task.begin_step(s("actions"), s("dof_state"), s("jac"))
+    out.update(pos_act=npy(pos_act), reset=npy(reset), reset_succ=npy(task.reset_succ), progress=npy(task.progress_buf),
+               epis_max_rew=npy(task.epis_max_rew), epis_max_step=npy(task.epis_max_step), after_success=npy(task.success))
+    return out, task
+
+
+def same_bits(a, b):
+    if a.dtype == np.float32:
+        return np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    return np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("M", [1, 12])
+@pytest.mark.parametrize("nd", [9, 11])
+@pytest.mark.parametrize("nb", [13, 14])
+def test_shapes_and_batch_independence(nb, nd, M):
+    N = 257
+    st = make_state(N, nb, nd, 7000 + nb * 100 + nd * 10 + M)
+    full, task = run_slice(st, 0, N, nb, nd, M)
+    assert full["normal_state"].shape == (N, 19 + 2 * nd) and full["proprio"].shape == (N, 7 + 2 * nd)
+    assert full["pose_R"].shape == (N, M, 3, 3) and full["pose_T"].shape == (N, M, 3) and full["pos_act"].shape == (N, nd)
+    assert 0 < full["reset"].sum() < N and full["is_reached"].sum() * 4 >= N and full["success"].sum() * 8 >= N
+    # every environment alone or inside another batch: the same bits (batches of 1, 5, 37 and 64 cut out of the 257)
+    for lo, n in ((0, 1), (256, 1), (131, 1), (100, 5), (7, 37), (190, 64), (193, 64)):
+        part, _ = run_slice(st, lo, lo + n, nb, nd, M)
+        for k, v in part.items():
+            assert same_bits(v, full[k][lo:lo + n]), (k, lo, n)
+    # the float64 restatement of the contract.  Post groups: every value is a short chain (< 40 operations) of float32 operations
+    # on values of magnitude <= max(1, |value|); the reward multiplies such an error by at most 20 -> 64 eps max(1, |want|) * 20.
+    part_body = task.part_body.cpu().numpy()
+    part_C = None if task.part_C is None else task.part_C.cpu().numpy()
+    ref = G.post(st["rigid_body"], st["dof_state"], st["root"], 1, st["ltip"], st["rtip"], st["dof_lo"], st["dof_hi"], [0, 0, 0.2],
+                 0.025, [0, 0, 0.025], part_body, part_C)
+    for k in ("normal_state", "proprio", "rew", "extras", "pose_R", "pose_T"):
+        bound = 64 * EPS * 20 * max(1.0, float(np.abs(ref[k]).max()))
+        err = float(np.abs(full[k].astype(np.float64) - ref[k]).max())
+        record_margin(f"shapes nb={nb} nd={nd} M={M}: {k} |hip - fp64| / bound", err / bound, 1.0)
+        assert err <= bound, (k, err, bound)
+    assert np.array_equal(full["success"], ref["success"]) and np.array_equal(full["is_reached"], ref["is_reached"])
+    # bookkeeping from the kernel's own reward: integers equal
+    tgt = G.control(st["actions"], st["dof_state"], st["jac"], st["ltip"] - 1, st["rtip"] - 1, st["dof_lo"], st["dof_hi"], 1 / 60, "ik")
+    bk = G.bookkeeping(dict(rew=full["rew"], success=full["success"], progress=st["progress"] + 1, epis_max_rew=st["epis_max_rew"],
+                            epis_max_step=st["epis_max_step"]), tgt, st["default"], 40, 200, True)
+    for k, kk in (("reset", "reset"), ("reset_succ", "reset_succ"), ("progress", "progress"), ("epis_max_step", "epis_max_step"),
+                  ("after_success", "success")):
+        assert np.array_equal(full[k], bk[kk]), k
+    assert same_bits(full["epis_max_rew"], bk["epis_max_rew"].astype(np.float32))
+    # joint targets: a Cholesky solve in float32 is backward stable: |du| <= c n^2 eps cond(A) |u| with n = 6; c n^2 = 64 here,
+    # cond(A) of each environment from the float64 restatement; plus the rounding of qpos + u and of the targets themselves
+    na = nd - 2
+    J = (st["jac"][:, st["ltip"] - 1, :, :na].astype(np.float64) + st["jac"][:, st["rtip"] - 1, :, :na]) / 2
+    cond = np.linalg.cond(J @ J.transpose(0, 2, 1) + 0.0025 * np.eye(6))
+    u = np.abs(bk["pos_act"] - st["dof_state"][:, :, 0]).max(axis=1)
+    bound = 64 * EPS * cond * np.maximum(u, 1e-3) + 8 * EPS * np.abs(bk["pos_act"]).max()
+    err = np.abs(full["pos_act"].astype(np.float64) - bk["pos_act"]).max(axis=1)
+    record_margin(f"shapes nb={nb} nd={nd}: pos_act |hip - fp64| / bound", float((err / bound).max()), 1.0)
+    assert (err <= bound).all(), float((err / bound).max())
+
+
+@pytest.mark.parametrize("off", [1, 2, 3])
+def test_column_views_at_every_row_alignment_leave_everything_else_alone(off):
+    from partmanip_amd import ops
+    N, nb, nd = 37, 14, 9
+    st = make_state(N, nb, nd, 7100)
+    full, task = run_slice(st, 0, N, nb, nd, 12)
+    r = task.robot
+    width = 3 + 37 + 2 + 25 + 1 + 8 + 3                       # odd: the rows' alignment walks through all four residues
+    buf = torch.full((N * width + 8,), SENTINEL, device=DEV)
+    view = buf[off:off + N * width].view(N, width)
+    ns, pr, ex = view[:, 3:40], view[:, 42:67], view[:, 68:76]
+    args = (t(st["rigid_body"]), t(st["dof_state"]), t(st["root"]), 1, st["ltip"], st["rtip"], r.dof_lower_limits_tensor,
+            r.dof_upper_limits_tensor, task.pose_lower_limit, task.pose_upper_limit, task.success_pos, 0.025, task.obj_default_pos)
+    ops.grasp_cube_post(*args, normal_state=ns, proprio=pr, extras=ex)
+    assert np.array_equal(bits(ns), bits(full["normal_state"])) and np.array_equal(bits(pr), bits(full["proprio"]))
+    assert np.array_equal(bits(ex), bits(full["extras"]))
+    mask = torch.ones(N, width, dtype=torch.bool, device=DEV)
+    mask[:, 3:40] = mask[:, 42:67] = mask[:, 68:76] = False
+    assert bool((view[mask] == SENTINEL).all()) and bool((buf[:off] == SENTINEL).all()) and bool((buf[off + N * width:] == SENTINEL).all())
+    # null outputs are skipped: each output alone gives the bits of the full call
+    rew = torch.full((N,), SENTINEL, device=DEV)
+    ops.grasp_cube_post(*args, rew=rew)
+    assert np.array_equal(bits(rew), bits(full["rew"]))
+    pose_T = torch.full((N, 12, 3), SENTINEL, device=DEV)
+    ops.grasp_cube_post(*args, part_body=task.part_body, part_C=task.part_C, pose_T=pose_T)
+    assert np.array_equal(bits(pose_T), bits(full["pose_T"]))
+    pose_R = torch.full((N, 12, 3, 3), SENTINEL, device=DEV)
+    succ = torch.zeros(N, dtype=torch.bool, device=DEV)
+    ops.grasp_cube_post(*args, part_body=task.part_body, part_C=task.part_C, pose_R=pose_R, success=succ)
+    assert np.array_equal(bits(pose_R), bits(full["pose_R"])) and np.array_equal(npy(succ), full["success"])
+    ops.grasp_cube_post(*args)                                # nothing asked for: nothing written, no error
+
+
+# ------------------------------------------------------------------------------------------- 3. one observation row
+def test_one_row_composition_with_the_mesh_point_cloud():
+    from partmanip_amd.mesh2pc import PCfromMesh
+    N, nb, nd, P = 37, 14, 9, 64
+    st = make_state(N, nb, nd, 7200)
+    full, _ = run_slice(st, 0, N, nb, nd, 12)
+    task = build_task(st, 0, N, nb, nd, 12)
+    pc = PCfromMesh(N, DEV, num_points=P, part_pcs=np.random.RandomState(1).uniform(-0.07, 0.07, size=(12, P, 3)).astype(np.float32))
+    sel = t(np.random.RandomState(2).randint(0, 12 * P, size=P).astype(np.int32))
+    obs = torch.full((N, 3 * P + 25), SENTINEL, device=DEV)
+    task.end_step(t(st["rigid_body"]), t(st["dof_state"]), t(st["root"]), obs_out=obs)
+    pc.query_pc(*task.compute_scene_pose(), out=obs[:, :3 * P], sel=sel)
+    direct = pc.query_pc(t(full["pose_R"]), t(full["pose_T"]), sel=sel)
+    assert np.array_equal(bits(obs[:, :3 * P]), bits(direct.reshape(N, -1)))
+    assert np.array_equal(bits(obs[:, 3 * P:]), bits(full["proprio"]))
+    assert task.obs_buf["proprio_state"].data_ptr() == obs[:, 3 * P:].data_ptr()
+
+
+def test_one_row_composition_with_the_mesh_tsdf():
+    from partmanip_amd.mesh2sdf import TSDFfromMesh
+    from tests import mesh_tsdf_parts as MP
+    N, nb, nd, V = 2, 14, 9, MP.RES ** 3
+    st = make_state(N, nb, nd, 7300)
+    full, _ = run_slice(st, 0, N, nb, nd, 12)
+    task = build_task(st, 0, N, nb, nd, 12)
+    vol = TSDFfromMesh(N, MP.SIZE, MP.RES, DEV, sdf_dicts=MP.fixture_parts("cont"), vox_origin=list(MP.ORIGIN))
+    obs = torch.full((N, V + 25), SENTINEL, device=DEV)
+    task.end_step(t(st["rigid_body"]), t(st["dof_state"]), t(st["root"]), obs_out=obs)
+    vol.query_tsdf(*task.compute_scene_pose(), out=obs[:, :V])
+    direct = vol.query_tsdf(t(full["pose_R"]), t(full["pose_T"]))
+    assert np.array_equal(bits(obs[:, :V]), bits(direct.reshape(N, -1)))
+    assert np.array_equal(bits(obs[:, V:]), bits(full["proprio"]))
+
+
+# ------------------------------------------------------------------------------------------- 4. isolation
+def test_a_nan_stays_inside_its_environment():
+    N, nb, nd, victim = 37, 14, 9, 17
+    st = make_state(N, nb, nd, 7400)
+    st["progress"][:] = 1                                     # nobody times out: every environment's targets come from the solve
+    st["epis_max_step"][:] = 0
+    clean, _ = run_slice(st, 0, N, nb, nd, 12)
+    assert not clean["reset"][victim]
+    others = np.arange(N) != victim
+    bad = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in st.items()}
+    bad["rigid_body"][victim] = np.nan
+    got, _ = run_slice(bad, 0, N, nb, nd, 12)
+    for k in ("normal_state", "proprio", "rew", "extras", "success", "is_reached", "pose_R", "pose_T"):
+        assert same_bits(got[k][others], clean[k][others]), k
+    assert np.isnan(got["rew"][victim]) and np.isnan(got["pose_R"][victim]).all() and np.isnan(got["normal_state"][victim, :7]).all()
+    bad = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in st.items()}
+    bad["jac"][victim, st["ltip"] - 1, 2, 3] = np.nan
+    got, _ = run_slice(bad, 0, N, nb, nd, 12)
+    assert same_bits(got["pos_act"][others], clean["pos_act"][others])
+    assert same_bits(got["pos_act"][victim, nd - 2:], clean["pos_act"][victim, nd - 2:])         # the fingers do not read the Jacobian
+    assert not same_bits(got["pos_act"][victim, :nd - 2], clean["pos_act"][victim, :nd - 2])
+    for k in ("reset", "reset_succ", "progress", "epis_max_step", "epis_max_rew"):
+        assert same_bits(got[k], clean[k]), k
+
+
+# ------------------------------------------------------------------------------------------- 5. several steps in a row
+def test_three_steps_in_a_row_follow_the_restated_bookkeeping():
+    fx = load("grasp_cube_ref_64")
+    N = 64
+    task = fixture_task(fx)
+    rng = np.random.RandomState(11)
+    state = dict(rew=np.zeros(N, dtype=np.float32), success=np.zeros(N, dtype=bool), progress=fx["before_progress"].copy(),
+                 epis_max_rew=fx["before_epis_max_rew"].copy(), epis_max_step=fx["before_epis_max_step"].copy())
+    task.progress_buf.copy_(t(state["progress"]))
+    task.epis_max_rew.copy_(t(state["epis_max_rew"]))
+    task.epis_max_step.copy_(t(state["epis_max_step"]))
+    jl, jr = int(fx["ltip"]) - 1, int(fx["rtip"]) - 1
+    for step in range(3):
+        perm = rng.permutation(N)                             # the fixture's environments in another order each step
+        rb, dof, root, jac = (fx[k][perm] for k in ("rigid_body", "dof_state", "root", "jac"))
+        act = rng.uniform(-1, 1, size=(N, 7)).astype(np.float32)
+        pos_act, reset = task.begin_step(t(act), t(dof), t(jac))
+        tgt = G.control(act, dof, jac, jl, jr, fx["dof_lo"], fx["dof_hi"], float(fx["dt"]), "ik")
+        want = G.bookkeeping(state, tgt, fx["default_dof_pos"], int(fx["explore_step"]), 200, True)
+        assert np.array_equal(npy(reset), want["reset"]) and np.array_equal(npy(task.reset_succ), want["reset_succ"]), step
+        assert np.array_equal(npy(task.progress_buf), want["progress"]) and np.array_equal(npy(task.success), want["success"]), step
+        assert np.array_equal(npy(task.epis_max_step), want["epis_max_step"]), step
+        assert np.array_equal(bits(task.epis_max_rew), bits(want["epis_max_rew"])), step
+        c = task._counters[2 * task._slot:2 * task._slot + 2].cpu().numpy()
+        assert (int(c[0]), int(c[1])) == (want["n_succ"], want["n_reset"]), step
+        assert np.array_equal(npy(task.extras["succ_rate"]), np.array([want["succ_rate"]], dtype=np.float32)), step
+        assert np.array_equal(bits(pos_act[t(want["reset"])]), bits(np.broadcast_to(fx["default_dof_pos"], (N, 9))[want["reset"]]))
+        if step == 0:
+            assert want["n_reset"] > 0 and want["n_succ"] == 0
+        task.end_step(t(rb), t(dof), t(root))
+        assert np.array_equal(npy(task.progress_buf), want["progress"] + 1)
+        assert np.array_equal(npy(task.success), fx["out64_success"][perm]), step
+        state = dict(rew=npy(task.rew_buf), success=npy(task.success), progress=want["progress"] + 1,
+                     epis_max_rew=want["epis_max_rew"].astype(np.float32), epis_max_step=want["epis_max_step"])
+        assert state["success"].sum() == 16
+
+
+# ------------------------------------------------------------------------------------------- 6. repeatability
+def test_two_calls_give_the_same_bits():
+    st = make_state(257, 14, 9, 7500)
+    a, _ = run_slice(st, 0, 257, 14, 9, 12)
+    b, _ = run_slice(st, 0, 257, 14, 9, 12)
+    for k in a:
+        assert same_bits(a[k], b[k]), k
+
+
+# ------------------------------------------------------------------------------------------- 7. the timing tool
+def test_timing_tool_tiny():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "time_grasp_cube.py"), "--tiny"], cwd=ROOT, capture_output=True,
+                       text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    res = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    row = res["sizes"][0]
+    for k in ("begin_step", "end_step"):
+        assert row["hip_ms"][k] > 0 and row["torch_ms"][k] > 0 and row["launches"]["hip"][k] >= 1, k
+        assert row["launches"]["torch"][k] > row["launches"]["hip"][k], k
+        assert row["share_of_bytes_floor"][k] > 0, k

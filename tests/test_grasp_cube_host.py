@@ -1,0 +1,155 @@
+"""The grasp_cube task step (partmanip_amd.tasks, pm_grasp_cube_post_f32, pm_franka_control_f32), everything that needs no GPU: the
+numpy restatement of the contract (tests/grasp_cube_ref.py) against the REFERENCE's float64 outputs in the fixtures, the fixtures'
+own conditions, argument validation of the C entry points and of the wrappers."""
+import ctypes
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import grasp_cube_ref as G
+from tests.helpers import GOLDEN
+
+FIXTURES = ["grasp_cube_ref_small", "grasp_cube_ref_64"]
+
+
+def load(name):
+    with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+def generator():
+    spec = importlib.util.spec_from_file_location("make_grasp_cube_golden", os.path.join(GOLDEN, "make_grasp_cube_golden.py"))
+    m = importlib.util.module_from_spec(spec)
+    keep = os.environ.get("PYTORCH_JIT")
+    try:
+        spec.loader.exec_module(m)                            # sets PYTORCH_JIT for its own run; irrelevant once torch is imported
+    finally:
+        if keep is None:
+            os.environ.pop("PYTORCH_JIT", None)
+        else:
+            os.environ["PYTORCH_JIT"] = keep
+    return m
+
+
+def ref_post(fx, dtype=np.float64):
+    return G.post(fx["rigid_body"], fx["dof_state"], fx["root"], int(fx["obj_actor"]), int(fx["ltip"]), int(fx["rtip"]), fx["dof_lo"],
+                  fx["dof_hi"], fx["goal"], float(fx["goal_thresh"]), fx["obj_default_pos"], fx["part_body"], fx["part_C"], dtype=dtype)
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_numpy_restatement_reproduces_the_reference_float64(name):
+    fx = load(name)
+    got = ref_post(fx)
+    for k in ("normal_state", "proprio", "rew", "extras", "pose_R", "pose_T"):
+        np.testing.assert_allclose(got[k], fx["out64_" + k], rtol=0, atol=1e-13, err_msg=k)
+    assert np.array_equal(got["success"], fx["out64_success"]) and np.array_equal(got["is_reached"], fx["out64_is_reached"])
+    jl, jr = int(fx["ltip"]) - 1, int(fx["rtip"]) - 1
+    tgt = G.control(fx["actions"], fx["dof_state"], fx["jac"], jl, jr, fx["dof_lo"], fx["dof_hi"], float(fx["dt"]), "ik")
+    np.testing.assert_allclose(tgt, fx["out64_pos_act_ik"], rtol=0, atol=1e-12)
+    pos = G.control(fx["actions_pos"], fx["dof_state"], None, 0, 0, fx["dof_lo"], fx["dof_hi"], float(fx["dt"]), "pos")
+    np.testing.assert_allclose(pos, fx["out64_pos_act_pos"], rtol=0, atol=1e-13)
+    before = dict(rew=fx["out64_rew"], success=fx["out64_success"], progress=fx["before_progress"],
+                  epis_max_rew=fx["before_epis_max_rew"].astype(np.float64), epis_max_step=fx["before_epis_max_step"])
+    for prefix, train, mel in (("", True, 200), ("test_", False, int(fx["max_episode_length_test"]))):
+        s = G.bookkeeping(before, tgt, fx["default_dof_pos"].astype(np.float64), int(fx["explore_step"]), mel, train)
+        o = lambda k: fx["out64_" + prefix + k]               # noqa: E731
+        assert np.array_equal(s["reset"], o("reset")) and np.array_equal(s["progress"], o("after_progress"))
+        assert np.array_equal(s["success"], o("after_success")) and np.array_equal(s["epis_max_step"], o("after_epis_max_step"))
+        np.testing.assert_allclose(s["epis_max_rew"], o("after_epis_max_rew"), rtol=0, atol=1e-13)
+        np.testing.assert_allclose(s["pos_act"], o("pos_act"), rtol=0, atol=1e-12)
+        if train:
+            assert np.array_equal(s["reset_succ"], o("reset_succ"))
+            assert s["n_succ"] == int(o("n_succ")) and s["n_reset"] == int(o("n_reset"))
+            assert np.float32(s["succ_rate"]) == o("succ_rate").reshape(-1)[0]
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_the_generators_conditions_hold_on_the_committed_fixtures(name):
+    fx = load(name)
+    generator().check_conditions(fx)
+    assert fx["rigid_body"].shape[0] == (5 if name.endswith("small") else 64)
+
+
+def test_float32_restatement_is_within_the_reference_margin():
+    """The association the kernel uses (this restatement in float32) against the float64 reference: within 4 e_ref per group."""
+    for name in FIXTURES:
+        fx = load(name)
+        got = ref_post(fx, np.float32)
+        for k in ("normal_state", "proprio", "rew", "extras", "pose_R", "pose_T"):
+            assert got[k].dtype == np.float32, k
+            e_ref = np.abs(fx["out32_" + k].astype(np.float64) - fx["out64_" + k]).max()
+            err = np.abs(got[k].astype(np.float64) - fx["out64_" + k]).max()
+            assert err <= 4 * e_ref, (k, err, e_ref)
+
+
+def test_c_entry_points_reject_null_pointers_and_bad_sizes():
+    from partmanip_amd._lib import lib
+    one = ctypes.c_void_p(16)                                 # a non-null address that is never dereferenced on these paths
+
+    def post(rb=one, N=4, nb=14, nd=9, na=2, obj=1, lt=10, rt=12, ns_stride=37, pr_stride=25, ex_stride=8, part_body=one, M=12,
+             pose_R=one):
+        return lib.pm_grasp_cube_post_f32(rb, one, one, N, nb, nd, na, obj, lt, rt, one, one, one, one, one, 0.025, one, part_body,
+                                          None, M, one, ns_stride, one, pr_stride, one, one, one, one, ex_stride, pose_R, one, None)
+
+    assert post(rb=None) == -1 and post(N=0) == -1 and post(nb=0) == -1 and post(nd=0) == -1
+    assert post(obj=2) == -1 and post(lt=14) == -1 and post(rt=-1) == -1
+    assert post(ns_stride=36) == -1 and post(pr_stride=24) == -1 and post(ex_stride=7) == -1
+    assert post(part_body=None) == -1 and post(M=0) == -1 and post(nb=1000, lt=0, rt=0) == -1
+
+    def ctl(actions=one, A=7, N=4, nd=9, nl=12, jl=9, jr=11, jac=one, mode=0, slot=0, counters=one, act_stride=7):
+        return lib.pm_franka_control_f32(actions, act_stride, A, one, jac, N, nd, nl, jl, jr, one, one, one, 1 / 60, mode, one, one,
+                                         one, 40, 200, 1, one, one, one, one, one, counters, slot, None)
+
+    assert ctl(actions=None) == -1 and ctl(N=0) == -1 and ctl(nd=2) == -1 and ctl(nd=65) == -1 and ctl(A=8) == -1
+    assert ctl(jac=None) == -1 and ctl(jl=12) == -1 and ctl(jr=-1) == -1 and ctl(mode=2) == -1 and ctl(slot=2) == -1
+    assert ctl(counters=None) == -1 and ctl(act_stride=6) == -1 and ctl(mode=1, A=7) == -1
+
+
+def test_wrappers_refuse_cpu_tensors():
+    from partmanip_amd import ops
+    from partmanip_amd.tasks import GraspCubeTensors
+    fx = load("grasp_cube_ref_small")
+    task = GraspCubeTensors(5, "cpu", {"robot": {"driveMode": "ik"}}, 1 / 60)
+    t = lambda k: torch.from_numpy(fx[k])                     # noqa: E731
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        task.end_step(t("rigid_body"), t("dof_state"), t("root"))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        task.begin_step(t("actions"), t("dof_state"), t("jac"))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.grasp_cube_post(t("rigid_body"), t("dof_state"), t("root"), 1, 10, 12, t("dof_lo"), t("dof_hi"), task.pose_lower_limit,
+                            task.pose_upper_limit, t("goal"), 0.025, t("obj_default_pos"))
+
+
+def test_task_surface_and_left_out_drive_modes():
+    import tasks
+    from partmanip_amd.tasks import Franka, GraspCubeTensors
+    from partmanip_amd.tasks.grasp_cube import default_part_body
+    assert tasks.GraspCubeTensors is GraspCubeTensors and tasks.Franka is Franka
+    for mode in ("ik_abs", "heuristic"):
+        with pytest.raises(NotImplementedError, match=mode):
+            GraspCubeTensors(4, "cpu", {"robot": {"driveMode": mode}}, 1 / 60)
+    with pytest.raises(NotImplementedError, match="mobile"):
+        GraspCubeTensors(4, "cpu", {"robot": {"driveMode": "ik", "assetFile": "franka_panda_sdf_mobile"}}, 1 / 60)
+    with pytest.raises(NotImplementedError, match="mobile"):
+        Franka({"driveMode": "ik", "mobile": True}, 1 / 60, 4, "cpu")
+    task = GraspCubeTensors(4, "cpu", {"robot": {"driveMode": "ik"}, "explore_step": 40, "maxEpisodeLength": 200}, 1 / 60)
+    assert task.num_actions == 7 and task.num_obs == {"normal_state": 37, "proprio_state": 25}
+    assert GraspCubeTensors(4, "cpu", {"robot": {"driveMode": "pos"}}, 1 / 60).num_actions == 8
+    assert default_part_body(14) == [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 13] and task.part_body.tolist() == default_part_body(14)
+    fx = load("grasp_cube_ref_small")
+    assert np.array_equal(task.part_C.numpy(), fx["part_C"]) and np.array_equal(task.part_body.numpy(), fx["part_body"])
+    assert np.array_equal(task.pose_lower_limit.numpy(), G.POSE_LO.astype(np.float32))
+    assert np.array_equal(task.robot.dof_lower_limits_tensor.numpy(), fx["dof_lo"])
+    assert np.array_equal(task.robot.dof_upper_limits_tensor.numpy(), fx["dof_hi"])
+    for k in ("obs_buf", "rew_buf", "success", "reset_buf", "reset_succ", "progress_buf", "epis_max_rew", "epis_max_step", "extras",
+              "pos_act", "num_obs", "num_actions", "robot"):
+        assert hasattr(task, k), k
+    assert task.progress_buf.dtype == torch.int64 and float(task.epis_max_rew[0]) == -100.0
+
+
+def test_abi_version():
+    from partmanip_amd import _lib
+    assert _lib.ABI_VERSION >= 156 and _lib.lib.pm_version() == _lib.ABI_VERSION
