@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 156 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 157 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -576,6 +576,64 @@ int pm_franka_control_f32(const float* actions, long act_stride, int A, const fl
                           int drive_mode, const float* rew, uint8_t* success, int64_t* progress, int explore_step,
                           int max_episode_length, int train, float* pos_act, float* epis_max_rew, int64_t* epis_max_step,
                           uint8_t* reset, uint8_t* reset_succ, int32_t* counters, int slot, void* stream);
+
+/* ------------------------------------------------------------------ open_drawer task step (heterogeneous environments)
+ * The tensor program of the reference's tasks/open_drawer.py (compute_observations, compute_reward, reset_idx) with
+ * load_robot.update_state: one launch after physics, one before it next to pm_franka_control_f32.  Neither synchronises, allocates
+ * or uses atomics; both are stream-ordered.
+ *
+ * Every environment holds another cabinet, so the simulator's tensors are flat: rigid_body_all (B, 13), dof_state_all (D, 2), root
+ * (N, na, 13), contiguous.  rigid_body_mask (N, nrb + 2) and dof_state_mask (N, nd + 1) int32 are row indices into them: the robot's
+ * nrb bodies, then the target link and the handle; the robot's nd DOFs, then the target joint.  Per environment: part_bbox_init
+ * (N, 8, 3), part_axis_dir_init (N, 3), joint_lo / joint_hi (N), obj_id (N) int32 in [0, num_objs).
+ *
+ * pm_open_drawer_post_f32.  Row g[s] = rigid_body_all[rigid_body_mask[e, s]], d[k] = dof_state_all[dof_state_mask[e, k]], q = d[nd][0]:
+ *   tip (13) = (g[ltip] + g[rtip]) / 2 (quaternion included: not unit);  gripper_length = |g[ltip][:3] - g[rtip][:3]|
+ *   part_bbox (N, 8, 3) = (part_bbox_init + q axis) R(obj quat)^T + obj pos, R = quat_to_mat of the object's root quaternion
+ *   out = b0 - b4, long = b1 - b0, short = b3 - b0 (each normalised, lengths kept), mid = (b0 + b6) / 2
+ *   normal_state (N, 29 + 2 nd) = [tip 13 | mid 3 | out 3 | short 3 | long 3 | |out| |long| |short| | qpos_normalized nd | qvel nd | q]
+ *   delta = tip[:3] - mid;  reached_out = |delta . out| < |out| / 2;  reached_long likewise;  reached_short = ((g[ltip][:3] - mid) .
+ *   short) ((g[rtip][:3] - mid) . short) < 0;  is_reached = all three;  reaching = -|delta| + 0.1 (any of the three)
+ *   axes by quat_rotate(tip[3:7], e) = e (2 w^2 - 1) + 2 w (q x e) + 2 q (q . e): grip = e_z, sep = e_y, down = e_x
+ *   rot = -grip . out + max(sep . short, -sep . short) + max(down . long, -down . long) - 3
+ *   close = (0.1 - gripper_length) is_reached + 0.1 (gripper_length - 0.1) (not is_reached)
+ *   is_grasped = is_reached and gripper_length < |short| + 0.01 and rot > -0.2;  frac = (q - joint_lo) / joint_hi
+ *   joint_state = is_grasped (0.1 + min(frac, suc_prop));  is_open_notgrasp = frac > 0.1;  is_open = is_grasped and is_open_notgrasp
+ *   base = reaching + 0.5 rot + 5 close + 5 joint_state;  success = is_grasped and q - joint_lo >= suc_prop joint_hi
+ *   rew = base + |base| rot + 2 success;  min / max propagate NaN, comparisons with NaN are false
+ *   extras (N, 8) = is_open, is_open_notgrasp, reaching_reward, close_reward, rot_reward, joint_state_reward, raw_reward, is_grasped
+ *   succ_objid (num_objs) bytes: succ_objid[obj_id[e]] = 1 where success (sticky: never cleared here)
+ *   robot_dof_state (N, nd, 2) = d[:nd], part_dof_state (N, 2) = d[nd]: the gathered rows, bit for bit
+ *   pose_T (N, M, 3) = g[part_slot[p]][:3];  pose_R (N, M, 3, 3) = quat_to_mat(g[part_slot[p]][3:7]) C_p (part_C NULL: identity)
+ * Every output may be NULL (skipped).  normal_state and extras take a row stride in elements; nothing outside the named columns is
+ * written.  A mask entry outside its tensor reads as NaN and a part_slot entry outside [0, nrb + 2) gives NaN poses; neither is
+ * dereferenced; an obj_id outside [0, num_objs) sets no flag.  An environment's outputs depend on its own rows only.
+ * PM_EINVAL: a NULL input, N, nrb, nd, na, B, D < 1, B or D >= 2^31, an index outside its range, a row stride below the row width,
+ * succ_objid without obj_id or with num_objs < 1, pose outputs without part_slot or with M < 1, rows too large for the staging.
+ *
+ * pm_open_drawer_reset_f32 = the state half of open_drawer.reset_idx, after pm_franka_control_f32 wrote pos_act (N, nd) and reset (N).
+ * Every environment: pos_act_all[dof_state_mask[e, k]] = pos_act[e, k], k < nd.  Environments with reset[e] != 0, in place:
+ *   root[e, robot_actor, :7] = robot_default_root;  root[e, obj_actor, :7] = obj_default_root;  root[e, :, 7:] = 0
+ *   random_reset != 0, u (N, 4) in [0, 1): position += u[:3] t_range 2 - t_range;  quaternion = quat_mul(default, (0, 0, sin a, cos a)),
+ *   a = u[3] r_range 2 - r_range, quat_mul in Isaac Gym's association
+ *   dof_state_all[dof_state_mask[e, k]] = (default_dof_pos[k], 0), k < nd;  dof_state_all[dof_state_mask[e, nd]] = (joint_lo[e], 0)
+ *   robot_dof_state[e] and part_dof_state[e] (either may be NULL) receive the same values
+ * Nothing else is written: other environments' rows and a cabinet's other joints stay as they are.  dof_state_mask must not name a
+ * row twice (the writes would race); entries outside [0, D) are skipped.
+ * PM_EINVAL: a NULL pointer (u with random_reset), N, nd, na, D < 1, D >= 2^31, an actor outside [0, na), robot_actor == obj_actor. */
+int pm_open_drawer_post_f32(const float* rigid_body_all, long B, const float* dof_state_all, long D, const float* root, int N, int nrb,
+                            int nd, int na, int obj_actor, int ltip, int rtip, const int32_t* rigid_body_mask,
+                            const int32_t* dof_state_mask, const int32_t* obj_id, int num_objs, const float* part_bbox_init,
+                            const float* part_axis_dir_init, const float* joint_lo, const float* joint_hi, const float* dof_lo,
+                            const float* dof_hi, float suc_prop, const int32_t* part_slot, const float* part_C, int M,
+                            float* normal_state, long ns_stride, float* rew, uint8_t* success, uint8_t* is_reached, float* part_bbox,
+                            float* extras, long ex_stride, uint8_t* succ_objid, float* robot_dof_state, float* part_dof_state,
+                            float* pose_R, float* pose_T, void* stream);
+int pm_open_drawer_reset_f32(const uint8_t* reset, const float* pos_act, const int32_t* dof_state_mask, int N, int nd, int na,
+                             int robot_actor, int obj_actor, const float* robot_default_root, const float* obj_default_root,
+                             int random_reset, const float* u, float t_range, float r_range, const float* default_dof_pos,
+                             const float* joint_lo, float* root, float* dof_state_all, long D, float* pos_act_all,
+                             float* robot_dof_state, float* part_dof_state, void* stream);
 
 /* ------------------------------------------------------------------ K15 fused set-abstraction level
  * One PointNet++ SA level (north_star; not in the reference snapshot, README.md:23,30) as one forward and

@@ -39,30 +39,13 @@
 // environments per block chosen at 4096 environments (512 blocks), never more than 48 KB.  franka_control_kernel 58 VGPRs, 58 SGPRs,
 // no scratch, 8 waves / SIMD; LDS eb * (6 (nd - 2) + 1) floats = 1.4 KB at 8 environments per block.  Times: profiles/grasp_cube_timing.json.
 #include "common.h"
+#include "task_common.h"                                      // gc_quat_to_mat, gc_scale, gc_norm3
 
 #define GC_THREADS 256
 #define GC_EB_MAX 32                                         // environments per block (at most; the first wave holds one per lane)
 #define GC_LDS_MAX 49152                                     // bytes of dynamic LDS a block may ask for
 #define FC_THREADS 64
 #define FC_ND_MAX 64
-
-// torch_jit_utils.py:375-403, q = (i, j, k, r)
-__device__ __forceinline__ void gc_quat_to_mat(const float* q, float* m) {
-    const float i = q[0], j = q[1], k = q[2], r = q[3];
-    const float two_s = 2.0f / (((i * i + j * j) + k * k) + r * r);
-    m[0] = 1.0f - two_s * (j * j + k * k);
-    m[1] = two_s * (i * j - k * r);
-    m[2] = two_s * (i * k + j * r);
-    m[3] = two_s * (i * j + k * r);
-    m[4] = 1.0f - two_s * (i * i + k * k);
-    m[5] = two_s * (j * k - i * r);
-    m[6] = two_s * (i * k - j * r);
-    m[7] = two_s * (j * k + i * r);
-    m[8] = 1.0f - two_s * (i * i + j * j);
-}
-
-__device__ __forceinline__ float gc_scale(float x, float lo, float hi) { return (2.0f * (x - lo)) / (hi - lo) - 1.0f; }
-__device__ __forceinline__ float gc_norm3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
 
 // torch_jit_utils.py:412-425: candidate c takes columns (a, b) = IND[c % 6] of R, row 0 of both negated for c < 12, row 1 for
 // 6 <= c < 18, third column = first x second; the candidate of largest trace, the lowest c on ties.  o: 3 x 3 row-major.

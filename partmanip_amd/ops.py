@@ -1458,6 +1458,144 @@ def franka_control(actions, dof_state, jac, jl, jr, dof_lo, dof_hi, default_dof_
     return pos_act
 
 
+def _flags(t_, name, n):
+    if t_.dtype not in (torch.bool, torch.uint8) or not t_.is_contiguous() or t_.numel() != n:
+        raise ValueError(f"{name}: expected a contiguous bool / uint8 tensor of {n} elements, got {t_.dtype} {tuple(t_.shape)}")
+
+
+def _shape_f32c(t_, name, shape):
+    _f32c(t_, name)
+    if tuple(t_.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected {tuple(shape)}, got {tuple(t_.shape)}")
+
+
+def _index_table(t_, name, N):
+    if t_.dtype != torch.int32 or t_.dim() != 2 or t_.shape[0] != N or not t_.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous int32 tensor ({N}, width), got {t_.dtype} {tuple(t_.shape)}")
+    return t_.shape[1]
+
+
+def open_drawer_post(rigid_body_all, dof_state_all, root, rigid_body_mask, dof_state_mask, obj_actor, ltip, rtip, part_bbox_init,
+                     part_axis_dir_init, joint_lo, joint_hi, dof_lo, dof_hi, suc_prop=0.5, obj_id=None, part_slot=None, part_C=None,
+                     normal_state=None, rew=None, success=None, is_reached=None, part_bbox=None, extras=None, succ_objid=None,
+                     robot_dof_state=None, part_dof_state=None, pose_R=None, pose_T=None):
+    """Everything after physics of the open_drawer task in one launch (pm_open_drawer_post_f32, include/partmanip_hip.h): flat
+    rigid_body_all (B, 13) and dof_state_all (D, 2), root (N, na, 13), all contiguous float32, reached through rigid_body_mask
+    (N, nrb + 2) and dof_state_mask (N, nd + 1) int32 (the caller guarantees their range: OpenDrawerTensors checks it once).
+    Outputs are written in place and every one may be None (skipped): normal_state (N, 29 + 2 nd) and extras (N, 8) may be column
+    views of a wider buffer; rew (N); success, is_reached (N) and succ_objid (num_objs, with obj_id (N) int32) bool or uint8;
+    part_bbox (N, 8, 3); robot_dof_state (N, nd, 2); part_dof_state (N, 2); pose_R (N, M, 3, 3), pose_T (N, M, 3) with part_slot
+    (M) int32 and part_C (M, 3, 3) or None."""
+    for t_, name, w in ((rigid_body_all, "rigid_body_all", 13), (dof_state_all, "dof_state_all", 2)):
+        _f32c(t_, name)
+        if t_.dim() != 2 or t_.shape[1] != w or t_.shape[0] == 0:
+            raise ValueError(f"{name}: expected (rows, {w}), got {tuple(t_.shape)}")
+    _f32c(root, "root")
+    if root.dim() != 3 or root.shape[2] != 13 or root.shape[0] == 0 or root.shape[1] == 0:
+        raise ValueError(f"root: expected (N, na, 13), got {tuple(root.shape)}")
+    N, na = root.shape[0], root.shape[1]
+    B, D = rigid_body_all.shape[0], dof_state_all.shape[0]
+    nrb = _index_table(rigid_body_mask, "rigid_body_mask", N) - 2
+    nd = _index_table(dof_state_mask, "dof_state_mask", N) - 1
+    if nrb < 1 or nd < 1:
+        raise ValueError(f"masks: expected widths nrb + 2 >= 3 and nd + 1 >= 2, got {nrb + 2} and {nd + 1}")
+    if not (0 <= obj_actor < na and 0 <= ltip < nrb and 0 <= rtip < nrb):
+        raise ValueError(f"obj_actor {obj_actor} / ltip {ltip} / rtip {rtip} outside ({na} actors, {nrb} robot bodies)")
+    _shape_f32c(part_bbox_init, "part_bbox_init", (N, 8, 3))
+    _shape_f32c(part_axis_dir_init, "part_axis_dir_init", (N, 3))
+    for t_, name, n in ((joint_lo, "joint_lo", N), (joint_hi, "joint_hi", N), (dof_lo, "dof_lo", nd), (dof_hi, "dof_hi", nd)):
+        _vec(t_, name, n)
+    num_objs = 0
+    if succ_objid is not None:
+        if obj_id is None:
+            raise ValueError("succ_objid needs obj_id (N) int32")
+        num_objs = succ_objid.numel()
+        if num_objs == 0:
+            raise ValueError("succ_objid: expected at least one object")
+        _flags(succ_objid, "succ_objid", num_objs)
+    if obj_id is not None:
+        _vec(obj_id, "obj_id", N, torch.int32)
+    M = 0
+    if pose_R is not None or pose_T is not None:
+        if part_slot is None or part_slot.dim() != 1 or part_slot.numel() == 0:
+            raise ValueError("pose_R / pose_T need part_slot (M) int32")
+        M = part_slot.numel()
+        _vec(part_slot, "part_slot", M, torch.int32)
+        if part_C is not None:
+            _shape_f32c(part_C, "part_C", (M, 3, 3))
+        for t_, name, shape in ((pose_R, "pose_R", (N, M, 3, 3)), (pose_T, "pose_T", (N, M, 3))):
+            if t_ is not None:
+                _shape_f32c(t_, name, shape)
+    lns = _row_view(normal_state, "normal_state", N, 29 + 2 * nd) if normal_state is not None else 0
+    lex = _row_view(extras, "extras", N, 8) if extras is not None else 0
+    if rew is not None:
+        _vec(rew, "rew", N)
+    for t_, name in ((success, "success"), (is_reached, "is_reached")):
+        if t_ is not None:
+            _flags(t_, name, N)
+    for t_, name, shape in ((part_bbox, "part_bbox", (N, 8, 3)), (robot_dof_state, "robot_dof_state", (N, nd, 2)),
+                            (part_dof_state, "part_dof_state", (N, 2))):
+        if t_ is not None:
+            _shape_f32c(t_, name, shape)
+    every = (rigid_body_all, dof_state_all, root, rigid_body_mask, dof_state_mask, part_bbox_init, part_axis_dir_init, joint_lo,
+             joint_hi, dof_lo, dof_hi, obj_id, part_slot, part_C, normal_state, rew, success, is_reached, part_bbox, extras,
+             succ_objid, robot_dof_state, part_dof_state, pose_R, pose_T)
+    _req(*every)
+    if any(t_ is not None and t_.device != root.device for t_ in every):
+        raise ValueError("open_drawer_post: all tensors must live on one device")
+    with TIMER.bracket("open_drawer_post"):
+        check(lib.pm_open_drawer_post_f32(_ptr(rigid_body_all), B, _ptr(dof_state_all), D, _ptr(root), N, nrb, nd, na, int(obj_actor),
+                                          int(ltip), int(rtip), _ptr(rigid_body_mask), _ptr(dof_state_mask), _ptr(obj_id), num_objs,
+                                          _ptr(part_bbox_init), _ptr(part_axis_dir_init), _ptr(joint_lo), _ptr(joint_hi),
+                                          _ptr(dof_lo), _ptr(dof_hi), float(suc_prop), _ptr(part_slot), _ptr(part_C), M,
+                                          _ptr(normal_state), lns, _ptr(rew), _ptr(success), _ptr(is_reached), _ptr(part_bbox),
+                                          _ptr(extras), lex, _ptr(succ_objid), _ptr(robot_dof_state), _ptr(part_dof_state),
+                                          _ptr(pose_R), _ptr(pose_T), _stream()), "pm_open_drawer_post_f32")
+
+
+def open_drawer_reset(reset, pos_act, dof_state_mask, root, dof_state_all, pos_act_all, robot_actor, obj_actor, robot_default_root,
+                      obj_default_root, default_dof_pos, joint_lo, u=None, t_range=0.05, r_range=0.2617993877991494,
+                      robot_dof_state=None, part_dof_state=None):
+    """The state half of open_drawer.reset_idx in one launch (pm_open_drawer_reset_f32), in place: pos_act (N, nd) is scattered into
+    pos_act_all (D) through dof_state_mask (N, nd + 1) int32 for every environment; environments with reset (N) bool / uint8 set get
+    their default root rows in root (N, na, 13) (u (N, 4) in [0, 1), when given, perturbs the object's position and yaw), default DOF
+    rows in dof_state_all (D, 2) and the same values in robot_dof_state (N, nd, 2) / part_dof_state (N, 2).  dof_state_mask must
+    not name a row twice."""
+    _f32c(root, "root")
+    if root.dim() != 3 or root.shape[2] != 13 or root.shape[0] == 0 or root.shape[1] == 0:
+        raise ValueError(f"root: expected (N, na, 13), got {tuple(root.shape)}")
+    N, na = root.shape[0], root.shape[1]
+    nd = _index_table(dof_state_mask, "dof_state_mask", N) - 1
+    if nd < 1:
+        raise ValueError(f"dof_state_mask: expected a width nd + 1 >= 2, got {nd + 1}")
+    _f32c(dof_state_all, "dof_state_all")
+    if dof_state_all.dim() != 2 or dof_state_all.shape[1] != 2 or dof_state_all.shape[0] == 0:
+        raise ValueError(f"dof_state_all: expected (D, 2), got {tuple(dof_state_all.shape)}")
+    D = dof_state_all.shape[0]
+    _flags(reset, "reset", N)
+    for t_, name, n in ((pos_act, "pos_act", N * nd), (pos_act_all, "pos_act_all", D), (robot_default_root, "robot_default_root", 7),
+                        (obj_default_root, "obj_default_root", 7), (default_dof_pos, "default_dof_pos", nd), (joint_lo, "joint_lo", N)):
+        _vec(t_, name, n)
+    if not (0 <= robot_actor < na and 0 <= obj_actor < na) or robot_actor == obj_actor:
+        raise ValueError(f"robot_actor {robot_actor} / obj_actor {obj_actor}: expected two different actors of {na}")
+    if u is not None:
+        _shape_f32c(u, "u", (N, 4))
+    for t_, name, shape in ((robot_dof_state, "robot_dof_state", (N, nd, 2)), (part_dof_state, "part_dof_state", (N, 2))):
+        if t_ is not None:
+            _shape_f32c(t_, name, shape)
+    every = (reset, pos_act, dof_state_mask, root, dof_state_all, pos_act_all, robot_default_root, obj_default_root, default_dof_pos,
+             joint_lo, u, robot_dof_state, part_dof_state)
+    _req(*every)
+    if any(t_ is not None and t_.device != root.device for t_ in every):
+        raise ValueError("open_drawer_reset: all tensors must live on one device")
+    with TIMER.bracket("open_drawer_reset"):
+        check(lib.pm_open_drawer_reset_f32(_ptr(reset), _ptr(pos_act), _ptr(dof_state_mask), N, nd, na, int(robot_actor),
+                                           int(obj_actor), _ptr(robot_default_root), _ptr(obj_default_root), 0 if u is None else 1,
+                                           _ptr(u), float(t_range), float(r_range), _ptr(default_dof_pos), _ptr(joint_lo), _ptr(root),
+                                           _ptr(dof_state_all), D, _ptr(pos_act_all), _ptr(robot_dof_state), _ptr(part_dof_state),
+                                           _stream()), "pm_open_drawer_reset_f32")
+
+
 def mesh_sdf_bake(tri, shape, voxel_size, centre, trunc, tri_cull=True):
     """Signed-distance grid of a triangle mesh (pm_mesh_sdf_bake_f32): tri (F, 3, 3) float32 corner positions, shape = (X, Y, Z),
     voxel (i, j, k) at (idx - shape // 2) * voxel_size + centre (3 floats; fp32, two roundings).  Returns (X, Y, Z) float32:

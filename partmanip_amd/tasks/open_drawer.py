@@ -1,0 +1,238 @@
+"""The tensor program of the reference's open_drawer task (tasks/open_drawer.py compute_observations / compute_reward / reset_idx,
+tasks/hand_base.py:363-392) around any simulator whose environments differ: flat state tensors and two index tables in, observation
+rows, reward, reset flags, part poses, joint targets and the reset rows of the state tensors out.
+
+    task = OpenDrawerTensors(num_envs, device, cfg, dt, rigid_body_mask, dof_state_mask, obj_id, part_bbox_init,
+                             part_axis_dir_init, part_joint_lower_limits, part_joint_upper_limits, num_objs)
+    pos_act_all, reset = task.begin_step(actions, jacobian, dof_state_all, root, pos_act_all)   # two launches; then: your step
+    obs, rew, reset, extras = task.end_step(rigid_body_all, dof_state_all, root)                # one launch (+ progress_buf += 1)
+    rot, pos = task.compute_scene_pose()                                  # -> TSDFfromMesh.query_tsdf / PCfromMesh.query_pc
+
+What stays with the caller is what the reference does through Isaac Gym: stepping the simulator, handing `pos_act_all` to its
+position drive and pushing the rewritten rows of `dof_state_all` / `root` into it with its indexed setters.  The index lists those
+setters want (`global_indices[env_ids]`) are built by the caller from `reset_buf`: that is a host read or a nonzero(), which this
+class never does.
+
+Left out: mobile bases and the drive modes 'ik_abs' and 'heuristic' (NotImplementedError naming them, raised by Franka; the shipped
+cfg/tasks/open_drawer.yaml asks for the mobile base and is refused that way), the reference's random STREAM (see begin_step) and
+extras['step_id'] (it is `progress_buf.float()`)."""
+import math
+
+import numpy as np
+import torch
+
+from .. import ops
+from .franka import Franka
+
+EXTRAS_COLUMNS = ("is_open", "is_open_notgrasp", "reaching_reward", "close_reward", "rot_reward", "joint_state_reward", "raw_reward",
+                  "is_grasped")
+OBJ_DEFAULT_ROOT = (-0.6, 0.0, 0.5, 0.0, 0.0, 1.0, 0.0)        # open_drawer.py:44
+RESET_T_RANGE, RESET_R_RANGE = 0.05, math.pi / 12             # open_drawer.py:46-47
+SUC_PROP = 0.5                                                # open_drawer.py:84
+
+
+def default_part_slot(num_rigid_body):
+    """The 11 robot parts GraspCubeTensors poses (bodies 0-9 and the right finger), then the target link and the handle, as slots of
+    an environment's gathered rows."""
+    if num_rigid_body < 12:
+        raise ValueError(f"the default part list needs at least 12 robot bodies, got {num_rigid_body}")
+    return list(range(10)) + [num_rigid_body - 2, num_rigid_body, num_rigid_body + 1]
+
+
+def build_masks(num_robot_bodies, num_robot_dofs, obj_bodies, obj_dofs, target_link, target_handle, target_dof):
+    """The index tables as open_drawer.py:58-70 builds them, for environments laid out one after the other (robot first): obj_bodies /
+    obj_dofs (N) are each cabinet's body and DOF counts, target_link / target_handle / target_dof (N) index into the cabinet.
+    Returns (rigid_body_mask (N, nrb + 2), dof_state_mask (N, nd + 1)) int32 numpy and the totals (B, D)."""
+    N = len(obj_bodies)
+    rb = np.zeros((N, num_robot_bodies + 2), dtype=np.int32)
+    dm = np.zeros((N, num_robot_dofs + 1), dtype=np.int32)
+    rigid_count = dof_count = 0
+    for i in range(N):
+        dm[i, :num_robot_dofs] = np.arange(dof_count, dof_count + num_robot_dofs)
+        dm[i, -1] = dof_count + num_robot_dofs + int(target_dof[i])
+        rb[i, :num_robot_bodies] = np.arange(rigid_count, rigid_count + num_robot_bodies)
+        rb[i, -2] = rigid_count + num_robot_bodies + int(target_link[i])
+        rb[i, -1] = rigid_count + num_robot_bodies + int(target_handle[i])
+        dof_count += num_robot_dofs + int(obj_dofs[i])
+        rigid_count += num_robot_bodies + int(obj_bodies[i])
+    return rb, dm, rigid_count, dof_count
+
+
+def _host_ints(x, name, shape):
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{name}: expected an integer array, got {a.dtype}")
+    if a.shape != tuple(shape):
+        raise ValueError(f"{name}: expected {tuple(shape)}, got {a.shape}")
+    return a.astype(np.int64)
+
+
+class OpenDrawerTensors:
+    """cfg: the task's dictionary (robot.driveMode, robot.dof, robot.root, explore_step, maxEpisodeLength, random_reset).  The robot
+    is the fixed-base Franka with the 'ik' and 'pos' drives: a cfg that asks for a mobile base (cfg/tasks/open_drawer.yaml does) or
+    for 'ik_abs' / 'heuristic' raises NotImplementedError.  robot.root defaults to the identity pose at the origin.
+
+    rigid_body_mask (N, nrb + 2) and dof_state_mask (N, nd + 1): row indices into the simulator's flat rigid-body and DOF tensors
+    (build_masks), checked here once on the host: every index >= 0 (and below num_rigid_bodies / num_dof_states when those totals
+    are given; the tensors handed to begin_step / end_step must have at least max index + 1 rows either way), no index twice in
+    dof_state_mask; ValueError otherwise.  obj_id (N) in [0, num_objs); part_bbox_init (N, 8, 3) already scaled;
+    part_joint_upper_limits already multiplied by the object scale.  part_slot (M) / part_C (M, 3, 3) or None choose the posed
+    parts among an environment's nrb + 2 gathered rows (default: default_part_slot with the Franka's mesh-frame matrices, identity
+    for the link and the handle)."""
+
+    def __init__(self, num_envs, device, cfg, dt, rigid_body_mask, dof_state_mask, obj_id, part_bbox_init, part_axis_dir_init,
+                 part_joint_lower_limits, part_joint_upper_limits, num_objs, num_rigid_bodies=None, num_dof_states=None,
+                 num_actors=2, robot_actor=0, obj_actor=1, robot=None, part_slot=None, part_C="default",
+                 obj_default_root=OBJ_DEFAULT_ROOT, suc_prop=SUC_PROP):
+        self.num_envs, self.device, self.dt = int(num_envs), device, float(dt)
+        N = self.num_envs
+        self.robot = robot if robot is not None else Franka(cfg.get("robot", {}), dt, num_envs, device)
+        nd, nrb = self.robot.num_dofs, self.robot.num_rigid_body
+        self.num_actors, self.robot_actor, self.obj_actor = int(num_actors), int(robot_actor), int(obj_actor)
+        if not (0 <= self.robot_actor < self.num_actors and 0 <= self.obj_actor < self.num_actors) or self.robot_actor == self.obj_actor:
+            raise ValueError(f"robot_actor {robot_actor} / obj_actor {obj_actor}: expected two different actors of {num_actors}")
+        self.num_objs = int(num_objs)
+        if self.num_objs < 1:
+            raise ValueError(f"num_objs must be at least 1, got {num_objs}")
+        rbm = _host_ints(rigid_body_mask, "rigid_body_mask", (N, nrb + 2))
+        dfm = _host_ints(dof_state_mask, "dof_state_mask", (N, nd + 1))
+        for a, name, total in ((rbm, "rigid_body_mask", num_rigid_bodies), (dfm, "dof_state_mask", num_dof_states)):
+            hi = int(total) if total is not None else 2 ** 31 - 1
+            if a.min() < 0 or a.max() >= hi:
+                raise ValueError(f"{name}: indices must lie in [0, {hi}), got [{a.min()}, {a.max()}]")
+        if np.unique(dfm).size != dfm.size:
+            raise ValueError("dof_state_mask: an index appears twice (two environments would write one DOF row)")
+        self.num_rigid_bodies = int(num_rigid_bodies) if num_rigid_bodies is not None else int(rbm.max()) + 1
+        self.num_dof_states = int(num_dof_states) if num_dof_states is not None else int(dfm.max()) + 1
+        oid = _host_ints(obj_id, "obj_id", (N,))
+        if oid.min() < 0 or oid.max() >= self.num_objs:
+            raise ValueError(f"obj_id: values must lie in [0, {self.num_objs}), got [{oid.min()}, {oid.max()}]")
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)   # noqa: E731
+        self.rigid_body_mask, self.dof_state_mask, self.obj_id = i32(rbm), i32(dfm), i32(oid)
+        f = dict(dtype=torch.float32, device=device)
+
+        def const(x, name, shape):
+            v = torch.as_tensor(x, dtype=torch.float32).to(device).contiguous()
+            if tuple(v.shape) != shape:
+                raise ValueError(f"{name}: expected {shape}, got {tuple(v.shape)}")
+            return v
+
+        self.part_bbox_init = const(part_bbox_init, "part_bbox_init", (N, 8, 3))
+        self.part_axis_dir_init = const(part_axis_dir_init, "part_axis_dir_init", (N, 3))
+        self.part_joint_lower_limits = const(part_joint_lower_limits, "part_joint_lower_limits", (N,))
+        self.part_joint_upper_limits = const(part_joint_upper_limits, "part_joint_upper_limits", (N,))
+        self.obj_default_root = const(obj_default_root, "obj_default_root", (7,))
+        root = self.robot.default_root
+        self.robot_default_root = const((0, 0, 0, 0, 0, 0, 1) if root is None else root.reshape(-1)[:7], "robot.root", (7,))
+        self.num_actions = self.robot.num_actions
+        self.num_obs = {"normal_state": 29 + 2 * nd}
+        self.max_episode_length = int(cfg.get("maxEpisodeLength", 200))
+        self.explore_step = int(cfg.get("explore_step", 40))
+        self.random_reset = bool(cfg.get("random_reset", False))
+        self.reset_t_range, self.reset_r_range, self.suc_prop = RESET_T_RANGE, RESET_R_RANGE, float(suc_prop)
+        self.train_test_flag = "train"
+        if part_slot is None:
+            part_slot = default_part_slot(nrb)
+            if isinstance(part_C, str):
+                part_C = torch.cat([self.robot.coordinate_transform_matrix.to(device), torch.eye(3, **f).expand(2, 3, 3)])
+        elif isinstance(part_C, str):
+            part_C = None
+        self.part_slot = torch.as_tensor(part_slot, dtype=torch.int32).reshape(-1).to(device).contiguous()
+        self.part_C = None if part_C is None else torch.as_tensor(part_C, dtype=torch.float32).to(device).contiguous()
+        M = self.part_slot.numel()
+        self.obs_buf = {"normal_state": torch.zeros(N, self.num_obs["normal_state"], **f)}
+        self.rew_buf = torch.zeros(N, **f)
+        b = dict(dtype=torch.bool, device=device)
+        self.success, self.is_reached = torch.zeros(N, **b), torch.zeros(N, **b)
+        self.reset_buf, self.reset_succ = torch.zeros(N, **b), torch.zeros(N, **b)
+        self.succ_objid_lst = torch.zeros(self.num_objs, **b)
+        self.progress_buf = torch.zeros(N, dtype=torch.long, device=device)
+        self.epis_max_rew = torch.full((N,), -100.0, **f)
+        self.epis_max_step = torch.zeros(N, dtype=torch.long, device=device)
+        self.pos_act = torch.zeros(N, nd, **f)
+        self.robot_dof_state = torch.zeros(N, nd, 2, **f)
+        self.part_dof_state = torch.zeros(N, 2, **f)
+        self.part_bbox = torch.zeros(N, 8, 3, **f)
+        self.pose_R = torch.zeros(N, M, 3, 3, **f)
+        self.pose_T = torch.zeros(N, M, 3, **f)
+        self._extras = torch.zeros(N, len(EXTRAS_COLUMNS), **f)
+        self.extras = {k: self._extras[:, i] for i, k in enumerate(EXTRAS_COLUMNS)}
+        self.extras["is_reached"] = self.is_reached
+        self.extras["success_objnum"] = self.succ_objid_lst
+        self._counters = torch.zeros(4, dtype=torch.int32, device=device)
+        self._slot = 1
+
+    def _check_state(self, rigid_body_all, dof_state_all, root, pos_act_all):
+        if rigid_body_all is not None and (rigid_body_all.dim() != 2 or rigid_body_all.shape[0] < self.num_rigid_bodies):
+            raise ValueError(f"rigid_body_all: expected (>= {self.num_rigid_bodies}, 13), got {tuple(rigid_body_all.shape)}")
+        if dof_state_all.dim() != 2 or dof_state_all.shape[0] < self.num_dof_states:
+            raise ValueError(f"dof_state_all: expected (>= {self.num_dof_states}, 2), got {tuple(dof_state_all.shape)}")
+        if tuple(root.shape) != (self.num_envs, self.num_actors, 13):
+            raise ValueError(f"root: expected {(self.num_envs, self.num_actors, 13)}, got {tuple(root.shape)}")
+        if pos_act_all is not None and pos_act_all.numel() != dof_state_all.shape[0]:
+            raise ValueError(f"pos_act_all: expected {dof_state_all.shape[0]} elements, got {pos_act_all.numel()}")
+
+    def _reset_launch(self, flags, dof_state_all, root, pos_act_all, u):
+        if self.random_reset and u is None:
+            u = torch.rand(self.num_envs, 4, dtype=torch.float32, device=root.device)
+        r = self.robot
+        ops.open_drawer_reset(flags, self.pos_act, self.dof_state_mask, root, dof_state_all, pos_act_all, self.robot_actor,
+                              self.obj_actor, self.robot_default_root, self.obj_default_root, r.default_dof_pos,
+                              self.part_joint_lower_limits, u if self.random_reset else None, self.reset_t_range, self.reset_r_range,
+                              robot_dof_state=self.robot_dof_state, part_dof_state=self.part_dof_state)
+
+    def begin_step(self, actions, jacobian, dof_state_all, root, pos_act_all, u=None):
+        """hand_base.pre_physics_step with open_drawer.reset_idx: joint targets from the actions and the robot DOF state of the last
+        end_step (or reset), the episode bookkeeping, then in one more launch the scatter of the targets into pos_act_all (D) and, for
+        the environments that start over, the default rows of root (N, na, 13) and dof_state_all (D, 2), in place.
+
+        u (N, 4) in [0, 1) drives the perturbation when cfg['random_reset'] is set (row e: translation x, y, z and yaw of environment e);
+        None draws it with torch.rand.  The random STREAM is therefore not the reference's, whose number of draws depends on how many
+        environments reset (a host read here); the distribution is the same.  Returns (pos_act_all, reset_buf)."""
+        if self.train_test_flag not in ("train", "test"):
+            raise NotImplementedError(f"train_test_flag {self.train_test_flag!r}")
+        self._check_state(None, dof_state_all, root, pos_act_all)
+        train = self.train_test_flag == "train"
+        self._slot ^= 1
+        r = self.robot
+        ops.franka_control(actions, self.robot_dof_state, jacobian, r.ltip_rb_index - 1, r.rtip_rb_index - 1, r.dof_lower_limits_tensor,
+                           r.dof_upper_limits_tensor, r.default_dof_pos, self.dt, r.driveMode, self.rew_buf, self.success,
+                           self.progress_buf, self.explore_step, self.max_episode_length, train, self.pos_act, self.epis_max_rew,
+                           self.epis_max_step, self.reset_buf, self.reset_succ, self._counters, self._slot)
+        self._reset_launch(self.reset_buf, dof_state_all, root, pos_act_all, u)
+        if train:                                             # hand_base.py:373
+            c = self._counters[2 * self._slot:2 * self._slot + 2]
+            self.extras["succ_rate"] = c[0:1] / torch.clamp(c[1], min=1)
+        return pos_act_all, self.reset_buf
+
+    def reset(self, dof_state_all, root, pos_act_all, u=None):
+        """hand_base.reset's reset_idx(ones): every environment's buffers and state rows start over (the same launch as in begin_step
+        with every flag set).  The caller then pushes the state into its simulator, steps it once and calls end_step."""
+        self._check_state(None, dof_state_all, root, pos_act_all)
+        self.pos_act.copy_(self.robot.default_dof_pos.expand_as(self.pos_act))
+        self.progress_buf.zero_()
+        self.success.zero_()
+        self.epis_max_rew.fill_(-100.0)
+        self.epis_max_step.zero_()
+        self._reset_launch(torch.ones(self.num_envs, dtype=torch.bool, device=root.device), dof_state_all, root, pos_act_all, u)
+        return pos_act_all
+
+    def end_step(self, rigid_body_all, dof_state_all, root):
+        """hand_base.post_physics_step: progress_buf += 1, then the gather, observation rows, reward, flags, the per-object success
+        flags and part poses in one launch.  rigid_body_all (B, 13), dof_state_all (D, 2), root (N, na, 13)."""
+        self._check_state(rigid_body_all, dof_state_all, root, None)
+        self.progress_buf += 1
+        r = self.robot
+        ops.open_drawer_post(rigid_body_all, dof_state_all, root, self.rigid_body_mask, self.dof_state_mask, self.obj_actor,
+                             r.ltip_rb_index, r.rtip_rb_index, self.part_bbox_init, self.part_axis_dir_init,
+                             self.part_joint_lower_limits, self.part_joint_upper_limits, r.dof_lower_limits_tensor,
+                             r.dof_upper_limits_tensor, self.suc_prop, obj_id=self.obj_id, part_slot=self.part_slot, part_C=self.part_C,
+                             normal_state=self.obs_buf["normal_state"], rew=self.rew_buf, success=self.success,
+                             is_reached=self.is_reached, part_bbox=self.part_bbox, extras=self._extras,
+                             succ_objid=self.succ_objid_lst, robot_dof_state=self.robot_dof_state,
+                             part_dof_state=self.part_dof_state, pose_R=self.pose_R, pose_T=self.pose_T)
+        return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
+
+    def compute_scene_pose(self):
+        """(rot (N, M, 3, 3), pos (N, M, 3)) of the last end_step: the input of query_tsdf / query_pc."""
+        return self.pose_R, self.pose_T

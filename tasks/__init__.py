@@ -1,3 +1,3 @@
-"""Import surface in the manner of the reference's `tasks` package: `from tasks import GraspCubeTensors, Franka` resolves to the
-MI355X-native tensor programs in `partmanip_amd.tasks` (no simulator inside)."""
-from partmanip_amd.tasks import Franka, GraspCubeTensors  # noqa: F401
+"""Import surface in the manner of the reference's `tasks` package: `from tasks import GraspCubeTensors, OpenDrawerTensors, Franka`
+resolve to the MI355X-native tensor programs in `partmanip_amd.tasks` (no simulator inside)."""
+from partmanip_amd.tasks import Franka, GraspCubeTensors, OpenDrawerTensors  # noqa: F401
