@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 157 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 158 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -564,7 +564,21 @@ int pm_mesh_pc_query_f32(const float* pts, const int32_t* part_of, int Q, const 
  * the number of resets to counters[2 slot + 1] and ZEROES the other pair, so a caller that starts from zeros and alternates slot =
  * 0, 1, 0, ... reads this step's two sums from its own pair without a clearing launch.
  * PM_EINVAL: a NULL pointer (jac with drive_mode 0), N < 1, nd < 3 or > 64, A not as stated, jl / jr outside [0, nl), slot not 0 / 1,
- * an unknown drive_mode, act_stride < A. */
+ * an unknown drive_mode, act_stride < A.
+ *
+ * pm_franka_control_mobile_f32 = the same launch for the mobile Franka (load_robot.py:97-101, 112-113 with `mobile`): nbase = 3
+ * virtual prismatic base joints in front of the arm, so the arm is DOFs [nbase, nd - 2) and the action row is [base 3 | arm | gripper].
+ * base_R (3, 3) row-major in device memory = quat_to_mat of the robot's default root quaternion.  Per environment that is not
+ * resetting, a = its action row, q = its DOF positions, db = 0.005 a[0:3]:
+ *   base: target[i] = q[i] + sum_j base_R[j][i] db[j], i < 3 (base_R transposed times db, summed left to right)
+ *   drive_mode 1 = 'pos' (A == nd - 1): arm k in [nbase, nd - 2): q[k] + a[k] dt 20; fingers = q + a[A - 1] dt
+ *   drive_mode 0 = 'ik' (A == 7 + nbase), b = a[nbase:]: dpose = 0.005 b[0:6], dpose[0:3] -= db; J = (jac[jl] + jac[jr]) / 2 over the
+ *   columns [nbase, nd - 2) only (the base's columns are never read); arm = q[nbase:nd-2] + J^T (J J^T + 0.05^2 I)^-1 dpose;
+ *   fingers = q + b[6] dt / 5
+ * every target clamped to [dof_lo, dof_hi] (NaN propagates); resetting environments get default_dof_pos over all nd DOFs.  The
+ * bookkeeping, the counter slots and the stream ordering are those of pm_franka_control_f32: one launch, no synchronisation, no
+ * allocation.  PM_EINVAL: nbase != 3 (nbase == 0 is pm_franka_control_f32), base_R NULL, nd < nbase + 3 or > 64, A not as stated, and
+ * everything pm_franka_control_f32 refuses. */
 int pm_grasp_cube_post_f32(const float* rigid_body, const float* dof_state, const float* root, int N, int nb, int nd, int na,
                            int obj_actor, int ltip, int rtip, const float* dof_lo, const float* dof_hi, const float* pose_lo,
                            const float* pose_hi, const float* goal, float goal_thresh, const float* obj_default_pos,
@@ -576,6 +590,12 @@ int pm_franka_control_f32(const float* actions, long act_stride, int A, const fl
                           int drive_mode, const float* rew, uint8_t* success, int64_t* progress, int explore_step,
                           int max_episode_length, int train, float* pos_act, float* epis_max_rew, int64_t* epis_max_step,
                           uint8_t* reset, uint8_t* reset_succ, int32_t* counters, int slot, void* stream);
+int pm_franka_control_mobile_f32(const float* actions, long act_stride, int A, const float* dof_state, const float* jac, int N,
+                                 int nd, int nl, int jl, int jr, const float* dof_lo, const float* dof_hi,
+                                 const float* default_dof_pos, float dt, int drive_mode, int nbase, const float* base_R,
+                                 const float* rew, uint8_t* success, int64_t* progress, int explore_step, int max_episode_length,
+                                 int train, float* pos_act, float* epis_max_rew, int64_t* epis_max_step, uint8_t* reset,
+                                 uint8_t* reset_succ, int32_t* counters, int slot, void* stream);
 
 /* ------------------------------------------------------------------ open_drawer task step (heterogeneous environments)
  * The tensor program of the reference's tasks/open_drawer.py (compute_observations, compute_reward, reset_idx) with

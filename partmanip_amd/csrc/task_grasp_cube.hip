@@ -1,7 +1,9 @@
 // The grasp_cube task step (the reference's tasks/grasp_cube.py, tasks/load_robot.py, tasks/hand_base.py:363-392, 431-441) as two
 // launches: grasp_cube_post_kernel after physics (observation rows, reward, flags, part poses) and franka_control_kernel before it
-// (joint targets by damped least squares, episode bookkeeping).  The reference spends several dozen tensor-library launches per
-// step on this (a 24-candidate gather / argmin, a batched 6 x 6 inverse, many cats), each of them launch-bound at 4096 environments.
+// (joint targets by damped least squares, episode bookkeeping; instantiated for the fixed-base Franka and for the mobile one with
+// three virtual base joints in front of the arm, pm_franka_control_f32 and pm_franka_control_mobile_f32).  The reference spends
+// several dozen tensor-library launches per step on this (a 24-candidate gather / argmin, a batched 6 x 6 inverse, many cats), each
+// of them launch-bound at 4096 environments.
 //
 // Shape.  An environment costs a few hundred flops over about 1 KB of state (14 bodies x 13 floats, 9 DOFs x 2, one root row, two
 // 6 x 9 Jacobian rows) and writes about 0.9 KB (37 + 25 + 8 + 12 x 12 floats), so the question is how a wave reads and writes that
@@ -36,8 +38,10 @@
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): grasp_cube_post_kernel 76 VGPRs, 106 SGPRs, no scratch, 6 waves /
 // SIMD; dynamic LDS eb * (13 nb + 4 nd + 37 + 12 M) floats = 1596 B per environment at nb = 14, nd = 9, M = 12: 12.8 KB with the 8
-// environments per block chosen at 4096 environments (512 blocks), never more than 48 KB.  franka_control_kernel 58 VGPRs, 58 SGPRs,
-// no scratch, 8 waves / SIMD; LDS eb * (6 (nd - 2) + 1) floats = 1.4 KB at 8 environments per block.  Times: profiles/grasp_cube_timing.json.
+// environments per block chosen at 4096 environments (512 blocks), never more than 48 KB.  franka_control_kernel<0> 58 VGPRs, 58 SGPRs,
+// no scratch, 8 waves / SIMD (as before it became a template); <3>, the mobile Franka, 62 VGPRs, 58 SGPRs, no scratch, 8 waves / SIMD; LDS
+// eb * (6 na + 1) floats, na = nd - 2 - NB arm DOFs = 1.4 KB at 8 environments per block for either robot (na = 7).  Times:
+// profiles/grasp_cube_timing.json, profiles/mobile_franka_timing.json.
 #include "common.h"
 #include "task_common.h"                                      // gc_quat_to_mat, gc_scale, gc_norm3
 
@@ -270,28 +274,37 @@ extern "C" int pm_grasp_cube_post_f32(const float* rigid_body, const float* dof_
 
 // ---------------------------------------------------------------------------------------------------- before physics
 // One wave per block, one environment per lane.  The block first averages the two link rows of the Jacobian over the arm DOFs into
-// LDS (lane i reads element i of the block's (environment, row, DOF) list: runs of nd - 2 consecutive dwords out of rows of nd),
+// LDS (lane i reads element i of the block's (environment, row, DOF) list: runs of na consecutive dwords out of rows of nd),
 // as [eb][6 * na + 1] (an odd stride where na is even, and 6 na is always even: the lanes' rows start on different banks).
+//
+// NB = the number of virtual prismatic base joints in front of the arm (load_robot.py's `self.mobile * 3`): 0 for the fixed-base
+// Franka (pm_franka_control_f32), 3 for the mobile one (pm_franka_control_mobile_f32).  The arm is then DOFs [NB, nd - 2), na =
+// nd - 2 - NB, and the loader starts each run at column NB: the base's Jacobian columns never reach LDS.  With NB = 3 the lane also
+// reads the 9 floats of base_R (the same address in every lane: scalar loads), forms db = 0.005 a[:3], the base targets q + base_R^T
+// db (sum over j left to right, as a matrix product does) and takes db off the first three entries of dpose.  One template, two
+// instantiations: the Cholesky solve and the bookkeeping exist once, and NB = 0 compiles to the arithmetic it always had.
 __device__ __forceinline__ float fc_clamp(float v, float lo, float hi) { return v != v ? v : fmaxf(fminf(v, hi), lo); }
 
+template <int NB>
 __global__ __launch_bounds__(FC_THREADS) void franka_control_kernel(
     const float* __restrict__ actions, long act_stride, int A, const float* __restrict__ dof_state, const float* __restrict__ jac,
     int N, int nd, int nl, int jl, int jr, const float* __restrict__ dof_lo, const float* __restrict__ dof_hi,
-    const float* __restrict__ default_dof_pos, float dt, int drive_mode, const float* __restrict__ rew, uint8_t* __restrict__ success,
-    int64_t* __restrict__ progress, int explore_step, int max_episode_length, int train, int eb, float* __restrict__ pos_act,
-    float* __restrict__ epis_max_rew, int64_t* __restrict__ epis_max_step, uint8_t* __restrict__ reset,
-    uint8_t* __restrict__ reset_succ, int32_t* __restrict__ counters, int slot) {
+    const float* __restrict__ default_dof_pos, float dt, int drive_mode, const float* __restrict__ base_R,
+    const float* __restrict__ rew, uint8_t* __restrict__ success, int64_t* __restrict__ progress, int explore_step,
+    int max_episode_length, int train, int eb, float* __restrict__ pos_act, float* __restrict__ epis_max_rew,
+    int64_t* __restrict__ epis_max_step, uint8_t* __restrict__ reset, uint8_t* __restrict__ reset_succ, int32_t* __restrict__ counters,
+    int slot) {
     extern __shared__ float fc_J[];
     const int tid = threadIdx.x;
     const int b0 = blockIdx.x * eb;
     const int neb = min(eb, N - b0);
-    const int na = nd - 2, JS = 6 * na + 1;
+    const int na = nd - 2 - NB, JS = 6 * na + 1;
     if (blockIdx.x == 0 && tid == 0) counters[2 * (1 - slot)] = 0, counters[2 * (1 - slot) + 1] = 0;
     if (drive_mode == 0) {
         for (int i = tid; i < neb * 6 * na; i += FC_THREADS) {
             const int e = i / (6 * na), rem = i - e * 6 * na, r = rem / na, k = rem - r * na;
             const long base = (long)(b0 + e) * nl;
-            const float l = jac[((base + jl) * 6 + r) * nd + k], rr = jac[((base + jr) * 6 + r) * nd + k];
+            const float l = jac[((base + jl) * 6 + r) * nd + NB + k], rr = jac[((base + jr) * 6 + r) * nd + NB + k];
             fc_J[e * JS + rem] = (l + rr) / 2.0f;
         }
         __syncthreads();
@@ -324,66 +337,83 @@ __global__ __launch_bounds__(FC_THREADS) void franka_control_kernel(
             progress[b] = 0;
             success[b] = 0;
             for (int d = 0; d < nd; ++d) out[d] = default_dof_pos[d];
-        } else if (drive_mode == 0) {
-            const float* J = fc_J + tid * JS;
-            float Am[6][6], x[6];
+        } else {
+            float db[3] = {0.f, 0.f, 0.f};
+            if (NB > 0) {                                       // load_robot.py:98-100
 #pragma unroll
-            for (int i = 0; i < 6; ++i)
+                for (int j = 0; j < 3; ++j) db[j] = a[j] * 0.005f;
 #pragma unroll
-                for (int j = 0; j < 6; ++j) Am[i][j] = 0.f;
-            for (int k = 0; k < na; ++k) {
-                float c[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) c[i] = J[i * na + k];
+                for (int i = 0; i < NB; ++i) {
+                    const float s = (base_R[i] * db[0] + base_R[3 + i] * db[1]) + base_R[6 + i] * db[2];
+                    out[i] = fc_clamp(qs[2 * i] + s, dof_lo[i], dof_hi[i]);
+                }
+            }
+            a += NB, qs += 2 * NB, out += NB;                   // the arm and the fingers, as load_robot.py's raw_output[..., 3:]
+            const float* lo = dof_lo + NB;
+            const float* hi = dof_hi + NB;
+            const int nf = na + 2;
+            if (drive_mode == 0) {
+                const float* J = fc_J + tid * JS;
+                float Am[6][6], x[6];
 #pragma unroll
                 for (int i = 0; i < 6; ++i)
 #pragma unroll
-                    for (int j = 0; j <= i; ++j) Am[i][j] += c[i] * c[j];
-            }
+                    for (int j = 0; j < 6; ++j) Am[i][j] = 0.f;
+                for (int k = 0; k < na; ++k) {
+                    float c[6];
 #pragma unroll
-            for (int i = 0; i < 6; ++i) Am[i][i] += 0.0025f;
-            // Cholesky A = L L^T in place (lower), then L y = dpose, L^T x = y
+                    for (int i = 0; i < 6; ++i) c[i] = J[i * na + k];
 #pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                float d = Am[j][j];
+                    for (int i = 0; i < 6; ++i)
 #pragma unroll
-                for (int k = 0; k < j; ++k) d -= Am[j][k] * Am[j][k];
-                d = sqrtf(d);
-                Am[j][j] = d;
-#pragma unroll
-                for (int i = j + 1; i < 6; ++i) {
-                    float s = Am[i][j];
-#pragma unroll
-                    for (int k = 0; k < j; ++k) s -= Am[i][k] * Am[j][k];
-                    Am[i][j] = s / d;
+                        for (int j = 0; j <= i; ++j) Am[i][j] += c[i] * c[j];
                 }
+#pragma unroll
+                for (int i = 0; i < 6; ++i) Am[i][i] += 0.0025f;
+                // Cholesky A = L L^T in place (lower), then L y = dpose, L^T x = y
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    float d = Am[j][j];
+#pragma unroll
+                    for (int k = 0; k < j; ++k) d -= Am[j][k] * Am[j][k];
+                    d = sqrtf(d);
+                    Am[j][j] = d;
+#pragma unroll
+                    for (int i = j + 1; i < 6; ++i) {
+                        float s = Am[i][j];
+#pragma unroll
+                        for (int k = 0; k < j; ++k) s -= Am[i][k] * Am[j][k];
+                        Am[i][j] = s / d;
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 6; ++i) {
+                    float s = a[i] * 0.005f;
+                    if (NB > 0 && i < 3) s -= db[i];            // load_robot.py:112-113: the base carries the hand along
+#pragma unroll
+                    for (int k = 0; k < i; ++k) s -= Am[i][k] * x[k];
+                    x[i] = s / Am[i][i];
+                }
+#pragma unroll
+                for (int i = 5; i >= 0; --i) {
+                    float s = x[i];
+#pragma unroll
+                    for (int k = i + 1; k < 6; ++k) s -= Am[k][i] * x[k];
+                    x[i] = s / Am[i][i];
+                }
+                for (int k = 0; k < na; ++k) {
+                    float u = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) u = i == 0 ? J[k] * x[0] : u + J[i * na + k] * x[i];
+                    out[k] = fc_clamp(qs[2 * k] + u, lo[k], hi[k]);
+                }
+                const float g = a[6] * dt / 5.0f;
+                for (int k = na; k < nf; ++k) out[k] = fc_clamp(qs[2 * k] + g, lo[k], hi[k]);
+            } else {
+                for (int k = 0; k < na; ++k) out[k] = fc_clamp(qs[2 * k] + a[k] * dt * 20.0f, lo[k], hi[k]);
+                const float g = a[na] * dt;
+                for (int k = na; k < nf; ++k) out[k] = fc_clamp(qs[2 * k] + g, lo[k], hi[k]);
             }
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                float s = a[i] * 0.005f;
-#pragma unroll
-                for (int k = 0; k < i; ++k) s -= Am[i][k] * x[k];
-                x[i] = s / Am[i][i];
-            }
-#pragma unroll
-            for (int i = 5; i >= 0; --i) {
-                float s = x[i];
-#pragma unroll
-                for (int k = i + 1; k < 6; ++k) s -= Am[k][i] * x[k];
-                x[i] = s / Am[i][i];
-            }
-            for (int k = 0; k < na; ++k) {
-                float u = 0.f;
-#pragma unroll
-                for (int i = 0; i < 6; ++i) u = i == 0 ? J[k] * x[0] : u + J[i * na + k] * x[i];
-                out[k] = fc_clamp(qs[2 * k] + u, dof_lo[k], dof_hi[k]);
-            }
-            const float g = a[6] * dt / 5.0f;
-            for (int k = na; k < nd; ++k) out[k] = fc_clamp(qs[2 * k] + g, dof_lo[k], dof_hi[k]);
-        } else {
-            for (int k = 0; k < na; ++k) out[k] = fc_clamp(qs[2 * k] + a[k] * dt * 20.0f, dof_lo[k], dof_hi[k]);
-            const float g = a[na] * dt;
-            for (int k = na; k < nd; ++k) out[k] = fc_clamp(qs[2 * k] + g, dof_lo[k], dof_hi[k]);
         }
     }
     const int ts = __popcll(__ballot(n_succ)), tr = __popcll(__ballot(n_reset));
@@ -393,26 +423,52 @@ __global__ __launch_bounds__(FC_THREADS) void franka_control_kernel(
     }
 }
 
+// both entry points: the checks they share, the environments per block and the launch
+template <int NB>
+static int fc_launch(const float* actions, long act_stride, int A, const float* dof_state, const float* jac, int N, int nd, int nl,
+                     int jl, int jr, const float* dof_lo, const float* dof_hi, const float* default_dof_pos, float dt, int drive_mode,
+                     const float* base_R, const float* rew, uint8_t* success, int64_t* progress, int explore_step,
+                     int max_episode_length, int train, float* pos_act, float* epis_max_rew, int64_t* epis_max_step, uint8_t* reset,
+                     uint8_t* reset_succ, int32_t* counters, int slot, void* stream) {
+    PM_REQUIRE(actions && dof_state && dof_lo && dof_hi && default_dof_pos && rew && success && progress && pos_act);
+    PM_REQUIRE(epis_max_rew && epis_max_step && reset && reset_succ && counters);
+    PM_REQUIRE(N >= 1 && nd >= NB + 3 && nd <= FC_ND_MAX && (slot == 0 || slot == 1));
+    PM_REQUIRE(drive_mode == 0 || drive_mode == 1);
+    if (drive_mode == 0) PM_REQUIRE(jac && A == 7 + NB && nl >= 1 && jl >= 0 && jl < nl && jr >= 0 && jr < nl);
+    else PM_REQUIRE(A == nd - 1);
+    PM_REQUIRE(act_stride >= A);
+    int eb = FC_THREADS;
+    while (eb > 8 && (N + eb - 1) / eb < 512) eb >>= 1;
+    const size_t lds = drive_mode == 0 ? (size_t)eb * (6 * (nd - 2 - NB) + 1) * sizeof(float) : 0;
+    const unsigned grid = (unsigned)((N + eb - 1) / eb);
+    hipLaunchKernelGGL(franka_control_kernel<NB>, dim3(grid), dim3(FC_THREADS), lds, pm_stream(stream), actions, act_stride, A,
+                       dof_state, jac, N, nd, nl, jl, jr, dof_lo, dof_hi, default_dof_pos, dt, drive_mode, base_R, rew, success,
+                       progress, explore_step, max_episode_length, train, eb, pos_act, epis_max_rew, epis_max_step, reset, reset_succ,
+                       counters, slot);
+    PM_CHECK_LAUNCH();
+    return PM_OK;
+}
+
 extern "C" int pm_franka_control_f32(const float* actions, long act_stride, int A, const float* dof_state, const float* jac, int N,
                                      int nd, int nl, int jl, int jr, const float* dof_lo, const float* dof_hi,
                                      const float* default_dof_pos, float dt, int drive_mode, const float* rew, uint8_t* success,
                                      int64_t* progress, int explore_step, int max_episode_length, int train, float* pos_act,
                                      float* epis_max_rew, int64_t* epis_max_step, uint8_t* reset, uint8_t* reset_succ,
                                      int32_t* counters, int slot, void* stream) {
-    PM_REQUIRE(actions && dof_state && dof_lo && dof_hi && default_dof_pos && rew && success && progress && pos_act);
-    PM_REQUIRE(epis_max_rew && epis_max_step && reset && reset_succ && counters);
-    PM_REQUIRE(N >= 1 && nd >= 3 && nd <= FC_ND_MAX && (slot == 0 || slot == 1));
-    PM_REQUIRE(drive_mode == 0 || drive_mode == 1);
-    if (drive_mode == 0) PM_REQUIRE(jac && A == 7 && nl >= 1 && jl >= 0 && jl < nl && jr >= 0 && jr < nl);
-    else PM_REQUIRE(A == nd - 1);
-    PM_REQUIRE(act_stride >= A);
-    int eb = FC_THREADS;
-    while (eb > 8 && (N + eb - 1) / eb < 512) eb >>= 1;
-    const size_t lds = drive_mode == 0 ? (size_t)eb * (6 * (nd - 2) + 1) * sizeof(float) : 0;
-    const unsigned grid = (unsigned)((N + eb - 1) / eb);
-    hipLaunchKernelGGL(franka_control_kernel, dim3(grid), dim3(FC_THREADS), lds, pm_stream(stream), actions, act_stride, A, dof_state,
-                       jac, N, nd, nl, jl, jr, dof_lo, dof_hi, default_dof_pos, dt, drive_mode, rew, success, progress, explore_step,
-                       max_episode_length, train, eb, pos_act, epis_max_rew, epis_max_step, reset, reset_succ, counters, slot);
-    PM_CHECK_LAUNCH();
-    return PM_OK;
+    return fc_launch<0>(actions, act_stride, A, dof_state, jac, N, nd, nl, jl, jr, dof_lo, dof_hi, default_dof_pos, dt, drive_mode,
+                        nullptr, rew, success, progress, explore_step, max_episode_length, train, pos_act, epis_max_rew,
+                        epis_max_step, reset, reset_succ, counters, slot, stream);
+}
+
+extern "C" int pm_franka_control_mobile_f32(const float* actions, long act_stride, int A, const float* dof_state, const float* jac,
+                                            int N, int nd, int nl, int jl, int jr, const float* dof_lo, const float* dof_hi,
+                                            const float* default_dof_pos, float dt, int drive_mode, int nbase, const float* base_R,
+                                            const float* rew, uint8_t* success, int64_t* progress, int explore_step,
+                                            int max_episode_length, int train, float* pos_act, float* epis_max_rew,
+                                            int64_t* epis_max_step, uint8_t* reset, uint8_t* reset_succ, int32_t* counters, int slot,
+                                            void* stream) {
+    PM_REQUIRE(nbase == 3 && base_R);
+    return fc_launch<3>(actions, act_stride, A, dof_state, jac, N, nd, nl, jl, jr, dof_lo, dof_hi, default_dof_pos, dt, drive_mode,
+                        base_R, rew, success, progress, explore_step, max_episode_length, train, pos_act, epis_max_rew,
+                        epis_max_step, reset, reset_succ, counters, slot, stream);
 }

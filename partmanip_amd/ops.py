@@ -1402,20 +1402,36 @@ DRIVE_MODES = {"ik": 0, "pos": 1}                            # drive_mode of pm_
 
 
 def franka_control(actions, dof_state, jac, jl, jr, dof_lo, dof_hi, default_dof_pos, dt, drive_mode, rew, success, progress,
-                   explore_step, max_episode_length, train, pos_act, epis_max_rew, epis_max_step, reset, reset_succ, counters, slot):
+                   explore_step, max_episode_length, train, pos_act, epis_max_rew, epis_max_step, reset, reset_succ, counters, slot,
+                   num_base_dofs=0, base_R=None):
     """Everything before physics in one launch (pm_franka_control_f32): joint targets from the actions ('ik': damped least squares
     over jac (N, nl, 6, nd), link rows jl and jr; 'pos': scaled actions; jac may be None there) and the reference's episode
     bookkeeping, in place: success (N) bool / uint8, progress and epis_max_step (N) int64, epis_max_rew (N), pos_act (N, nd), reset
-    and reset_succ (N) bool / uint8, counters (4) int32 (this call adds to pair `slot` and zeroes the other).  Returns pos_act."""
-    _req(actions, dof_state, jac, dof_lo, dof_hi, default_dof_pos, rew, success, progress, pos_act, epis_max_rew, epis_max_step,
-         reset, reset_succ, counters)
+    and reset_succ (N) bool / uint8, counters (4) int32 (this call adds to pair `slot` and zeroes the other).  Returns pos_act.
+
+    num_base_dofs = 3 with base_R (3, 3) float32 (quat_to_mat of the robot's default root quaternion) drives the mobile Franka
+    (pm_franka_control_mobile_f32, still one launch): actions are then (N, 10) for 'ik' = [base 3 | pose 6 | gripper] and (N, nd - 1)
+    for 'pos', the base targets are qpos + base_R^T (0.005 a[:3]) and the arm is DOFs [3, nd - 2)."""
+    nbase = int(num_base_dofs)
+    if nbase not in (0, 3):
+        raise ValueError(f"num_base_dofs: expected 0 (fixed base) or 3 (mobile base), got {num_base_dofs}")
+    tensors = (actions, dof_state, jac, dof_lo, dof_hi, default_dof_pos, rew, success, progress, pos_act, epis_max_rew, epis_max_step,
+               reset, reset_succ, counters, base_R)
+    if not nbase:                                             # the mobile path checks its shapes first, the device before the launch
+        _req(*tensors)
     if drive_mode not in DRIVE_MODES:
         raise ValueError(f"drive_mode: expected one of {tuple(DRIVE_MODES)}, got {drive_mode!r}")
     _f32c(dof_state, "dof_state")
-    if dof_state.dim() != 3 or dof_state.shape[2] != 2 or dof_state.shape[0] == 0 or dof_state.shape[1] < 3:
-        raise ValueError(f"dof_state: expected (N, nd >= 3, 2), got {tuple(dof_state.shape)}")
+    if nbase:
+        if base_R is None or base_R.dtype != torch.float32 or tuple(base_R.shape) != (3, 3) or not base_R.is_contiguous():
+            raise ValueError("base_R: expected a contiguous float32 (3, 3) tensor for a mobile base, got "
+                             + ("None" if base_R is None else f"{base_R.dtype} {tuple(base_R.shape)}"))
+    elif base_R is not None:
+        raise ValueError("base_R is given but num_base_dofs is 0")
+    if dof_state.dim() != 3 or dof_state.shape[2] != 2 or dof_state.shape[0] == 0 or dof_state.shape[1] < nbase + 3:
+        raise ValueError(f"dof_state: expected (N, nd >= {nbase + 3}, 2), got {tuple(dof_state.shape)}")
     N, nd = dof_state.shape[0], dof_state.shape[1]
-    A = 7 if drive_mode == "ik" else nd - 1
+    A = 7 + nbase if drive_mode == "ik" else nd - 1
     if actions.dtype != torch.float32 or actions.dim() != 2 or tuple(actions.shape) != (N, A) or actions.stride(1) != 1:
         raise ValueError(f"actions: expected a float32 ({N}, {A}) tensor with unit inner stride for drive mode {drive_mode!r}, got "
                          f"{actions.dtype} {tuple(actions.shape)}")
@@ -1447,8 +1463,19 @@ def franka_control(actions, dof_state, jac, jl, jr, dof_lo, dof_hi, default_dof_
         raise ValueError(f"slot: expected 0 or 1, got {slot}")
     dev = dof_state.device
     if any(t_ is not None and t_.device != dev for t_ in (actions, jac, dof_lo, dof_hi, default_dof_pos, rew, success, progress,
-                                                          pos_act, epis_max_rew, epis_max_step, reset, reset_succ, counters)):
+                                                          pos_act, epis_max_rew, epis_max_step, reset, reset_succ, counters, base_R)):
         raise ValueError("franka_control: all tensors must live on one device")
+    if nbase:
+        _req(*tensors)
+        with TIMER.bracket("franka_control"):
+            check(lib.pm_franka_control_mobile_f32(_ptr(actions), lda, A, _ptr(dof_state), _ptr(jac), N, nd, nl, int(jl), int(jr),
+                                                   _ptr(dof_lo), _ptr(dof_hi), _ptr(default_dof_pos), float(dt),
+                                                   DRIVE_MODES[drive_mode], nbase, _ptr(base_R), _ptr(rew), _ptr(success),
+                                                   _ptr(progress), int(explore_step), int(max_episode_length), 1 if train else 0,
+                                                   _ptr(pos_act), _ptr(epis_max_rew), _ptr(epis_max_step), _ptr(reset),
+                                                   _ptr(reset_succ), _ptr(counters), int(slot), _stream()),
+                  "pm_franka_control_mobile_f32")
+        return pos_act
     with TIMER.bracket("franka_control"):
         check(lib.pm_franka_control_f32(_ptr(actions), lda, A, _ptr(dof_state), _ptr(jac), N, nd, nl, int(jl), int(jr), _ptr(dof_lo),
                                         _ptr(dof_hi), _ptr(default_dof_pos), float(dt), DRIVE_MODES[drive_mode], _ptr(rew),

@@ -10,8 +10,13 @@ What stays with the caller is what the reference does through Isaac Gym: steppin
 environments in `reset_buf` back into it (grasp_cube.reset_idx:152-182) and handing `pos_act` to its position drive.  The buffer
 part of reset_idx (pos_act, progress_buf, success, epis_max_rew, epis_max_step) happens inside begin_step.
 
-Left out: the drive modes 'ik_abs' and 'heuristic', mobile bases (NotImplementedError naming them), the reference's "Jacobian has
-problem" exit (a host synchronisation) and extras['step_id'] (it is `progress_buf.float()`)."""
+The mobile Franka comes in through `robot=MobileFranka(robot_cfg, dt, num_envs, device)` with `num_bodies=18` (its 17 bodies + the
+cube); it is driven by pm_franka_control_mobile_f32 and its posed parts are its mesh_bodies + the cube.
+
+Left out: building a mobile base from the cfg alone (NotImplementedError naming "mobile", from Franka: a config cannot say how many
+bodies the asset has; pass robot=MobileFranka(...)), the drive modes 'ik_abs' (the reference's own code raises a shape error for more
+than one environment) and 'heuristic' (a debugging mode that ends the process): NotImplementedError naming them; the reference's
+"Jacobian has problem" exit (a host synchronisation) and extras['step_id'] (it is `progress_buf.float()`)."""
 import torch
 
 from .. import ops
@@ -32,7 +37,8 @@ def default_part_body(num_bodies):
 class GraspCubeTensors:
     """cfg: the task's dictionary (cfg/tasks/grasp_cube.yaml: robot.driveMode, explore_step, maxEpisodeLength, optionally robot.dof).
     num_bodies / num_actors / obj_actor describe the simulator's tensors (defaults: the Franka's 13 bodies + the cube, actors
-    0 = robot, 1 = object); part_body (M) and part_C (M, 3, 3) or None choose the posed parts (defaults: the reference's 12)."""
+    0 = robot, 1 = object); part_body (M) and part_C (M, 3, 3) or None choose the posed parts (defaults: the reference's 12; with a
+    robot that names its mesh_bodies, those + the last body)."""
 
     def __init__(self, num_envs, device, cfg, dt, num_bodies=14, num_actors=2, obj_actor=1, robot=None, part_body=None,
                  part_C="default", goal=(0.0, 0.0, 0.2), goal_thresh=0.025, obj_default_pos=(0.0, 0.0, 0.025)):
@@ -52,7 +58,8 @@ class GraspCubeTensors:
         self.success_pos = torch.tensor(goal, **f)
         self.obj_default_pos = torch.tensor(obj_default_pos, **f)
         if part_body is None:
-            part_body = default_part_body(self.num_bodies)
+            mesh = getattr(self.robot, "mesh_bodies", None)
+            part_body = default_part_body(self.num_bodies) if mesh is None else list(mesh) + [self.num_bodies - 1]
             if isinstance(part_C, str):
                 part_C = torch.cat([self.robot.coordinate_transform_matrix.to(device), torch.eye(3, **f).unsqueeze(0)])
         elif isinstance(part_C, str):
@@ -79,6 +86,8 @@ class GraspCubeTensors:
         self.extras["is_reached"] = self.is_reached
         self._counters = torch.zeros(4, dtype=torch.int32, device=device)
         self._slot = 1
+        nbase = getattr(self.robot, "num_base_dofs", 0)
+        self._base = dict(num_base_dofs=nbase, base_R=self.robot.base_R) if nbase else {}
 
     def begin_step(self, actions, dof_state, jacobian=None):
         """hand_base.pre_physics_step: joint targets from the actions, the episode bookkeeping on the reward and success of the last
@@ -91,7 +100,7 @@ class GraspCubeTensors:
         ops.franka_control(actions, dof_state, jacobian, r.ltip_rb_index - 1, r.rtip_rb_index - 1, r.dof_lower_limits_tensor,
                            r.dof_upper_limits_tensor, r.default_dof_pos, self.dt, r.driveMode, self.rew_buf, self.success,
                            self.progress_buf, self.explore_step, self.max_episode_length, train, self.pos_act, self.epis_max_rew,
-                           self.epis_max_step, self.reset_buf, self.reset_succ, self._counters, self._slot)
+                           self.epis_max_step, self.reset_buf, self.reset_succ, self._counters, self._slot, **self._base)
         if train:                                             # hand_base.py:373
             c = self._counters[2 * self._slot:2 * self._slot + 2]
             self.extras["succ_rate"] = c[0:1] / torch.clamp(c[1], min=1)

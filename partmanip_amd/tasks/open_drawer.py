@@ -13,9 +13,15 @@ position drive and pushing the rewritten rows of `dof_state_all` / `root` into i
 setters want (`global_indices[env_ids]`) are built by the caller from `reset_buf`: that is a host read or a nonzero(), which this
 class never does.
 
-Left out: mobile bases and the drive modes 'ik_abs' and 'heuristic' (NotImplementedError naming them, raised by Franka; the shipped
-cfg/tasks/open_drawer.yaml asks for the mobile base and is refused that way), the reference's random STREAM (see begin_step) and
-extras['step_id'] (it is `progress_buf.float()`)."""
+The shipped cfg/tasks/open_drawer.yaml asks for the mobile Franka (three virtual base joints, 12 DOFs, 17 bodies).  A config file
+cannot say how many bodies the asset has or where its tips are, so that robot comes in through `robot=`:
+
+    task = OpenDrawerTensors(num_envs, device, cfg, dt, ..., robot=MobileFranka(cfg["robot"], dt, num_envs, device))
+
+Left out: building a mobile base from the cfg alone (the cfg-only constructor raises NotImplementedError naming "mobile", from Franka;
+pass robot=MobileFranka(...)), the drive modes 'ik_abs' (the reference's own code raises a shape error for more than one environment)
+and 'heuristic' (a debugging mode that ends the process): NotImplementedError naming them; the reference's random STREAM (see
+begin_step) and extras['step_id'] (it is `progress_buf.float()`)."""
 import math
 
 import numpy as np
@@ -68,17 +74,19 @@ def _host_ints(x, name, shape):
 
 
 class OpenDrawerTensors:
-    """cfg: the task's dictionary (robot.driveMode, robot.dof, robot.root, explore_step, maxEpisodeLength, random_reset).  The robot
-    is the fixed-base Franka with the 'ik' and 'pos' drives: a cfg that asks for a mobile base (cfg/tasks/open_drawer.yaml does) or
-    for 'ik_abs' / 'heuristic' raises NotImplementedError.  robot.root defaults to the identity pose at the origin.
+    """cfg: the task's dictionary (robot.driveMode, robot.dof, robot.root, explore_step, maxEpisodeLength, random_reset).  Without
+    `robot=` the robot is the fixed-base Franka with the 'ik' and 'pos' drives: a cfg that asks for a mobile base
+    (cfg/tasks/open_drawer.yaml does) or for 'ik_abs' / 'heuristic' then raises NotImplementedError.  robot=MobileFranka(cfg["robot"],
+    dt, num_envs, device) is the mobile Franka of that yaml (num_actions 10, normal_state 53 columns); a robot with num_base_dofs > 0
+    is driven by pm_franka_control_mobile_f32 with its base_R.  robot.root defaults to the identity pose at the origin.
 
     rigid_body_mask (N, nrb + 2) and dof_state_mask (N, nd + 1): row indices into the simulator's flat rigid-body and DOF tensors
     (build_masks), checked here once on the host: every index >= 0 (and below num_rigid_bodies / num_dof_states when those totals
     are given; the tensors handed to begin_step / end_step must have at least max index + 1 rows either way), no index twice in
     dof_state_mask; ValueError otherwise.  obj_id (N) in [0, num_objs); part_bbox_init (N, 8, 3) already scaled;
     part_joint_upper_limits already multiplied by the object scale.  part_slot (M) / part_C (M, 3, 3) or None choose the posed
-    parts among an environment's nrb + 2 gathered rows (default: default_part_slot with the Franka's mesh-frame matrices, identity
-    for the link and the handle)."""
+    parts among an environment's nrb + 2 gathered rows (default: default_part_slot, or the robot's mesh_bodies + [nrb, nrb + 1]
+    where it names them, with the Franka's mesh-frame matrices, identity for the link and the handle)."""
 
     def __init__(self, num_envs, device, cfg, dt, rigid_body_mask, dof_state_mask, obj_id, part_bbox_init, part_axis_dir_init,
                  part_joint_lower_limits, part_joint_upper_limits, num_objs, num_rigid_bodies=None, num_dof_states=None,
@@ -132,7 +140,8 @@ class OpenDrawerTensors:
         self.reset_t_range, self.reset_r_range, self.suc_prop = RESET_T_RANGE, RESET_R_RANGE, float(suc_prop)
         self.train_test_flag = "train"
         if part_slot is None:
-            part_slot = default_part_slot(nrb)
+            mesh = getattr(self.robot, "mesh_bodies", None)
+            part_slot = default_part_slot(nrb) if mesh is None else list(mesh) + [nrb, nrb + 1]
             if isinstance(part_C, str):
                 part_C = torch.cat([self.robot.coordinate_transform_matrix.to(device), torch.eye(3, **f).expand(2, 3, 3)])
         elif isinstance(part_C, str):
@@ -161,6 +170,8 @@ class OpenDrawerTensors:
         self.extras["success_objnum"] = self.succ_objid_lst
         self._counters = torch.zeros(4, dtype=torch.int32, device=device)
         self._slot = 1
+        nbase = getattr(self.robot, "num_base_dofs", 0)
+        self._base = dict(num_base_dofs=nbase, base_R=self.robot.base_R) if nbase else {}
 
     def _check_state(self, rigid_body_all, dof_state_all, root, pos_act_all):
         if rigid_body_all is not None and (rigid_body_all.dim() != 2 or rigid_body_all.shape[0] < self.num_rigid_bodies):
@@ -198,7 +209,7 @@ class OpenDrawerTensors:
         ops.franka_control(actions, self.robot_dof_state, jacobian, r.ltip_rb_index - 1, r.rtip_rb_index - 1, r.dof_lower_limits_tensor,
                            r.dof_upper_limits_tensor, r.default_dof_pos, self.dt, r.driveMode, self.rew_buf, self.success,
                            self.progress_buf, self.explore_step, self.max_episode_length, train, self.pos_act, self.epis_max_rew,
-                           self.epis_max_step, self.reset_buf, self.reset_succ, self._counters, self._slot)
+                           self.epis_max_step, self.reset_buf, self.reset_succ, self._counters, self._slot, **self._base)
         self._reset_launch(self.reset_buf, dof_state_all, root, pos_act_all, u)
         if train:                                             # hand_base.py:373
             c = self._counters[2 * self._slot:2 * self._slot + 2]
