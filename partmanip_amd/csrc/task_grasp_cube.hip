@@ -41,9 +41,10 @@
 // environments per block chosen at 4096 environments (512 blocks), never more than 48 KB.  franka_control_kernel<0> 58 VGPRs, 58 SGPRs,
 // no scratch, 8 waves / SIMD (as before it became a template); <3>, the mobile Franka, 62 VGPRs, 58 SGPRs, no scratch, 8 waves / SIMD; LDS
 // eb * (6 na + 1) floats, na = nd - 2 - NB arm DOFs = 1.4 KB at 8 environments per block for either robot (na = 7).  Times:
-// profiles/grasp_cube_timing.json, profiles/mobile_franka_timing.json.
+// profiles/grasp_cube_timing.json; the mobile robot has not been timed yet (tools/time_mobile_franka.py writes
+// profiles/mobile_franka_timing.json when it is run).
 #include "common.h"
-#include "task_common.h"                                      // gc_quat_to_mat, gc_scale, gc_norm3
+#include "task_common.h"                                      // ts_*: the helpers shared with task_open_drawer.hip
 
 #define GC_THREADS 256
 #define GC_EB_MAX 32                                         // environments per block (at most; the first wave holds one per lane)
@@ -55,7 +56,7 @@
 // 6 <= c < 18, third column = first x second; the candidate of largest trace, the lowest c on ties.  o: 3 x 3 row-major.
 __device__ __forceinline__ void gc_deambiguity(const float* q, float* o) {
     float R[9];
-    gc_quat_to_mat(q, R);
+    ts_quat_to_mat(q, R);
     float best = 0.f;
     int bc = 0;
 #pragma unroll
@@ -79,11 +80,9 @@ __device__ __forceinline__ void gc_deambiguity(const float* q, float* o) {
     o[6] = a2, o[7] = b2, o[8] = a0 * b1 - a1 * b0;
 }
 
-// LDS, in floats: rb [eb][nb * 13] | dof [eb][nd * 2] | obj [eb][7] | ns [eb][W] | sc [eb][11] | R [eb][M][9] | T [eb][M][3]
-// sc = rew, extras[8], success, is_reached
-#define GC_SC 11
-__host__ __device__ static inline long gc_lds_floats(int eb, int nb, int nd, int M) {
-    return (long)eb * ((long)nb * 13 + nd * 2 + 7 + (19 + 2 * nd) + GC_SC + (long)M * 12);
+// LDS, in floats: rb [eb][nb * 13] | dof [eb][nd * 2] | obj [eb][7] | ns [eb][W] | sc [eb][TS_SC] | R [eb][M][9] | T [eb][M][3]
+static inline long gc_env_bytes(int nb, int nd, int M) {
+    return 4 * ((long)nb * 13 + nd * 2 + 7 + (19 + 2 * nd) + TS_SC + (long)M * 12);
 }
 
 __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
@@ -104,7 +103,7 @@ __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
     float* s_obj = s_dof + eb * DF;
     float* s_ns = s_obj + eb * 7;
     float* s_sc = s_ns + eb * W;
-    float* s_R = s_sc + eb * GC_SC;
+    float* s_R = s_sc + eb * TS_SC;
     float* s_T = s_R + eb * M * 9;
 
     // 1. the block's state, flat
@@ -131,25 +130,25 @@ __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
 #pragma unroll
             for (int c = 0; c < 7; ++c) {
                 tip[c] = (L[c] + Rt[c]) / 2.0f;
-                ns[c] = gc_scale(tip[c], pose_lo[c], pose_hi[c]);
+                ns[c] = ts_scale(tip[c], pose_lo[c], pose_hi[c]);
             }
-            const float gl = gc_norm3(L[0] - Rt[0], L[1] - Rt[1], L[2] - Rt[2]);
+            const float gl = ts_norm3(L[0] - Rt[0], L[1] - Rt[1], L[2] - Rt[2]);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) ns[7 + c] = gc_scale(obj[c], pose_lo[c], pose_hi[c]);
+            for (int c = 0; c < 3; ++c) ns[7 + c] = ts_scale(obj[c], pose_lo[c], pose_hi[c]);
             float o[9], h[9];
             gc_deambiguity(obj + 3, o);
 #pragma unroll
             for (int c = 0; c < 9; ++c) ns[10 + c] = o[c];
             for (int d = 0; d < nd; ++d) {
-                ns[19 + d] = gc_scale(s_dof[e * DF + 2 * d], dof_lo[d], dof_hi[d]);
+                ns[19 + d] = ts_scale(s_dof[e * DF + 2 * d], dof_lo[d], dof_hi[d]);
                 ns[19 + nd + d] = s_dof[e * DF + 2 * d + 1];
             }
             // grasp_cube.py:73-113
-            const float dist = gc_norm3(tip[0] - obj[0], tip[1] - obj[1], tip[2] - obj[2]);
+            const float dist = ts_norm3(tip[0] - obj[0], tip[1] - obj[1], tip[2] - obj[2]);
             const bool reached = dist < 0.02f;
             const float reaching = -dist;
             const float close = reached ? (0.1f - gl) : 0.1f * (gl - 0.1f);
-            gc_quat_to_mat(tip + 3, h);
+            ts_quat_to_mat(tip + 3, h);
             const float down = -h[8];
             float p1 = 0.f, p2 = 0.f;
 #pragma unroll
@@ -159,18 +158,17 @@ __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
                 p1 = r == 0 ? u1 : p1 + u1;
                 p2 = r == 0 ? u2 : p2 + u2;
             }
-            const float pmax = (p1 != p1 || p2 != p2) ? (p1 + p2) : fmaxf(p1, p2);      // torch.max: NaN if either is
-            const float rot = (down + pmax) - 3.0f;
-            const float dgoal = gc_norm3(obj[0] - goal[0], obj[1] - goal[1], obj[2] - goal[2]);
+            const float rot = (down + ts_max(p1, p2)) - 3.0f;
+            const float dgoal = ts_norm3(obj[0] - goal[0], obj[1] - goal[1], obj[2] - goal[2]);
             const float gap = 0.2f - dgoal;
             const float rgoal = reached ? (gap != gap ? gap : fmaxf(gap, 0.0f)) : 0.0f;
             const bool succ = (dgoal <= goal_thresh) && reached;
             float rw = ((reaching + 0.5f * rot) + 5.0f * close) + 20.0f * rgoal;
             rw = rw + (succ ? 3.0f : 0.0f);
-            float* sc = s_sc + e * GC_SC;
+            float* sc = s_sc + e * TS_SC;
             sc[0] = rw;
             sc[1] = reaching, sc[2] = close, sc[3] = rot, sc[4] = rgoal;
-            sc[5] = gc_norm3(obj[0] - obj_default_pos[0], obj[1] - obj_default_pos[1], obj[2] - obj_default_pos[2]);
+            sc[5] = ts_norm3(obj[0] - obj_default_pos[0], obj[1] - obj_default_pos[1], obj[2] - obj_default_pos[2]);
             sc[6] = rw, sc[7] = obj[2], sc[8] = obj[2] > 0.1f ? 1.0f : 0.0f;
             sc[9] = succ ? 1.0f : 0.0f, sc[10] = reached ? 1.0f : 0.0f;
         }
@@ -187,7 +185,7 @@ __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
                 const float* src = s_rb + e * RB + body * 13;
                 T[0] = src[0], T[1] = src[1], T[2] = src[2];
                 float Q[9];
-                gc_quat_to_mat(src + 3, Q);
+                ts_quat_to_mat(src + 3, Q);
                 if (part_C) {
                     const float* Cp = part_C + p * 9;
 #pragma unroll
@@ -224,12 +222,12 @@ __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
     if (extras)
         for (int i = tid; i < neb * 8; i += GC_THREADS) {
             const int e = i >> 3, c = i & 7;
-            extras[(long)(b0 + e) * ex_stride + c] = s_sc[e * GC_SC + 1 + c];
+            extras[(long)(b0 + e) * ex_stride + c] = s_sc[e * TS_SC + 1 + c];
         }
     if (tid < neb) {
-        if (rew) rew[b0 + tid] = s_sc[tid * GC_SC];
-        if (success) success[b0 + tid] = s_sc[tid * GC_SC + 9] != 0.0f;
-        if (is_reached) is_reached[b0 + tid] = s_sc[tid * GC_SC + 10] != 0.0f;
+        if (rew) rew[b0 + tid] = s_sc[tid * TS_SC];
+        if (success) success[b0 + tid] = s_sc[tid * TS_SC + 9] != 0.0f;
+        if (is_reached) is_reached[b0 + tid] = s_sc[tid * TS_SC + 10] != 0.0f;
     }
     if (pose_R) {
         float* g = pose_R + (long)b0 * M * 9;
@@ -258,10 +256,8 @@ extern "C" int pm_grasp_cube_post_f32(const float* rigid_body, const float* dof_
     PM_REQUIRE(!poses || (part_body && M >= 1));
     PM_REQUIRE((long)nb * 13 + nd * 2 <= 12000);
     const int Mk = poses ? M : 0;
-    // as many environments per block as LDS holds, fewer while the grid would leave most of the chip idle (same bits either way)
-    int eb = GC_EB_MAX;
-    while (eb > 1 && (gc_lds_floats(eb, nb, nd, Mk) * 4 > GC_LDS_MAX || (eb > 4 && (N + eb - 1) / eb < 512))) eb >>= 1;
-    const long lds = gc_lds_floats(eb, nb, nd, Mk) * 4;
+    const int eb = ts_envs_per_block(N, gc_env_bytes(nb, nd, Mk), GC_EB_MAX, GC_LDS_MAX);
+    const long lds = eb * gc_env_bytes(nb, nd, Mk);
     PM_REQUIRE(lds <= GC_LDS_MAX);
     const unsigned grid = (unsigned)((N + eb - 1) / eb);
     hipLaunchKernelGGL(grasp_cube_post_kernel, dim3(grid), dim3(GC_THREADS), (size_t)lds, pm_stream(stream), rigid_body, dof_state,
@@ -283,8 +279,6 @@ extern "C" int pm_grasp_cube_post_f32(const float* rigid_body, const float* dof_
 // reads the 9 floats of base_R (the same address in every lane: scalar loads), forms db = 0.005 a[:3], the base targets q + base_R^T
 // db (sum over j left to right, as a matrix product does) and takes db off the first three entries of dpose.  One template, two
 // instantiations: the Cholesky solve and the bookkeeping exist once, and NB = 0 compiles to the arithmetic it always had.
-__device__ __forceinline__ float fc_clamp(float v, float lo, float hi) { return v != v ? v : fmaxf(fminf(v, hi), lo); }
-
 template <int NB>
 __global__ __launch_bounds__(FC_THREADS) void franka_control_kernel(
     const float* __restrict__ actions, long act_stride, int A, const float* __restrict__ dof_state, const float* __restrict__ jac,
@@ -322,7 +316,7 @@ __global__ __launch_bounds__(FC_THREADS) void franka_control_kernel(
         if (train) {
             const float r = rew[b], mr = epis_max_rew[b];
             int64_t ms = r < mr ? epis_max_step[b] : prog;
-            const float nmr = (r != r || mr != mr) ? r + mr : fmaxf(r, mr);             // torch.maximum
+            const float nmr = ts_max(r, mr);                                            // torch.maximum
             rst = (prog >= ms + explore_step) || succ;
             reset_succ[b] = succ;
             epis_max_step[b] = rst ? 0 : ms;
@@ -345,7 +339,7 @@ __global__ __launch_bounds__(FC_THREADS) void franka_control_kernel(
 #pragma unroll
                 for (int i = 0; i < NB; ++i) {
                     const float s = (base_R[i] * db[0] + base_R[3 + i] * db[1]) + base_R[6 + i] * db[2];
-                    out[i] = fc_clamp(qs[2 * i] + s, dof_lo[i], dof_hi[i]);
+                    out[i] = ts_clamp(qs[2 * i] + s, dof_lo[i], dof_hi[i]);
                 }
             }
             a += NB, qs += 2 * NB, out += NB;                   // the arm and the fingers, as load_robot.py's raw_output[..., 3:]
@@ -405,14 +399,14 @@ __global__ __launch_bounds__(FC_THREADS) void franka_control_kernel(
                     float u = 0.f;
 #pragma unroll
                     for (int i = 0; i < 6; ++i) u = i == 0 ? J[k] * x[0] : u + J[i * na + k] * x[i];
-                    out[k] = fc_clamp(qs[2 * k] + u, lo[k], hi[k]);
+                    out[k] = ts_clamp(qs[2 * k] + u, lo[k], hi[k]);
                 }
                 const float g = a[6] * dt / 5.0f;
-                for (int k = na; k < nf; ++k) out[k] = fc_clamp(qs[2 * k] + g, lo[k], hi[k]);
+                for (int k = na; k < nf; ++k) out[k] = ts_clamp(qs[2 * k] + g, lo[k], hi[k]);
             } else {
-                for (int k = 0; k < na; ++k) out[k] = fc_clamp(qs[2 * k] + a[k] * dt * 20.0f, lo[k], hi[k]);
+                for (int k = 0; k < na; ++k) out[k] = ts_clamp(qs[2 * k] + a[k] * dt * 20.0f, lo[k], hi[k]);
                 const float g = a[na] * dt;
-                for (int k = na; k < nf; ++k) out[k] = fc_clamp(qs[2 * k] + g, lo[k], hi[k]);
+                for (int k = na; k < nf; ++k) out[k] = ts_clamp(qs[2 * k] + g, lo[k], hi[k]);
             }
         }
     }
@@ -438,7 +432,7 @@ static int fc_launch(const float* actions, long act_stride, int A, const float* 
     else PM_REQUIRE(A == nd - 1);
     PM_REQUIRE(act_stride >= A);
     int eb = FC_THREADS;
-    while (eb > 8 && (N + eb - 1) / eb < 512) eb >>= 1;
+    while (eb > 8 && (N + eb - 1) / eb < TS_GRID_MIN) eb >>= 1;
     const size_t lds = drive_mode == 0 ? (size_t)eb * (6 * (nd - 2 - NB) + 1) * sizeof(float) : 0;
     const unsigned grid = (unsigned)((N + eb - 1) / eb);
     hipLaunchKernelGGL(franka_control_kernel<NB>, dim3(grid), dim3(FC_THREADS), lds, pm_stream(stream), actions, act_stride, A,

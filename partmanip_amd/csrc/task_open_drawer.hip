@@ -32,16 +32,14 @@
 // eb * (13 (nrb + 2) + 2 (nd + 1) + 7 + (29 + 2 nd) + 11 + 24 + 12 M) floats = 1840 B per environment at nrb = 13, nd = 9, M = 13: 14.4 KB
 // with 8 environments per block, never more than 48 KB.  Times: profiles/open_drawer_timing.json.
 #include "common.h"
-#include "task_common.h"                                      // gc_quat_to_mat, gc_scale, gc_norm3
+#include "task_common.h"                                      // ts_*: the helpers shared with task_grasp_cube.hip
 
 #define OD_THREADS 256
 #define OD_EB_MAX 32                                         // environments per block (at most; the first wave holds one per lane)
 #define OD_LDS_MAX 49152
-#define OD_SC 11                                             // rew, extras[8], success, is_reached
 #define OD_RS_THREADS 256
 
 __device__ __forceinline__ float od_dot3(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-__device__ __forceinline__ float od_max(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }   // torch.max
 
 // Isaac Gym's quat_rotate (q = (x, y, z, w), not normalised): v (2 w^2 - 1) + 2 w (q x v) + 2 q (q . v)
 __device__ __forceinline__ void od_quat_rotate(const float* q, const float* v, float* o) {
@@ -54,10 +52,10 @@ __device__ __forceinline__ void od_quat_rotate(const float* q, const float* v, f
     o[2] = (v[2] * s + (cz * w) * 2.0f) + (q[2] * d) * 2.0f;
 }
 
-// LDS, in floats: rb [eb][(nrb + 2) * 13] | dof [eb][(nd + 1) * 2] | obj [eb][7] | ns [eb][W] | sc [eb][11] | bb [eb][24] |
+// LDS, in floats: rb [eb][(nrb + 2) * 13] | dof [eb][(nd + 1) * 2] | obj [eb][7] | ns [eb][W] | sc [eb][TS_SC] | bb [eb][24] |
 // R [eb][M][9] | T [eb][M][3]
-__host__ __device__ static inline long od_lds_floats(int eb, int ns, int nd, int M) {
-    return (long)eb * ((long)ns * 13 + (nd + 1) * 2 + 7 + (29 + 2 * nd) + OD_SC + 24 + (long)M * 12);
+static inline long od_env_bytes(int ns, int nd, int M) {
+    return 4 * ((long)ns * 13 + (nd + 1) * 2 + 7 + (29 + 2 * nd) + TS_SC + 24 + (long)M * 12);
 }
 
 __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
@@ -80,7 +78,7 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
     float* s_obj = s_dof + eb * DF;
     float* s_ns = s_obj + eb * 7;
     float* s_sc = s_ns + eb * W;
-    float* s_bb = s_sc + eb * OD_SC;
+    float* s_bb = s_sc + eb * TS_SC;
     float* s_R = s_bb + eb * 24;
     float* s_T = s_R + eb * M * 9;
     const float qnan = __builtin_nanf("");
@@ -122,12 +120,12 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
                 if (c < 7) tip[c] = v;
                 ns[c] = v;
             }
-            const float gl = gc_norm3(L[0] - Rt[0], L[1] - Rt[1], L[2] - Rt[2]);
+            const float gl = ts_norm3(L[0] - Rt[0], L[1] - Rt[1], L[2] - Rt[2]);
             const float q = s_dof[e * DF + 2 * nd];
             // open_drawer.py:258-259
             {
                 float Rm[9];
-                gc_quat_to_mat(obj + 3, Rm);
+                ts_quat_to_mat(obj + 3, Rm);
                 const float* ax = axis_dir + (long)(b0 + e) * 3;
                 const float a0 = q * ax[0], a1 = q * ax[1], a2 = q * ax[2];
 #pragma unroll
@@ -146,9 +144,9 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
                 h_short[c] = bb[9 + c] - bb[c];
                 mid[c] = (bb[c] + bb[18 + c]) / 2.0f;
             }
-            const float len_out = gc_norm3(h_out[0], h_out[1], h_out[2]);
-            const float len_long = gc_norm3(h_long[0], h_long[1], h_long[2]);
-            const float len_short = gc_norm3(h_short[0], h_short[1], h_short[2]);
+            const float len_out = ts_norm3(h_out[0], h_out[1], h_out[2]);
+            const float len_long = ts_norm3(h_long[0], h_long[1], h_long[2]);
+            const float len_short = ts_norm3(h_short[0], h_short[1], h_short[2]);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 h_out[c] = h_out[c] / len_out, h_long[c] = h_long[c] / len_long, h_short[c] = h_short[c] / len_short;
@@ -156,7 +154,7 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
             }
             ns[25] = len_out, ns[26] = len_long, ns[27] = len_short;
             for (int d = 0; d < nd; ++d) {
-                ns[28 + d] = gc_scale(s_dof[e * DF + 2 * d], dof_lo[d], dof_hi[d]);
+                ns[28 + d] = ts_scale(s_dof[e * DF + 2 * d], dof_lo[d], dof_hi[d]);
                 ns[28 + nd + d] = s_dof[e * DF + 2 * d + 1];
             }
             ns[28 + 2 * nd] = q;
@@ -164,7 +162,7 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
             float delta[3], dl[3], dr[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) delta[c] = tip[c] - mid[c], dl[c] = L[c] - mid[c], dr[c] = Rt[c] - mid[c];
-            const float dist = gc_norm3(delta[0], delta[1], delta[2]);
+            const float dist = ts_norm3(delta[0], delta[1], delta[2]);
             const bool r_out = fabsf(od_dot3(delta, h_out)) < len_out / 2.0f;
             const bool r_short = (od_dot3(dl, h_short) * od_dot3(dr, h_short)) < 0.0f;
             const bool r_long = fabsf(od_dot3(delta, h_long)) < len_long / 2.0f;
@@ -181,8 +179,8 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
             const float ngrip[3] = {-grip[0], -grip[1], -grip[2]}, nsep[3] = {-sep[0], -sep[1], -sep[2]};
             const float ndown[3] = {-down[0], -down[1], -down[2]};
             const float dot1 = od_dot3(ngrip, h_out);
-            const float dot2 = od_max(od_dot3(sep, h_short), od_dot3(nsep, h_short));
-            const float dot3 = od_max(od_dot3(down, h_long), od_dot3(ndown, h_long));
+            const float dot2 = ts_max(od_dot3(sep, h_short), od_dot3(nsep, h_short));
+            const float dot3 = ts_max(od_dot3(down, h_long), od_dot3(ndown, h_long));
             const float rot = ((dot1 + dot2) + dot3) - 3.0f;
             // open_drawer.py:207-234
             const float fr = reached ? 1.0f : 0.0f;
@@ -200,7 +198,7 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
             float rw = base + fabsf(base) * rot;
             const bool succ = grasp && (travel >= suc_prop * hi);
             rw = rw + (succ ? 2.0f : 0.0f);
-            float* sc = s_sc + e * OD_SC;
+            float* sc = s_sc + e * TS_SC;
             sc[0] = rw;
             sc[1] = open ? 1.0f : 0.0f, sc[2] = open_ng ? 1.0f : 0.0f, sc[3] = reaching, sc[4] = close, sc[5] = rot, sc[6] = jsr;
             sc[7] = rw, sc[8] = fg, sc[9] = succ ? 1.0f : 0.0f, sc[10] = fr;
@@ -218,7 +216,7 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
                 const float* src = s_rb + e * RB + slot * 13;
                 T[0] = src[0], T[1] = src[1], T[2] = src[2];
                 float Q[9];
-                gc_quat_to_mat(src + 3, Q);
+                ts_quat_to_mat(src + 3, Q);
                 if (part_C) {
                     const float* Cp = part_C + p * 9;
 #pragma unroll
@@ -248,13 +246,13 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
     if (extras)
         for (int i = tid; i < neb * 8; i += OD_THREADS) {
             const int e = i >> 3, c = i & 7;
-            extras[(long)(b0 + e) * ex_stride + c] = s_sc[e * OD_SC + 1 + c];
+            extras[(long)(b0 + e) * ex_stride + c] = s_sc[e * TS_SC + 1 + c];
         }
     if (tid < neb) {
-        const bool succ = s_sc[tid * OD_SC + 9] != 0.0f;
-        if (rew) rew[b0 + tid] = s_sc[tid * OD_SC];
+        const bool succ = s_sc[tid * TS_SC + 9] != 0.0f;
+        if (rew) rew[b0 + tid] = s_sc[tid * TS_SC];
         if (success) success[b0 + tid] = succ;
-        if (is_reached) is_reached[b0 + tid] = s_sc[tid * OD_SC + 10] != 0.0f;
+        if (is_reached) is_reached[b0 + tid] = s_sc[tid * TS_SC + 10] != 0.0f;
         if (succ_objid && succ) {
             const int o = obj_id[b0 + tid];
             if (o >= 0 && o < num_objs) succ_objid[o] = 1;
@@ -305,10 +303,8 @@ extern "C" int pm_open_drawer_post_f32(const float* rigid_body_all, long B, cons
     PM_REQUIRE(!poses || (part_slot && M >= 1));
     PM_REQUIRE((long)(nrb + 2) * 13 + (nd + 1) * 4 <= 12000);
     const int Mk = poses ? M : 0;
-    // as many environments per block as LDS holds, fewer while the grid would leave most of the chip idle (same bits either way)
-    int eb = OD_EB_MAX;
-    while (eb > 1 && (od_lds_floats(eb, nrb + 2, nd, Mk) * 4 > OD_LDS_MAX || (eb > 4 && (N + eb - 1) / eb < 512))) eb >>= 1;
-    const long lds = od_lds_floats(eb, nrb + 2, nd, Mk) * 4;
+    const int eb = ts_envs_per_block(N, od_env_bytes(nrb + 2, nd, Mk), OD_EB_MAX, OD_LDS_MAX);
+    const long lds = eb * od_env_bytes(nrb + 2, nd, Mk);
     PM_REQUIRE(lds <= OD_LDS_MAX);
     const unsigned grid = (unsigned)((N + eb - 1) / eb);
     hipLaunchKernelGGL(open_drawer_post_kernel, dim3(grid), dim3(OD_THREADS), (size_t)lds, pm_stream(stream), rigid_body_all, B,

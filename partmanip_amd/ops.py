@@ -1325,6 +1325,41 @@ def _vec(t_, name, n, dtype=torch.float32):
         raise ValueError(f"{name}: expected a contiguous {dtype} tensor of {n} elements, got {t_.dtype} {tuple(t_.shape)}")
 
 
+def _flags(t_, name, n):
+    if t_.dtype not in (torch.bool, torch.uint8) or not t_.is_contiguous() or t_.numel() != n:
+        raise ValueError(f"{name}: expected a contiguous bool / uint8 tensor of {n} elements, got {t_.dtype} {tuple(t_.shape)}")
+
+
+def _shape_f32c(t_, name, shape):
+    _f32c(t_, name)
+    if tuple(t_.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected {tuple(shape)}, got {tuple(t_.shape)}")
+
+
+def _root_dims(root, N=None):
+    """(N, na) of the simulator's root tensor (N, na, 13); with N given, the batch it must have."""
+    if root.dim() != 3 or root.shape[2] != 13 or root.shape[1] == 0 or (root.shape[0] == 0 if N is None else root.shape[0] != N):
+        raise ValueError(f"root: expected ({'N' if N is None else N}, na, 13), got {tuple(root.shape)}")
+    return root.shape[0], root.shape[1]
+
+
+def _part_poses(N, part, arg, part_C, pose_R, pose_T):
+    """The part-pose arguments of a post wrapper: the part list `part` (M) int32 (the argument called `arg`), part_C (M, 3, 3) or
+    None, pose_R (N, M, 3, 3) and pose_T (N, M, 3), either or both None.  Returns M, 0 where no pose is asked for."""
+    if pose_R is None and pose_T is None:
+        return 0
+    if part is None or part.dim() != 1 or part.numel() == 0:
+        raise ValueError(f"pose_R / pose_T need {arg} (M) int32")
+    M = part.numel()
+    _vec(part, arg, M, torch.int32)
+    if part_C is not None:
+        _shape_f32c(part_C, "part_C", (M, 3, 3))
+    for t_, name, shape in ((pose_R, "pose_R", (N, M, 3, 3)), (pose_T, "pose_T", (N, M, 3))):
+        if t_ is not None:
+            _shape_f32c(t_, name, shape)
+    return M
+
+
 def _row_view(t_, name, N, width):
     """Row stride (in elements) of a 2-D float32 output view (N, width) with unit inner stride."""
     if t_.dtype != torch.float32 or t_.dim() != 2 or tuple(t_.shape) != (N, width) or t_.stride(1) != 1:
@@ -1354,37 +1389,21 @@ def grasp_cube_post(rigid_body, dof_state, root, obj_actor, ltip, rtip, dof_lo, 
     if dof_state.dim() != 3 or dof_state.shape[0] != N or dof_state.shape[2] != 2 or dof_state.shape[1] == 0:
         raise ValueError(f"dof_state: expected ({N}, nd, 2), got {tuple(dof_state.shape)}")
     nd = dof_state.shape[1]
-    if root.dim() != 3 or root.shape[0] != N or root.shape[2] != 13 or root.shape[1] == 0:
-        raise ValueError(f"root: expected ({N}, na, 13), got {tuple(root.shape)}")
-    na = root.shape[1]
+    na = _root_dims(root, N)[1]
     if not (0 <= obj_actor < na and 0 <= ltip < nb and 0 <= rtip < nb):
         raise ValueError(f"obj_actor {obj_actor} / ltip {ltip} / rtip {rtip} outside ({na} actors, {nb} bodies)")
     for t_, name, n in ((dof_lo, "dof_lo", nd), (dof_hi, "dof_hi", nd), (pose_lo, "pose_lo", 7), (pose_hi, "pose_hi", 7),
                         (goal, "goal", 3), (obj_default_pos, "obj_default_pos", 3)):
         _vec(t_, name, n)
-    M = 0
-    if pose_R is not None or pose_T is not None:
-        if part_body is None or part_body.dim() != 1 or part_body.numel() == 0:
-            raise ValueError("pose_R / pose_T need part_body (M) int32")
-        M = part_body.numel()
-        _vec(part_body, "part_body", M, torch.int32)
-        if part_C is not None:
-            _f32c(part_C, "part_C")
-            if tuple(part_C.shape) != (M, 3, 3):
-                raise ValueError(f"part_C: expected ({M}, 3, 3), got {tuple(part_C.shape)}")
-        for t_, name, shape in ((pose_R, "pose_R", (N, M, 3, 3)), (pose_T, "pose_T", (N, M, 3))):
-            if t_ is not None:
-                _f32c(t_, name)
-                if tuple(t_.shape) != shape:
-                    raise ValueError(f"{name}: expected {shape}, got {tuple(t_.shape)}")
+    M = _part_poses(N, part_body, "part_body", part_C, pose_R, pose_T)
     lns = _row_view(normal_state, "normal_state", N, 19 + 2 * nd) if normal_state is not None else 0
     lpr = _row_view(proprio, "proprio", N, 7 + 2 * nd) if proprio is not None else 0
     lex = _row_view(extras, "extras", N, 8) if extras is not None else 0
     if rew is not None:
         _vec(rew, "rew", N)
     for t_, name in ((success, "success"), (is_reached, "is_reached")):
-        if t_ is not None and (t_.dtype not in (torch.bool, torch.uint8) or not t_.is_contiguous() or t_.numel() != N):
-            raise ValueError(f"{name}: expected a contiguous bool / uint8 tensor of {N} elements, got {t_.dtype} {tuple(t_.shape)}")
+        if t_ is not None:
+            _flags(t_, name, N)
     dev = rigid_body.device
     if any(t_ is not None and t_.device != dev for t_ in (dof_state, root, dof_lo, dof_hi, pose_lo, pose_hi, goal, obj_default_pos,
                                                           part_body, part_C, normal_state, proprio, rew, success, is_reached,
@@ -1457,43 +1476,25 @@ def franka_control(actions, dof_state, jac, jl, jr, dof_lo, dof_hi, default_dof_
     _vec(epis_max_step, "epis_max_step", N, torch.int64)
     _vec(counters, "counters", 4, torch.int32)
     for t_, name in ((success, "success"), (reset, "reset"), (reset_succ, "reset_succ")):
-        if t_.dtype not in (torch.bool, torch.uint8) or not t_.is_contiguous() or t_.numel() != N:
-            raise ValueError(f"{name}: expected a contiguous bool / uint8 tensor of {N} elements, got {t_.dtype} {tuple(t_.shape)}")
+        _flags(t_, name, N)
     if slot not in (0, 1):
         raise ValueError(f"slot: expected 0 or 1, got {slot}")
     dev = dof_state.device
     if any(t_ is not None and t_.device != dev for t_ in (actions, jac, dof_lo, dof_hi, default_dof_pos, rew, success, progress,
                                                           pos_act, epis_max_rew, epis_max_step, reset, reset_succ, counters, base_R)):
         raise ValueError("franka_control: all tensors must live on one device")
-    if nbase:
+    head = [_ptr(actions), lda, A, _ptr(dof_state), _ptr(jac), N, nd, nl, int(jl), int(jr), _ptr(dof_lo), _ptr(dof_hi),
+            _ptr(default_dof_pos), float(dt), DRIVE_MODES[drive_mode]]
+    tail = [_ptr(rew), _ptr(success), _ptr(progress), int(explore_step), int(max_episode_length), 1 if train else 0, _ptr(pos_act),
+            _ptr(epis_max_rew), _ptr(epis_max_step), _ptr(reset), _ptr(reset_succ), _ptr(counters), int(slot)]
+    entry = "pm_franka_control_f32"
+    if nbase:                                                 # the mobile entry point takes (nbase, base_R) between the two
         _req(*tensors)
-        with TIMER.bracket("franka_control"):
-            check(lib.pm_franka_control_mobile_f32(_ptr(actions), lda, A, _ptr(dof_state), _ptr(jac), N, nd, nl, int(jl), int(jr),
-                                                   _ptr(dof_lo), _ptr(dof_hi), _ptr(default_dof_pos), float(dt),
-                                                   DRIVE_MODES[drive_mode], nbase, _ptr(base_R), _ptr(rew), _ptr(success),
-                                                   _ptr(progress), int(explore_step), int(max_episode_length), 1 if train else 0,
-                                                   _ptr(pos_act), _ptr(epis_max_rew), _ptr(epis_max_step), _ptr(reset),
-                                                   _ptr(reset_succ), _ptr(counters), int(slot), _stream()),
-                  "pm_franka_control_mobile_f32")
-        return pos_act
+        head += [nbase, _ptr(base_R)]
+        entry = "pm_franka_control_mobile_f32"
     with TIMER.bracket("franka_control"):
-        check(lib.pm_franka_control_f32(_ptr(actions), lda, A, _ptr(dof_state), _ptr(jac), N, nd, nl, int(jl), int(jr), _ptr(dof_lo),
-                                        _ptr(dof_hi), _ptr(default_dof_pos), float(dt), DRIVE_MODES[drive_mode], _ptr(rew),
-                                        _ptr(success), _ptr(progress), int(explore_step), int(max_episode_length),
-                                        1 if train else 0, _ptr(pos_act), _ptr(epis_max_rew), _ptr(epis_max_step), _ptr(reset),
-                                        _ptr(reset_succ), _ptr(counters), int(slot), _stream()), "pm_franka_control_f32")
+        check(getattr(lib, entry)(*head, *tail, _stream()), entry)
     return pos_act
-
-
-def _flags(t_, name, n):
-    if t_.dtype not in (torch.bool, torch.uint8) or not t_.is_contiguous() or t_.numel() != n:
-        raise ValueError(f"{name}: expected a contiguous bool / uint8 tensor of {n} elements, got {t_.dtype} {tuple(t_.shape)}")
-
-
-def _shape_f32c(t_, name, shape):
-    _f32c(t_, name)
-    if tuple(t_.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected {tuple(shape)}, got {tuple(t_.shape)}")
 
 
 def _index_table(t_, name, N):
@@ -1518,9 +1519,7 @@ def open_drawer_post(rigid_body_all, dof_state_all, root, rigid_body_mask, dof_s
         if t_.dim() != 2 or t_.shape[1] != w or t_.shape[0] == 0:
             raise ValueError(f"{name}: expected (rows, {w}), got {tuple(t_.shape)}")
     _f32c(root, "root")
-    if root.dim() != 3 or root.shape[2] != 13 or root.shape[0] == 0 or root.shape[1] == 0:
-        raise ValueError(f"root: expected (N, na, 13), got {tuple(root.shape)}")
-    N, na = root.shape[0], root.shape[1]
+    N, na = _root_dims(root)
     B, D = rigid_body_all.shape[0], dof_state_all.shape[0]
     nrb = _index_table(rigid_body_mask, "rigid_body_mask", N) - 2
     nd = _index_table(dof_state_mask, "dof_state_mask", N) - 1
@@ -1542,17 +1541,7 @@ def open_drawer_post(rigid_body_all, dof_state_all, root, rigid_body_mask, dof_s
         _flags(succ_objid, "succ_objid", num_objs)
     if obj_id is not None:
         _vec(obj_id, "obj_id", N, torch.int32)
-    M = 0
-    if pose_R is not None or pose_T is not None:
-        if part_slot is None or part_slot.dim() != 1 or part_slot.numel() == 0:
-            raise ValueError("pose_R / pose_T need part_slot (M) int32")
-        M = part_slot.numel()
-        _vec(part_slot, "part_slot", M, torch.int32)
-        if part_C is not None:
-            _shape_f32c(part_C, "part_C", (M, 3, 3))
-        for t_, name, shape in ((pose_R, "pose_R", (N, M, 3, 3)), (pose_T, "pose_T", (N, M, 3))):
-            if t_ is not None:
-                _shape_f32c(t_, name, shape)
+    M = _part_poses(N, part_slot, "part_slot", part_C, pose_R, pose_T)
     lns = _row_view(normal_state, "normal_state", N, 29 + 2 * nd) if normal_state is not None else 0
     lex = _row_view(extras, "extras", N, 8) if extras is not None else 0
     if rew is not None:
@@ -1589,9 +1578,7 @@ def open_drawer_reset(reset, pos_act, dof_state_mask, root, dof_state_all, pos_a
     rows in dof_state_all (D, 2) and the same values in robot_dof_state (N, nd, 2) / part_dof_state (N, 2).  dof_state_mask must
     not name a row twice."""
     _f32c(root, "root")
-    if root.dim() != 3 or root.shape[2] != 13 or root.shape[0] == 0 or root.shape[1] == 0:
-        raise ValueError(f"root: expected (N, na, 13), got {tuple(root.shape)}")
-    N, na = root.shape[0], root.shape[1]
+    N, na = _root_dims(root)
     nd = _index_table(dof_state_mask, "dof_state_mask", N) - 1
     if nd < 1:
         raise ValueError(f"dof_state_mask: expected a width nd + 1 >= 2, got {nd + 1}")

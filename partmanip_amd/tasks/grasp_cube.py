@@ -20,7 +20,7 @@ than one environment) and 'heuristic' (a debugging mode that ends the process): 
 import torch
 
 from .. import ops
-from .franka import Franka
+from .base import TaskTensors, franka_parts
 
 EXTRAS_COLUMNS = ("reaching_reward", "close_reward", "rot_reward", "reaching_goal_reward", "obj_movement", "raw_reward",
                   "obj_height", "obj_up_flag")
@@ -31,10 +31,10 @@ def default_part_body(num_bodies):
     """hand_base.py:433-435: rigid_body[:, :12] with the last two entries taken from [-3] and [-1]."""
     if num_bodies < 12:
         raise ValueError(f"the default part list needs at least 12 bodies, got {num_bodies}")
-    return list(range(10)) + [num_bodies - 3, num_bodies - 1]
+    return franka_parts(num_bodies - 3) + [num_bodies - 1]
 
 
-class GraspCubeTensors:
+class GraspCubeTensors(TaskTensors):
     """cfg: the task's dictionary (cfg/tasks/grasp_cube.yaml: robot.driveMode, explore_step, maxEpisodeLength, optionally robot.dof).
     num_bodies / num_actors / obj_actor describe the simulator's tensors (defaults: the Franka's 13 bodies + the cube, actors
     0 = robot, 1 = object); part_body (M) and part_C (M, 3, 3) or None choose the posed parts (defaults: the reference's 12; with a
@@ -42,68 +42,24 @@ class GraspCubeTensors:
 
     def __init__(self, num_envs, device, cfg, dt, num_bodies=14, num_actors=2, obj_actor=1, robot=None, part_body=None,
                  part_C="default", goal=(0.0, 0.0, 0.2), goal_thresh=0.025, obj_default_pos=(0.0, 0.0, 0.025)):
-        self.num_envs, self.device, self.dt = int(num_envs), device, float(dt)
-        self.robot = robot if robot is not None else Franka(cfg.get("robot", {}), dt, num_envs, device)
+        super().__init__(num_envs, device, cfg, dt, robot)
         nd = self.robot.num_dofs
         self.num_bodies, self.num_actors, self.obj_actor = int(num_bodies), int(num_actors), int(obj_actor)
-        self.num_actions = self.robot.num_actions
         self.num_obs = {"normal_state": 19 + 2 * nd, "proprio_state": 7 + 2 * nd}
-        self.max_episode_length = int(cfg.get("maxEpisodeLength", 200))
-        self.explore_step = int(cfg.get("explore_step", 40))
-        self.train_test_flag = "train"
         self.goal_thresh = float(goal_thresh)
         f = dict(dtype=torch.float32, device=device)
         self.pose_lower_limit = torch.tensor([-RESET_RANGE, -RESET_RANGE, 0.0, -1, -1, -1, -1], **f)
         self.pose_upper_limit = torch.tensor([RESET_RANGE, RESET_RANGE, 0.4, 1, 1, 1, 1], **f)
         self.success_pos = torch.tensor(goal, **f)
         self.obj_default_pos = torch.tensor(obj_default_pos, **f)
-        if part_body is None:
-            mesh = getattr(self.robot, "mesh_bodies", None)
-            part_body = default_part_body(self.num_bodies) if mesh is None else list(mesh) + [self.num_bodies - 1]
-            if isinstance(part_C, str):
-                part_C = torch.cat([self.robot.coordinate_transform_matrix.to(device), torch.eye(3, **f).unsqueeze(0)])
-        elif isinstance(part_C, str):
-            part_C = None
-        self.part_body = torch.as_tensor(part_body, dtype=torch.int32).reshape(-1).to(device).contiguous()
-        self.part_C = None if part_C is None else torch.as_tensor(part_C, dtype=torch.float32).to(device).contiguous()
-        M = self.part_body.numel()
-        N = self.num_envs
-        self.obs_buf = {"normal_state": torch.zeros(N, self.num_obs["normal_state"], **f),
-                        "proprio_state": torch.zeros(N, self.num_obs["proprio_state"], **f)}
-        self.rew_buf = torch.zeros(N, **f)
-        self.success = torch.zeros(N, dtype=torch.bool, device=device)
-        self.is_reached = torch.zeros(N, dtype=torch.bool, device=device)
-        self.reset_buf = torch.zeros(N, dtype=torch.bool, device=device)
-        self.reset_succ = torch.zeros(N, dtype=torch.bool, device=device)
-        self.progress_buf = torch.zeros(N, dtype=torch.long, device=device)
-        self.epis_max_rew = torch.full((N,), -100.0, **f)
-        self.epis_max_step = torch.zeros(N, dtype=torch.long, device=device)
-        self.pos_act = torch.zeros(N, nd, **f)
-        self.pose_R = torch.zeros(N, M, 3, 3, **f)
-        self.pose_T = torch.zeros(N, M, 3, **f)
-        self._extras = torch.zeros(N, len(EXTRAS_COLUMNS), **f)
-        self.extras = {k: self._extras[:, i] for i, k in enumerate(EXTRAS_COLUMNS)}
-        self.extras["is_reached"] = self.is_reached
-        self._counters = torch.zeros(4, dtype=torch.int32, device=device)
-        self._slot = 1
-        nbase = getattr(self.robot, "num_base_dofs", 0)
-        self._base = dict(num_base_dofs=nbase, base_R=self.robot.base_R) if nbase else {}
+        self.part_body, self.part_C = self._parts(part_body, part_C, default_part_body, self.num_bodies, [self.num_bodies - 1])
+        self.obs_buf = {k: torch.zeros(self.num_envs, w, **f) for k, w in self.num_obs.items()}
+        self._buffers(self.part_body.numel(), EXTRAS_COLUMNS)
 
     def begin_step(self, actions, dof_state, jacobian=None):
         """hand_base.pre_physics_step: joint targets from the actions, the episode bookkeeping on the reward and success of the last
         end_step, and the buffer resets of the environments that start over.  Returns (pos_act, reset_buf)."""
-        if self.train_test_flag not in ("train", "test"):
-            raise NotImplementedError(f"train_test_flag {self.train_test_flag!r}")
-        train = self.train_test_flag == "train"
-        self._slot ^= 1
-        r = self.robot
-        ops.franka_control(actions, dof_state, jacobian, r.ltip_rb_index - 1, r.rtip_rb_index - 1, r.dof_lower_limits_tensor,
-                           r.dof_upper_limits_tensor, r.default_dof_pos, self.dt, r.driveMode, self.rew_buf, self.success,
-                           self.progress_buf, self.explore_step, self.max_episode_length, train, self.pos_act, self.epis_max_rew,
-                           self.epis_max_step, self.reset_buf, self.reset_succ, self._counters, self._slot, **self._base)
-        if train:                                             # hand_base.py:373
-            c = self._counters[2 * self._slot:2 * self._slot + 2]
-            self.extras["succ_rate"] = c[0:1] / torch.clamp(c[1], min=1)
+        self._control(actions, dof_state, jacobian)
         return self.pos_act, self.reset_buf
 
     def end_step(self, rigid_body, dof_state, root, obs_out=None):
@@ -124,7 +80,3 @@ class GraspCubeTensors:
                             success=self.success, is_reached=self.is_reached, extras=self._extras, pose_R=self.pose_R,
                             pose_T=self.pose_T)
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
-
-    def compute_scene_pose(self):
-        """(rot (N, M, 3, 3), pos (N, M, 3)) of the last end_step: hand_base.py:431-441, the input of query_tsdf / query_pc."""
-        return self.pose_R, self.pose_T

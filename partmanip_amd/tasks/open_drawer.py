@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .franka import Franka
+from .base import TaskTensors, franka_parts
 
 EXTRAS_COLUMNS = ("is_open", "is_open_notgrasp", "reaching_reward", "close_reward", "rot_reward", "joint_state_reward", "raw_reward",
                   "is_grasped")
@@ -42,7 +42,7 @@ def default_part_slot(num_rigid_body):
     an environment's gathered rows."""
     if num_rigid_body < 12:
         raise ValueError(f"the default part list needs at least 12 robot bodies, got {num_rigid_body}")
-    return list(range(10)) + [num_rigid_body - 2, num_rigid_body, num_rigid_body + 1]
+    return franka_parts(num_rigid_body - 2) + [num_rigid_body, num_rigid_body + 1]
 
 
 def build_masks(num_robot_bodies, num_robot_dofs, obj_bodies, obj_dofs, target_link, target_handle, target_dof):
@@ -73,7 +73,7 @@ def _host_ints(x, name, shape):
     return a.astype(np.int64)
 
 
-class OpenDrawerTensors:
+class OpenDrawerTensors(TaskTensors):
     """cfg: the task's dictionary (robot.driveMode, robot.dof, robot.root, explore_step, maxEpisodeLength, random_reset).  Without
     `robot=` the robot is the fixed-base Franka with the 'ik' and 'pos' drives: a cfg that asks for a mobile base
     (cfg/tasks/open_drawer.yaml does) or for 'ik_abs' / 'heuristic' then raises NotImplementedError.  robot=MobileFranka(cfg["robot"],
@@ -92,9 +92,8 @@ class OpenDrawerTensors:
                  part_joint_lower_limits, part_joint_upper_limits, num_objs, num_rigid_bodies=None, num_dof_states=None,
                  num_actors=2, robot_actor=0, obj_actor=1, robot=None, part_slot=None, part_C="default",
                  obj_default_root=OBJ_DEFAULT_ROOT, suc_prop=SUC_PROP):
-        self.num_envs, self.device, self.dt = int(num_envs), device, float(dt)
+        super().__init__(num_envs, device, cfg, dt, robot)
         N = self.num_envs
-        self.robot = robot if robot is not None else Franka(cfg.get("robot", {}), dt, num_envs, device)
         nd, nrb = self.robot.num_dofs, self.robot.num_rigid_body
         self.num_actors, self.robot_actor, self.obj_actor = int(num_actors), int(robot_actor), int(obj_actor)
         if not (0 <= self.robot_actor < self.num_actors and 0 <= self.obj_actor < self.num_actors) or self.robot_actor == self.obj_actor:
@@ -132,46 +131,17 @@ class OpenDrawerTensors:
         self.obj_default_root = const(obj_default_root, "obj_default_root", (7,))
         root = self.robot.default_root
         self.robot_default_root = const((0, 0, 0, 0, 0, 0, 1) if root is None else root.reshape(-1)[:7], "robot.root", (7,))
-        self.num_actions = self.robot.num_actions
         self.num_obs = {"normal_state": 29 + 2 * nd}
-        self.max_episode_length = int(cfg.get("maxEpisodeLength", 200))
-        self.explore_step = int(cfg.get("explore_step", 40))
         self.random_reset = bool(cfg.get("random_reset", False))
         self.reset_t_range, self.reset_r_range, self.suc_prop = RESET_T_RANGE, RESET_R_RANGE, float(suc_prop)
-        self.train_test_flag = "train"
-        if part_slot is None:
-            mesh = getattr(self.robot, "mesh_bodies", None)
-            part_slot = default_part_slot(nrb) if mesh is None else list(mesh) + [nrb, nrb + 1]
-            if isinstance(part_C, str):
-                part_C = torch.cat([self.robot.coordinate_transform_matrix.to(device), torch.eye(3, **f).expand(2, 3, 3)])
-        elif isinstance(part_C, str):
-            part_C = None
-        self.part_slot = torch.as_tensor(part_slot, dtype=torch.int32).reshape(-1).to(device).contiguous()
-        self.part_C = None if part_C is None else torch.as_tensor(part_C, dtype=torch.float32).to(device).contiguous()
-        M = self.part_slot.numel()
+        self.part_slot, self.part_C = self._parts(part_slot, part_C, default_part_slot, nrb, [nrb, nrb + 1])
         self.obs_buf = {"normal_state": torch.zeros(N, self.num_obs["normal_state"], **f)}
-        self.rew_buf = torch.zeros(N, **f)
-        b = dict(dtype=torch.bool, device=device)
-        self.success, self.is_reached = torch.zeros(N, **b), torch.zeros(N, **b)
-        self.reset_buf, self.reset_succ = torch.zeros(N, **b), torch.zeros(N, **b)
-        self.succ_objid_lst = torch.zeros(self.num_objs, **b)
-        self.progress_buf = torch.zeros(N, dtype=torch.long, device=device)
-        self.epis_max_rew = torch.full((N,), -100.0, **f)
-        self.epis_max_step = torch.zeros(N, dtype=torch.long, device=device)
-        self.pos_act = torch.zeros(N, nd, **f)
+        self._buffers(self.part_slot.numel(), EXTRAS_COLUMNS)
+        self.succ_objid_lst = torch.zeros(self.num_objs, dtype=torch.bool, device=device)
+        self.extras["success_objnum"] = self.succ_objid_lst
         self.robot_dof_state = torch.zeros(N, nd, 2, **f)
         self.part_dof_state = torch.zeros(N, 2, **f)
         self.part_bbox = torch.zeros(N, 8, 3, **f)
-        self.pose_R = torch.zeros(N, M, 3, 3, **f)
-        self.pose_T = torch.zeros(N, M, 3, **f)
-        self._extras = torch.zeros(N, len(EXTRAS_COLUMNS), **f)
-        self.extras = {k: self._extras[:, i] for i, k in enumerate(EXTRAS_COLUMNS)}
-        self.extras["is_reached"] = self.is_reached
-        self.extras["success_objnum"] = self.succ_objid_lst
-        self._counters = torch.zeros(4, dtype=torch.int32, device=device)
-        self._slot = 1
-        nbase = getattr(self.robot, "num_base_dofs", 0)
-        self._base = dict(num_base_dofs=nbase, base_R=self.robot.base_R) if nbase else {}
 
     def _check_state(self, rigid_body_all, dof_state_all, root, pos_act_all):
         if rigid_body_all is not None and (rigid_body_all.dim() != 2 or rigid_body_all.shape[0] < self.num_rigid_bodies):
@@ -200,20 +170,10 @@ class OpenDrawerTensors:
         u (N, 4) in [0, 1) drives the perturbation when cfg['random_reset'] is set (row e: translation x, y, z and yaw of environment e);
         None draws it with torch.rand.  The random STREAM is therefore not the reference's, whose number of draws depends on how many
         environments reset (a host read here); the distribution is the same.  Returns (pos_act_all, reset_buf)."""
-        if self.train_test_flag not in ("train", "test"):
-            raise NotImplementedError(f"train_test_flag {self.train_test_flag!r}")
+        self._train()                                         # a bad flag is refused before a bad argument
         self._check_state(None, dof_state_all, root, pos_act_all)
-        train = self.train_test_flag == "train"
-        self._slot ^= 1
-        r = self.robot
-        ops.franka_control(actions, self.robot_dof_state, jacobian, r.ltip_rb_index - 1, r.rtip_rb_index - 1, r.dof_lower_limits_tensor,
-                           r.dof_upper_limits_tensor, r.default_dof_pos, self.dt, r.driveMode, self.rew_buf, self.success,
-                           self.progress_buf, self.explore_step, self.max_episode_length, train, self.pos_act, self.epis_max_rew,
-                           self.epis_max_step, self.reset_buf, self.reset_succ, self._counters, self._slot, **self._base)
+        self._control(actions, self.robot_dof_state, jacobian)
         self._reset_launch(self.reset_buf, dof_state_all, root, pos_act_all, u)
-        if train:                                             # hand_base.py:373
-            c = self._counters[2 * self._slot:2 * self._slot + 2]
-            self.extras["succ_rate"] = c[0:1] / torch.clamp(c[1], min=1)
         return pos_act_all, self.reset_buf
 
     def reset(self, dof_state_all, root, pos_act_all, u=None):
@@ -243,7 +203,3 @@ class OpenDrawerTensors:
                              succ_objid=self.succ_objid_lst, robot_dof_state=self.robot_dof_state,
                              part_dof_state=self.part_dof_state, pose_R=self.pose_R, pose_T=self.pose_T)
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
-
-    def compute_scene_pose(self):
-        """(rot (N, M, 3, 3), pos (N, M, 3)) of the last end_step: the input of query_tsdf / query_pc."""
-        return self.pose_R, self.pose_T

@@ -69,8 +69,42 @@ def load_fixture(name):
         return {k: z[k] for k in z.files}
 
 
-def t(x):
-    return torch.from_numpy(np.ascontiguousarray(x))
+_FIXTURES = {}
+
+
+def load(name):
+    """A fixture, read once per session; tests copy what they change."""
+    if name not in _FIXTURES:
+        _FIXTURES[name] = load_fixture(name)
+    return _FIXTURES[name]
+
+
+def t(x, dtype=None, device=None):
+    v = torch.as_tensor(np.ascontiguousarray(x), dtype=dtype)
+    return v if device is None else v.to(device)
+
+
+def npy(x):
+    return x.detach().cpu().numpy()
+
+
+def same_bits(a, b):
+    """Equal arrays; float32 ones of one shape and dtype, compared as bit patterns (so NaN equals NaN and -0 differs from 0)."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.dtype == np.float32:
+        return a.shape == b.shape and b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    return np.array_equal(a, b)
+
+
+def within(name, key, got, want32, want64, prefix=""):
+    """max |got - out64| <= 4 e_ref, e_ref = max |out32 - out64| being what the reference's own float32 run loses against its float64
+    run; the ratio is recorded as `prefix + name: key ...`."""
+    e_ref = float(np.abs(want32.astype(np.float64) - want64).max())
+    err = float(np.abs(np.asarray(got, dtype=np.float64) - want64).max())
+    print(f"{name} {key}: e_ref = {e_ref:.3e}; max |hip - out64| = {err:.3e}" + (f" = {err / e_ref:.2f} e_ref" if e_ref > 0 else ""))
+    if e_ref > 0:
+        record_margin(f"{prefix}{name}: {key} max |hip - out64| / e_ref", err / e_ref, 4.0, e_ref=e_ref)
+    assert err <= 4 * e_ref, (name, key, err, e_ref)
 
 
 def state_dict_t(sd_np):

@@ -8,7 +8,7 @@ what the reference's own float32 run loses against its float64 run; the kernel m
 must be equal; a group with e_ref = 0 (rows that are copies of constants) must be equal.  Where a test compares states the fixtures do
 not cover against the float64 restatement, the bound is stated at the comparison.  Every margin goes through record_margin (folded into
 profiles/mobile_franka_margins.json)."""
-import os
+import functools
 
 import numpy as np
 import pytest
@@ -17,10 +17,13 @@ import torch
 from tests import grasp_cube_ref as G
 from tests import mobile_franka_ref as MF
 from tests import open_drawer_ref as OD
-from tests.helpers import GOLDEN, record_margin
+from tests import helpers
+from tests.helpers import load, npy, record_margin, same_bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+t = functools.partial(helpers.t, device=DEV)
+within = functools.partial(helpers.within, prefix="mobile_franka ")
 SENTINEL = -777.25
 EPS = float(np.finfo(np.float32).eps)
 ND, NRB, NBASE = 12, 17, 3
@@ -29,30 +32,6 @@ GROUPS = ("normal_state", "part_bbox", "rew", "pose_R", "pose_T")
 RUNS = (("ik_train", "ik", "train", False), ("ik_test_rand", "ik", "test", True), ("pos_train_rand", "pos", "train", True),
         ("pos_test", "pos", "test", False))
 FIXTURES = ["mobile_franka_ref_small", "mobile_franka_ref_70"]
-_CACHE = {}
-
-
-def load(name):
-    """A fixture, read once per session; tests copy what they change."""
-    if name not in _CACHE:
-        with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
-            _CACHE[name] = {k: z[k] for k in z.files}
-    return _CACHE[name]
-
-
-def t(x, dtype=None):
-    return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype).to(DEV)
-
-
-def npy(x):
-    return x.detach().cpu().numpy()
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.dtype == np.float32:
-        return a.shape == b.shape and b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    return np.array_equal(a, b)
 
 
 def make_robot(fx, n, drive="ik"):
@@ -112,16 +91,6 @@ def run_pre(fx, idx=None, drive="ik", mode="train", rnd=False, actions=None, jac
 
 
 PER_ENV = ("root", "pos_act", "reset", "reset_succ", "progress", "success", "epis_max_rew", "epis_max_step", "robot_dof_state", "part_dof_state")
-
-
-def within(name, key, got, want32, want64):
-    """max |got - out64| <= 4 e_ref of the group; the ratio is recorded."""
-    e_ref = float(np.abs(want32.astype(np.float64) - want64).max())
-    err = float(np.abs(np.asarray(got, dtype=np.float64) - want64).max())
-    print(f"{name} {key}: e_ref = {e_ref:.3e}; max |hip - out64| = {err:.3e}" + (f" = {err / e_ref:.2f} e_ref" if e_ref > 0 else ""))
-    if e_ref > 0:
-        record_margin(f"mobile_franka {name}: {key} max |hip - out64| / e_ref", err / e_ref, 4.0, e_ref=e_ref)
-    assert err <= 4 * e_ref, (name, key, err, e_ref)
 
 
 # ------------------------------------------------------------------------------------------- 1. the reference
@@ -279,6 +248,33 @@ def test_a_nan_stays_inside_its_environment():
     for k in PER_ENV:
         assert same_bits(got[k][others], clean[k][others]), k
     assert np.isnan(got["pos_act"][va, :NBASE]).all() and same_bits(got["pos_act"][va, NBASE:], clean["pos_act"][va, NBASE:])
+
+
+def test_sixteen_environments_per_block_give_the_bits_of_four():
+    """Every other test here runs at N <= 70, where the post kernel takes 4 environments per block and the control kernel 8.  The 70
+    fixture 118 times over (N = 8260: both take 16, the last block holds 4) must give, in environment e, the bits of environment
+    e mod 70 of the plain fixture: begin_step ('ik', train, random_reset), then end_step on the rows it rewrote."""
+    fx = load("mobile_franka_ref_70")
+    reps, B, D = 118, fx["rigid_body_all"].shape[0], fx["dof_state_all"].shape[0]
+    rep = lambda a: np.tile(a, (reps,) + (1,) * (a.ndim - 1))   # noqa: E731
+    big = dict(fx)
+    for k in ("rigid_body_all", "dof_state_all", "pos_act_all_before", "root", "obj_id", "part_bbox_init", "part_axis_dir_init", "joint_lo",
+              "joint_hi", "before_progress", "before_epis_max_rew", "before_epis_max_step", "actions", "jac", "u"):
+        big[k] = rep(fx[k])
+    for k, rows in (("rigid_body_mask", B), ("dof_state_mask", D)):     # copy j reads and writes its own rows
+        big[k] = np.concatenate([fx[k] + j * rows for j in range(reps)]).astype(np.int32)
+    res = []
+    for f in (fx, big):
+        pre, task = run_pre(f, rnd=True)
+        task.end_step(t(f["rigid_body_all"]), t(pre["dof_state_all"]), t(pre["root"]))
+        res.append((pre, post_outputs(task), npy(task.succ_objid_lst)))
+    (pre, post, flags), (bpre, bpost, bflags) = res
+    assert bpre["reset"].shape == (70 * reps,) and 0 < pre["reset"].sum() < 70
+    for k in PER_ENV + ("pos_act_all", "dof_state_all", "rew"):
+        assert same_bits(bpre[k], rep(pre[k])), k
+    for k, v in post.items():
+        assert same_bits(bpost[k], rep(v)), k
+    assert np.array_equal(bflags, flags)
 
 
 # ------------------------------------------------------------------------------------------- 3. layouts

@@ -10,14 +10,9 @@ import pytest
 import torch
 
 from tests import grasp_cube_ref as G
-from tests.helpers import GOLDEN
+from tests.helpers import GOLDEN, load
 
 FIXTURES = ["grasp_cube_ref_small", "grasp_cube_ref_64"]
-
-
-def load(name):
-    with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
-        return {k: z[k] for k in z.files}
 
 
 def generator():

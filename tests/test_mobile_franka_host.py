@@ -13,7 +13,7 @@ import torch
 import yaml
 
 from tests import mobile_franka_ref as MF
-from tests.helpers import GOLDEN, ROOT
+from tests.helpers import GOLDEN, ROOT, load
 
 FIXTURES = ["mobile_franka_ref_small", "mobile_franka_ref_70"]
 GROUPS = ("normal_state", "part_bbox", "rew", "extras", "pose_R", "pose_T")
@@ -22,11 +22,6 @@ RUNS = (("ik_train", "ik", True, False), ("ik_test_rand", "ik", False, True), ("
 MESH = [3, 4, 5, 6, 7, 8, 9, 10, 12, 13, 15]
 SHIPPED_ROOT = [0.4, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0]
 SHIPPED_DOF = [0, 0, 0, -0.2724, -0.1511, 0.2898, -2.3792, -2.8973, 2.4690, 2.3973, 0.04, 0.04]
-
-
-def load(name):
-    with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
-        return {k: z[k] for k in z.files}
 
 
 def generator():

@@ -16,17 +16,12 @@ import yaml
 
 from tests import grasp_cube_ref as G
 from tests import open_drawer_ref as OD
-from tests.helpers import GOLDEN, ROOT
+from tests.helpers import GOLDEN, ROOT, load
 
 FIXTURES = ["open_drawer_ref_small", "open_drawer_ref_70"]
 GROUPS = ("normal_state", "part_bbox", "rew", "extras", "pose_R", "pose_T")
 RUNS = (("ik_train", "ik", True, False), ("ik_test_rand", "ik", False, True), ("pos_train_rand", "pos", True, True),
         ("pos_test", "pos", False, False))
-
-
-def load(name):
-    with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
-        return {k: z[k] for k in z.files}
 
 
 def generator():
