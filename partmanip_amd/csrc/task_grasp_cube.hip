@@ -36,19 +36,24 @@
 // block it lands in: its bits are the same alone and inside any batch, and a NaN stays inside its environment.  The only
 // cross-environment values are the two int32 sums of the control kernel (one integer atomic per wave, exact in any order).
 //
+// What is shared.  The LDS layout (ts_env_floats / ts_carve), the flat copies, the root-row gather, the part poses of waves 1-3, the
+// DOF columns, the row-out loops, the flag stores and the host side of the launch (ts_post_launch) are the helpers of task_common.h,
+// shared with open_drawer_post_kernel; this file keeps the rotation choice, the per-environment chain of wave 0 and the proprio row.
+// One stage stays written out in both files: the tip average with the gripper length.  As a shared helper (average, then length,
+// then the caller's use of the average) it gives this kernel 78 VGPRs against the 76 of the loop written out (the loads of both
+// tip rows then precede every store to the row in LDS), and a stage moves only if no kernel pays a register for it.
+//
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): grasp_cube_post_kernel 76 VGPRs, 106 SGPRs, no scratch, 6 waves /
-// SIMD; dynamic LDS eb * (13 nb + 4 nd + 37 + 12 M) floats = 1596 B per environment at nb = 14, nd = 9, M = 12: 12.8 KB with the 8
+// SIMD; dynamic LDS eb * ts_env_floats(13 nb, 2 nd, 19 + 2 nd, 0, M) floats (task_common.h) = eb * (13 nb + 4 nd + 37 + 12 M) floats =
+// 1596 B per environment at nb = 14, nd = 9, M = 12: 12.8 KB with the 8
 // environments per block chosen at 4096 environments (512 blocks), never more than 48 KB.  franka_control_kernel<0> 58 VGPRs, 58 SGPRs,
 // no scratch, 8 waves / SIMD (as before it became a template); <3>, the mobile Franka, 62 VGPRs, 58 SGPRs, no scratch, 8 waves / SIMD; LDS
 // eb * (6 na + 1) floats, na = nd - 2 - NB arm DOFs = 1.4 KB at 8 environments per block for either robot (na = 7).  Times:
-// profiles/grasp_cube_timing.json; the mobile robot has not been timed yet (tools/time_mobile_franka.py writes
-// profiles/mobile_franka_timing.json when it is run).
+// profiles/grasp_cube_timing.json and, for the mobile robot, profiles/mobile_franka_timing.json (tools/time_mobile_franka.py).
 #include "common.h"
-#include "task_common.h"                                      // ts_*: the helpers shared with task_open_drawer.hip
+#include "task_common.h"                                      // ts_*: the helpers, stages and LDS layout shared with task_open_drawer.hip
 
 #define GC_THREADS 256
-#define GC_EB_MAX 32                                         // environments per block (at most; the first wave holds one per lane)
-#define GC_LDS_MAX 49152                                     // bytes of dynamic LDS a block may ask for
 #define FC_THREADS 64
 #define FC_ND_MAX 64
 
@@ -80,11 +85,6 @@ __device__ __forceinline__ void gc_deambiguity(const float* q, float* o) {
     o[6] = a2, o[7] = b2, o[8] = a0 * b1 - a1 * b0;
 }
 
-// LDS, in floats: rb [eb][nb * 13] | dof [eb][nd * 2] | obj [eb][7] | ns [eb][W] | sc [eb][TS_SC] | R [eb][M][9] | T [eb][M][3]
-static inline long gc_env_bytes(int nb, int nd, int M) {
-    return 4 * ((long)nb * 13 + nd * 2 + 7 + (19 + 2 * nd) + TS_SC + (long)M * 12);
-}
-
 __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
     const float* __restrict__ rigid_body, const float* __restrict__ dof_state, const float* __restrict__ root, int N, int nb, int nd,
     int na, int obj_actor, int ltip, int rtip, const float* __restrict__ dof_lo, const float* __restrict__ dof_hi,
@@ -98,34 +98,21 @@ __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
     const int b0 = blockIdx.x * eb;
     const int neb = min(eb, N - b0);
     const int RB = nb * 13, DF = nd * 2, W = 19 + 2 * nd;
-    float* s_rb = gc_lds;
-    float* s_dof = s_rb + (long)eb * RB;
-    float* s_obj = s_dof + eb * DF;
-    float* s_ns = s_obj + eb * 7;
-    float* s_sc = s_ns + eb * W;
-    float* s_R = s_sc + eb * TS_SC;
-    float* s_T = s_R + eb * M * 9;
+    const ts_lds sh = ts_carve(gc_lds, eb, RB, DF, W, 0, M);
 
     // 1. the block's state, flat
-    {
-        const float* g = rigid_body + (long)b0 * RB;
-        for (int i = tid; i < neb * RB; i += GC_THREADS) s_rb[i] = g[i];
-        g = dof_state + (long)b0 * DF;
-        for (int i = tid; i < neb * DF; i += GC_THREADS) s_dof[i] = g[i];
-        for (int i = tid; i < neb * 7; i += GC_THREADS) {
-            const int e = i / 7, c = i - e * 7;
-            s_obj[i] = root[((long)(b0 + e) * na + obj_actor) * 13 + c];
-        }
-    }
+    ts_copy(sh.rb, rigid_body + (long)b0 * RB, neb * RB, tid, GC_THREADS);
+    ts_copy(sh.dof, dof_state + (long)b0 * DF, neb * DF, tid, GC_THREADS);
+    ts_gather_root(sh.obj, root, b0, neb, na, obj_actor, tid, GC_THREADS);
     __syncthreads();
 
     // 2. compute
     if (tid < 64) {
         for (int e = tid; e < neb; e += 64) {
-            const float* L = s_rb + e * RB + ltip * 13;
-            const float* Rt = s_rb + e * RB + rtip * 13;
-            const float* obj = s_obj + e * 7;
-            float* ns = s_ns + e * W;
+            const float* L = sh.rb + e * RB + ltip * 13;
+            const float* Rt = sh.rb + e * RB + rtip * 13;
+            const float* obj = sh.obj + e * 7;
+            float* ns = sh.ns + e * W;
             float tip[7];
 #pragma unroll
             for (int c = 0; c < 7; ++c) {
@@ -139,10 +126,7 @@ __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
             gc_deambiguity(obj + 3, o);
 #pragma unroll
             for (int c = 0; c < 9; ++c) ns[10 + c] = o[c];
-            for (int d = 0; d < nd; ++d) {
-                ns[19 + d] = ts_scale(s_dof[e * DF + 2 * d], dof_lo[d], dof_hi[d]);
-                ns[19 + nd + d] = s_dof[e * DF + 2 * d + 1];
-            }
+            ts_dof_columns(ns, 19, sh.dof + e * DF, nd, dof_lo, dof_hi);
             // grasp_cube.py:73-113
             const float dist = ts_norm3(tip[0] - obj[0], tip[1] - obj[1], tip[2] - obj[2]);
             const bool reached = dist < 0.02f;
@@ -165,7 +149,7 @@ __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
             const bool succ = (dgoal <= goal_thresh) && reached;
             float rw = ((reaching + 0.5f * rot) + 5.0f * close) + 20.0f * rgoal;
             rw = rw + (succ ? 3.0f : 0.0f);
-            float* sc = s_sc + e * TS_SC;
+            float* sc = sh.sc + e * TS_SC;
             sc[0] = rw;
             sc[1] = reaching, sc[2] = close, sc[3] = rot, sc[4] = rgoal;
             sc[5] = ts_norm3(obj[0] - obj_default_pos[0], obj[1] - obj_default_pos[1], obj[2] - obj_default_pos[2]);
@@ -173,70 +157,23 @@ __global__ __launch_bounds__(GC_THREADS) void grasp_cube_post_kernel(
             sc[9] = succ ? 1.0f : 0.0f, sc[10] = reached ? 1.0f : 0.0f;
         }
     } else if (pose_R || pose_T) {
-        for (int w = tid - 64; w < neb * M; w += GC_THREADS - 64) {
-            const int e = w / M, p = w - e * M;
-            const int body = part_body[p];
-            float Rm[9], T[3];
-            if (body < 0 || body >= nb) {
-#pragma unroll
-                for (int c = 0; c < 9; ++c) Rm[c] = __builtin_nanf("");
-                T[0] = T[1] = T[2] = __builtin_nanf("");
-            } else {
-                const float* src = s_rb + e * RB + body * 13;
-                T[0] = src[0], T[1] = src[1], T[2] = src[2];
-                float Q[9];
-                ts_quat_to_mat(src + 3, Q);
-                if (part_C) {
-                    const float* Cp = part_C + p * 9;
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-#pragma unroll
-                        for (int j = 0; j < 3; ++j)
-                            Rm[3 * i + j] = (Q[3 * i] * Cp[j] + Q[3 * i + 1] * Cp[3 + j]) + Q[3 * i + 2] * Cp[6 + j];
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 9; ++c) Rm[c] = Q[c];
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 9; ++c) s_R[w * 9 + c] = Rm[c];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) s_T[w * 3 + c] = T[c];
-        }
+        ts_part_poses(sh.rb, RB, neb, part_body, nb, part_C, M, sh.R, sh.T, tid - 64, GC_THREADS - 64);
     }
     __syncthreads();
 
     // 3. rows out
-    if (normal_state)
-        for (int i = tid; i < neb * W; i += GC_THREADS) {
-            const int e = i / W, c = i - e * W;
-            normal_state[(long)(b0 + e) * ns_stride + c] = s_ns[i];
-        }
+    if (normal_state) ts_rows_out(normal_state, ns_stride, b0, sh.ns, W, W, neb, tid, GC_THREADS);
     if (proprio) {
         const int Wp = 7 + 2 * nd;
         for (int i = tid; i < neb * Wp; i += GC_THREADS) {
             const int e = i / Wp, c = i - e * Wp;
-            proprio[(long)(b0 + e) * pr_stride + c] = s_ns[e * W + (c < 7 ? c : c + 12)];
+            proprio[(long)(b0 + e) * pr_stride + c] = sh.ns[e * W + (c < 7 ? c : c + 12)];
         }
     }
-    if (extras)
-        for (int i = tid; i < neb * 8; i += GC_THREADS) {
-            const int e = i >> 3, c = i & 7;
-            extras[(long)(b0 + e) * ex_stride + c] = s_sc[e * TS_SC + 1 + c];
-        }
-    if (tid < neb) {
-        if (rew) rew[b0 + tid] = s_sc[tid * TS_SC];
-        if (success) success[b0 + tid] = s_sc[tid * TS_SC + 9] != 0.0f;
-        if (is_reached) is_reached[b0 + tid] = s_sc[tid * TS_SC + 10] != 0.0f;
-    }
-    if (pose_R) {
-        float* g = pose_R + (long)b0 * M * 9;
-        for (int i = tid; i < neb * M * 9; i += GC_THREADS) g[i] = s_R[i];
-    }
-    if (pose_T) {
-        float* g = pose_T + (long)b0 * M * 3;
-        for (int i = tid; i < neb * M * 3; i += GC_THREADS) g[i] = s_T[i];
-    }
+    if (extras) ts_rows_out(extras, ex_stride, b0, sh.sc + 1, TS_SC, 8, neb, tid, GC_THREADS);
+    if (tid < neb) ts_store_flags(sh.sc + tid * TS_SC, b0 + tid, rew, success, is_reached);
+    if (pose_R) ts_copy(pose_R + (long)b0 * M * 9, sh.R, neb * M * 9, tid, GC_THREADS);
+    if (pose_T) ts_copy(pose_T + (long)b0 * M * 3, sh.T, neb * M * 3, tid, GC_THREADS);
 }
 
 extern "C" int pm_grasp_cube_post_f32(const float* rigid_body, const float* dof_state, const float* root, int N, int nb, int nd,
@@ -255,15 +192,12 @@ extern "C" int pm_grasp_cube_post_f32(const float* rigid_body, const float* dof_
     const bool poses = pose_R || pose_T;
     PM_REQUIRE(!poses || (part_body && M >= 1));
     PM_REQUIRE((long)nb * 13 + nd * 2 <= 12000);
-    const int Mk = poses ? M : 0;
-    const int eb = ts_envs_per_block(N, gc_env_bytes(nb, nd, Mk), GC_EB_MAX, GC_LDS_MAX);
-    const long lds = eb * gc_env_bytes(nb, nd, Mk);
-    PM_REQUIRE(lds <= GC_LDS_MAX);
-    const unsigned grid = (unsigned)((N + eb - 1) / eb);
-    hipLaunchKernelGGL(grasp_cube_post_kernel, dim3(grid), dim3(GC_THREADS), (size_t)lds, pm_stream(stream), rigid_body, dof_state,
-                       root, N, nb, nd, na, obj_actor, ltip, rtip, dof_lo, dof_hi, pose_lo, pose_hi, goal, goal_thresh,
-                       obj_default_pos, part_body, part_C, Mk, eb, normal_state, ns_stride, proprio, pr_stride, rew, success,
-                       is_reached, extras, ex_stride, pose_R, pose_T);
+    ts_launch L;
+    PM_REQUIRE(ts_post_launch(N, nb * 13, nd * 2, 19 + 2 * nd, 0, poses, M, &L));
+    hipLaunchKernelGGL(grasp_cube_post_kernel, dim3(L.grid), dim3(GC_THREADS), L.lds, pm_stream(stream), rigid_body, dof_state, root,
+                       N, nb, nd, na, obj_actor, ltip, rtip, dof_lo, dof_hi, pose_lo, pose_hi, goal, goal_thresh, obj_default_pos,
+                       part_body, part_C, L.Mk, L.eb, normal_state, ns_stride, proprio, pr_stride, rew, success, is_reached, extras,
+                       ex_stride, pose_R, pose_T);
     PM_CHECK_LAUNCH();
     return PM_OK;
 }

@@ -27,16 +27,21 @@
 // Bounds.  A mask entry outside its tensor reads as NaN and is never dereferenced (post) or is skipped (reset); obj_id outside
 // [0, num_objs) sets no flag.  The wrapper's constructor checks the masks once on the host.
 //
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): open_drawer_post_kernel 63 VGPRs, 105 SGPRs, no scratch, 7 waves /
+// What is shared.  The LDS layout (ts_env_floats / ts_carve, the handle box in the task's own segment), the root-row gather, the flat
+// copies, the part poses of waves 1-3, the DOF columns, the row-out loops, the flag stores and the host side of the launch
+// (ts_post_launch) are the helpers of task_common.h, shared with grasp_cube_post_kernel; this file keeps the masked gather, the
+// per-environment chain of wave 0, succ_objid and part_dof_state.  The tip average stays written out in both files (see
+// task_grasp_cube.hip: as a helper it costs that kernel two registers).
+//
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): open_drawer_post_kernel 63 VGPRs, 104 SGPRs, no scratch, 7 waves /
 // SIMD; open_drawer_reset_kernel 34 VGPRs, 54 SGPRs, no scratch, 8 waves / SIMD, no LDS.  Dynamic LDS of the post kernel:
-// eb * (13 (nrb + 2) + 2 (nd + 1) + 7 + (29 + 2 nd) + 11 + 24 + 12 M) floats = 1840 B per environment at nrb = 13, nd = 9, M = 13: 14.4 KB
+// eb * ts_env_floats(13 (nrb + 2), 2 (nd + 1), 29 + 2 nd, 24, M) floats (task_common.h) = eb * (13 (nrb + 2) + 2 (nd + 1) + 7 +
+// (29 + 2 nd) + 11 + 24 + 12 M) floats = 1840 B per environment at nrb = 13, nd = 9, M = 13: 14.4 KB
 // with 8 environments per block, never more than 48 KB.  Times: profiles/open_drawer_timing.json.
 #include "common.h"
-#include "task_common.h"                                      // ts_*: the helpers shared with task_grasp_cube.hip
+#include "task_common.h"                                      // ts_*: the helpers, stages and LDS layout shared with task_grasp_cube.hip
 
 #define OD_THREADS 256
-#define OD_EB_MAX 32                                         // environments per block (at most; the first wave holds one per lane)
-#define OD_LDS_MAX 49152
 #define OD_RS_THREADS 256
 
 __device__ __forceinline__ float od_dot3(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
@@ -50,12 +55,6 @@ __device__ __forceinline__ void od_quat_rotate(const float* q, const float* v, f
     o[0] = (v[0] * s + (cx * w) * 2.0f) + (q[0] * d) * 2.0f;
     o[1] = (v[1] * s + (cy * w) * 2.0f) + (q[1] * d) * 2.0f;
     o[2] = (v[2] * s + (cz * w) * 2.0f) + (q[2] * d) * 2.0f;
-}
-
-// LDS, in floats: rb [eb][(nrb + 2) * 13] | dof [eb][(nd + 1) * 2] | obj [eb][7] | ns [eb][W] | sc [eb][TS_SC] | bb [eb][24] |
-// R [eb][M][9] | T [eb][M][3]
-static inline long od_env_bytes(int ns, int nd, int M) {
-    return 4 * ((long)ns * 13 + (nd + 1) * 2 + 7 + (29 + 2 * nd) + TS_SC + 24 + (long)M * 12);
 }
 
 __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
@@ -73,45 +72,32 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
     const int b0 = blockIdx.x * eb;
     const int neb = min(eb, N - b0);
     const int NS = nrb + 2, RB = NS * 13, DF = (nd + 1) * 2, W = 29 + 2 * nd;
-    float* s_rb = od_lds;
-    float* s_dof = s_rb + (long)eb * RB;
-    float* s_obj = s_dof + eb * DF;
-    float* s_ns = s_obj + eb * 7;
-    float* s_sc = s_ns + eb * W;
-    float* s_bb = s_sc + eb * TS_SC;
-    float* s_R = s_bb + eb * 24;
-    float* s_T = s_R + eb * M * 9;
+    const ts_lds sh = ts_carve(od_lds, eb, RB, DF, W, 24, M);        // extra: the handle box, [eb][8][3]
     const float qnan = __builtin_nanf("");
 
     // 1. the block's state, gathered
     for (int i = tid; i < neb * RB; i += OD_THREADS) {
         const int e = i / RB, rem = i - e * RB, s = rem / 13, c = rem - s * 13;
         const long row = rb_mask[(long)(b0 + e) * NS + s];
-        s_rb[i] = (row >= 0 && row < B) ? rigid_body_all[row * 13 + c] : qnan;
+        sh.rb[i] = (row >= 0 && row < B) ? rigid_body_all[row * 13 + c] : qnan;
     }
     for (int i = tid; i < neb * DF; i += OD_THREADS) {
         const int e = i / DF, rem = i - e * DF;
         const long row = dof_mask[(long)(b0 + e) * (nd + 1) + (rem >> 1)];
-        s_dof[i] = (row >= 0 && row < D) ? dof_state_all[row * 2 + (rem & 1)] : qnan;
+        sh.dof[i] = (row >= 0 && row < D) ? dof_state_all[row * 2 + (rem & 1)] : qnan;
     }
-    for (int i = tid; i < neb * 7; i += OD_THREADS) {
-        const int e = i / 7, c = i - e * 7;
-        s_obj[i] = root[((long)(b0 + e) * na + obj_actor) * 13 + c];
-    }
-    {
-        const float* g = bbox_init + (long)b0 * 24;
-        for (int i = tid; i < neb * 24; i += OD_THREADS) s_bb[i] = g[i];
-    }
+    ts_gather_root(sh.obj, root, b0, neb, na, obj_actor, tid, OD_THREADS);
+    ts_copy(sh.extra, bbox_init + (long)b0 * 24, neb * 24, tid, OD_THREADS);
     __syncthreads();
 
     // 2. compute
     if (tid < 64) {
         for (int e = tid; e < neb; e += 64) {
-            const float* L = s_rb + e * RB + ltip * 13;
-            const float* Rt = s_rb + e * RB + rtip * 13;
-            const float* obj = s_obj + e * 7;
-            float* ns = s_ns + e * W;
-            float* bb = s_bb + e * 24;
+            const float* L = sh.rb + e * RB + ltip * 13;
+            const float* Rt = sh.rb + e * RB + rtip * 13;
+            const float* obj = sh.obj + e * 7;
+            float* ns = sh.ns + e * W;
+            float* bb = sh.extra + e * 24;
             // load_robot.py:153-164
             float tip[7];
 #pragma unroll
@@ -121,7 +107,7 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
                 ns[c] = v;
             }
             const float gl = ts_norm3(L[0] - Rt[0], L[1] - Rt[1], L[2] - Rt[2]);
-            const float q = s_dof[e * DF + 2 * nd];
+            const float q = sh.dof[e * DF + 2 * nd];
             // open_drawer.py:258-259
             {
                 float Rm[9];
@@ -153,10 +139,7 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
                 ns[13 + c] = mid[c], ns[16 + c] = h_out[c], ns[19 + c] = h_short[c], ns[22 + c] = h_long[c];
             }
             ns[25] = len_out, ns[26] = len_long, ns[27] = len_short;
-            for (int d = 0; d < nd; ++d) {
-                ns[28 + d] = ts_scale(s_dof[e * DF + 2 * d], dof_lo[d], dof_hi[d]);
-                ns[28 + nd + d] = s_dof[e * DF + 2 * d + 1];
-            }
+            ts_dof_columns(ns, 28, sh.dof + e * DF, nd, dof_lo, dof_hi);
             ns[28 + 2 * nd] = q;
             // open_drawer.py:185-193
             float delta[3], dl[3], dr[3];
@@ -198,89 +181,34 @@ __global__ __launch_bounds__(OD_THREADS) void open_drawer_post_kernel(
             float rw = base + fabsf(base) * rot;
             const bool succ = grasp && (travel >= suc_prop * hi);
             rw = rw + (succ ? 2.0f : 0.0f);
-            float* sc = s_sc + e * TS_SC;
+            float* sc = sh.sc + e * TS_SC;
             sc[0] = rw;
             sc[1] = open ? 1.0f : 0.0f, sc[2] = open_ng ? 1.0f : 0.0f, sc[3] = reaching, sc[4] = close, sc[5] = rot, sc[6] = jsr;
             sc[7] = rw, sc[8] = fg, sc[9] = succ ? 1.0f : 0.0f, sc[10] = fr;
         }
     } else if (pose_R || pose_T) {
-        for (int w = tid - 64; w < neb * M; w += OD_THREADS - 64) {
-            const int e = w / M, p = w - e * M;
-            const int slot = part_slot[p];
-            float Rm[9], T[3];
-            if (slot < 0 || slot >= NS) {
-#pragma unroll
-                for (int c = 0; c < 9; ++c) Rm[c] = qnan;
-                T[0] = T[1] = T[2] = qnan;
-            } else {
-                const float* src = s_rb + e * RB + slot * 13;
-                T[0] = src[0], T[1] = src[1], T[2] = src[2];
-                float Q[9];
-                ts_quat_to_mat(src + 3, Q);
-                if (part_C) {
-                    const float* Cp = part_C + p * 9;
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-#pragma unroll
-                        for (int j = 0; j < 3; ++j)
-                            Rm[3 * i + j] = (Q[3 * i] * Cp[j] + Q[3 * i + 1] * Cp[3 + j]) + Q[3 * i + 2] * Cp[6 + j];
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 9; ++c) Rm[c] = Q[c];
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 9; ++c) s_R[w * 9 + c] = Rm[c];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) s_T[w * 3 + c] = T[c];
-        }
+        ts_part_poses(sh.rb, RB, neb, part_slot, NS, part_C, M, sh.R, sh.T, tid - 64, OD_THREADS - 64);
     }
     __syncthreads();
 
     // 3. rows out
-    if (normal_state)
-        for (int i = tid; i < neb * W; i += OD_THREADS) {
-            const int e = i / W, c = i - e * W;
-            normal_state[(long)(b0 + e) * ns_stride + c] = s_ns[i];
-        }
-    if (extras)
-        for (int i = tid; i < neb * 8; i += OD_THREADS) {
-            const int e = i >> 3, c = i & 7;
-            extras[(long)(b0 + e) * ex_stride + c] = s_sc[e * TS_SC + 1 + c];
-        }
+    if (normal_state) ts_rows_out(normal_state, ns_stride, b0, sh.ns, W, W, neb, tid, OD_THREADS);
+    if (extras) ts_rows_out(extras, ex_stride, b0, sh.sc + 1, TS_SC, 8, neb, tid, OD_THREADS);
     if (tid < neb) {
-        const bool succ = s_sc[tid * TS_SC + 9] != 0.0f;
-        if (rew) rew[b0 + tid] = s_sc[tid * TS_SC];
-        if (success) success[b0 + tid] = succ;
-        if (is_reached) is_reached[b0 + tid] = s_sc[tid * TS_SC + 10] != 0.0f;
+        const bool succ = ts_store_flags(sh.sc + tid * TS_SC, b0 + tid, rew, success, is_reached);
         if (succ_objid && succ) {
             const int o = obj_id[b0 + tid];
             if (o >= 0 && o < num_objs) succ_objid[o] = 1;
         }
         if (part_dof_state) {
-            part_dof_state[(long)(b0 + tid) * 2] = s_dof[tid * DF + 2 * nd];
-            part_dof_state[(long)(b0 + tid) * 2 + 1] = s_dof[tid * DF + 2 * nd + 1];
+            part_dof_state[(long)(b0 + tid) * 2] = sh.dof[tid * DF + 2 * nd];
+            part_dof_state[(long)(b0 + tid) * 2 + 1] = sh.dof[tid * DF + 2 * nd + 1];
         }
     }
-    if (part_bbox) {
-        float* g = part_bbox + (long)b0 * 24;
-        for (int i = tid; i < neb * 24; i += OD_THREADS) g[i] = s_bb[i];
-    }
-    if (robot_dof_state) {
-        float* g = robot_dof_state + (long)b0 * nd * 2;
-        for (int i = tid; i < neb * nd * 2; i += OD_THREADS) {
-            const int e = i / (nd * 2), c = i - e * nd * 2;
-            g[i] = s_dof[e * DF + c];
-        }
-    }
-    if (pose_R) {
-        float* g = pose_R + (long)b0 * M * 9;
-        for (int i = tid; i < neb * M * 9; i += OD_THREADS) g[i] = s_R[i];
-    }
-    if (pose_T) {
-        float* g = pose_T + (long)b0 * M * 3;
-        for (int i = tid; i < neb * M * 3; i += OD_THREADS) g[i] = s_T[i];
-    }
+    if (part_bbox) ts_copy(part_bbox + (long)b0 * 24, sh.extra, neb * 24, tid, OD_THREADS);
+    if (robot_dof_state) ts_rows_out(robot_dof_state, nd * 2, b0, sh.dof, DF, nd * 2, neb, tid, OD_THREADS);
+    if (pose_R) ts_copy(pose_R + (long)b0 * M * 9, sh.R, neb * M * 9, tid, OD_THREADS);
+    if (pose_T) ts_copy(pose_T + (long)b0 * M * 3, sh.T, neb * M * 3, tid, OD_THREADS);
 }
 
 extern "C" int pm_open_drawer_post_f32(const float* rigid_body_all, long B, const float* dof_state_all, long D, const float* root, int N,
@@ -302,14 +230,11 @@ extern "C" int pm_open_drawer_post_f32(const float* rigid_body_all, long B, cons
     const bool poses = pose_R || pose_T;
     PM_REQUIRE(!poses || (part_slot && M >= 1));
     PM_REQUIRE((long)(nrb + 2) * 13 + (nd + 1) * 4 <= 12000);
-    const int Mk = poses ? M : 0;
-    const int eb = ts_envs_per_block(N, od_env_bytes(nrb + 2, nd, Mk), OD_EB_MAX, OD_LDS_MAX);
-    const long lds = eb * od_env_bytes(nrb + 2, nd, Mk);
-    PM_REQUIRE(lds <= OD_LDS_MAX);
-    const unsigned grid = (unsigned)((N + eb - 1) / eb);
-    hipLaunchKernelGGL(open_drawer_post_kernel, dim3(grid), dim3(OD_THREADS), (size_t)lds, pm_stream(stream), rigid_body_all, B,
+    ts_launch L;
+    PM_REQUIRE(ts_post_launch(N, (nrb + 2) * 13, (nd + 1) * 2, 29 + 2 * nd, 24, poses, M, &L));
+    hipLaunchKernelGGL(open_drawer_post_kernel, dim3(L.grid), dim3(OD_THREADS), L.lds, pm_stream(stream), rigid_body_all, B,
                        dof_state_all, D, root, N, nrb, nd, na, obj_actor, ltip, rtip, rigid_body_mask, dof_state_mask, obj_id, num_objs,
-                       part_bbox_init, part_axis_dir_init, joint_lo, joint_hi, dof_lo, dof_hi, suc_prop, part_slot, part_C, Mk, eb,
+                       part_bbox_init, part_axis_dir_init, joint_lo, joint_hi, dof_lo, dof_hi, suc_prop, part_slot, part_C, L.Mk, L.eb,
                        normal_state, ns_stride, rew, success, is_reached, part_bbox, extras, ex_stride, succ_objid, robot_dof_state,
                        part_dof_state, pose_R, pose_T);
     PM_CHECK_LAUNCH();

@@ -96,6 +96,50 @@ def same_bits(a, b):
     return np.array_equal(a, b)
 
 
+def open_drawer_post_op(fx, task, reps, part_slot, part_C):
+    """ops.open_drawer_post on a fixture's state `reps` times over (copy j reads its own rows of the flat tensors) with a caller's part
+    list, into fresh buffers; every output as numpy.  task: an OpenDrawerTensors over the fixture, for its robot and constants."""
+    from partmanip_amd import ops
+    dev, r = task.device, task.robot
+    B, D = fx["rigid_body_all"].shape[0], fx["dof_state_all"].shape[0]
+    N, nd, M = task.num_envs * reps, r.num_dofs, part_slot.numel()
+    flat = lambda a: t(np.tile(a, (reps,) + (1,) * (a.ndim - 1)), device=dev)              # noqa: E731
+    rep = lambda x: x.repeat((reps,) + (1,) * (x.dim() - 1))                                 # noqa: E731
+    table = lambda m, rows: torch.cat([m + j * rows for j in range(reps)])                   # noqa: E731
+    f = lambda *shape: torch.full(shape, -777.25, device=dev)                                # noqa: E731
+    b = lambda n: torch.zeros(n, dtype=torch.bool, device=dev)                               # noqa: E731
+    out = dict(normal_state=f(N, 29 + 2 * nd), rew=f(N), extras=f(N, 8), part_bbox=f(N, 8, 3), robot_dof_state=f(N, nd, 2),
+               part_dof_state=f(N, 2), pose_R=f(N, M, 3, 3), pose_T=f(N, M, 3), success=b(N), is_reached=b(N), succ_objid=b(task.num_objs))
+    ops.open_drawer_post(flat(fx["rigid_body_all"]), flat(fx["dof_state_all"]), flat(fx["root"]), table(task.rigid_body_mask, B),
+                         table(task.dof_state_mask, D), task.obj_actor, r.ltip_rb_index, r.rtip_rb_index, rep(task.part_bbox_init),
+                         rep(task.part_axis_dir_init), rep(task.part_joint_lower_limits), rep(task.part_joint_upper_limits),
+                         r.dof_lower_limits_tensor, r.dof_upper_limits_tensor, task.suc_prop, obj_id=rep(task.obj_id), part_slot=part_slot,
+                         part_C=part_C, **out)
+    return {k: npy(v) for k, v in out.items()}
+
+
+def lds_cap_check(fx, task, M0):
+    """The 70-environment fixture 59 times over (N = 4130: 517 blocks at 8 environments per block, so the grid rule cuts no further)
+    with the task's part list repeated to M = 60 parts, where 16 environments per block no longer fit the 48 KB of LDS and 8 do: the
+    first 70 environments and the last 4 must give the bits of the untiled run with the default list (4 per block), pose entry k those
+    of entry k mod M0."""
+    reps, M = 59, 60
+    base = open_drawer_post_op(fx, task, 1, task.part_slot, task.part_C)
+    k5 = -(-M // M0)
+    got = open_drawer_post_op(fx, task, reps, task.part_slot.repeat(k5)[:M].contiguous(), task.part_C.repeat(k5, 1, 1)[:M].contiguous())
+    N = 70 * reps
+    assert task.part_slot.numel() == M0 and got["pose_R"].shape == (N, M, 3, 3) and 0 < base["is_reached"].sum() < 70
+    assert np.array_equal(got["succ_objid"], base["succ_objid"]) and base["succ_objid"].any()
+    for lo, hi in ((0, 70), (N - 4, N)):
+        for k, v in base.items():
+            if k == "succ_objid":
+                continue
+            want = v[lo % 70:lo % 70 + hi - lo]
+            if k in ("pose_R", "pose_T"):
+                want = np.tile(want, (1, k5) + (1,) * (want.ndim - 2))[:, :M]
+            assert same_bits(got[k][lo:hi], want), (k, lo)
+
+
 def within(name, key, got, want32, want64, prefix=""):
     """max |got - out64| <= 4 e_ref, e_ref = max |out32 - out64| being what the reference's own float32 run loses against its float64
     run; the ratio is recorded as `prefix + name: key ...`."""

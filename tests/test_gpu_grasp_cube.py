@@ -244,6 +244,63 @@ def test_sixteen_environments_per_block_give_the_bits_of_four():
             assert same_bits(v, full[k][lo:hi]), (k, lo)
 
 
+POST_KEYS = ("normal_state", "proprio", "rew", "extras", "success", "is_reached", "pose_R", "pose_T")
+
+
+def post_op(st, task, reps, part_body, part_C):
+    """ops.grasp_cube_post on a state tiled `reps` times with a caller's part list, into fresh buffers; every output as numpy."""
+    from partmanip_amd import ops
+    N, nd, M, r = st["rigid_body"].shape[0] * reps, st["dof_state"].shape[1], part_body.numel(), task.robot
+    rep = lambda a: t(np.tile(a, (reps,) + (1,) * (a.ndim - 1)))   # noqa: E731
+    f = lambda *shape: torch.full(shape, SENTINEL, device=DEV)     # noqa: E731
+    out = dict(normal_state=f(N, 19 + 2 * nd), proprio=f(N, 7 + 2 * nd), rew=f(N), extras=f(N, 8), pose_R=f(N, M, 3, 3), pose_T=f(N, M, 3),
+               success=torch.zeros(N, dtype=torch.bool, device=DEV), is_reached=torch.zeros(N, dtype=torch.bool, device=DEV))
+    ops.grasp_cube_post(rep(st["rigid_body"]), rep(st["dof_state"]), rep(st["root"]), 1, st["ltip"], st["rtip"], r.dof_lower_limits_tensor,
+                        r.dof_upper_limits_tensor, task.pose_lower_limit, task.pose_upper_limit, task.success_pos, 0.025,
+                        task.obj_default_pos, part_body=part_body, part_C=part_C, **out)
+    return {k: npy(out[k]) for k in POST_KEYS}
+
+
+def test_eight_environments_per_block_set_by_the_lds_cap_give_the_bits_of_four():
+    """No other test reaches a block size that the 48 KB of LDS force: with the default part list five times over (M = 60) an
+    environment costs 1020 + 48 * 60 = 3900 B, so 16 per block do not fit and 8 do, and at N = 4130 (a 70-environment state 59 times
+    over) the grid is 517 blocks, so the grid rule cuts no further.  The first 70 environments and the last 4 give the bits of the
+    untiled run with the default list (4 per block), pose entry k those of entry k mod 12."""
+    nb, nd, reps = 14, 9, 59
+    st = make_state(70, nb, nd, 7700)
+    base, task = run_slice(st, 0, 70, nb, nd, 12)
+    got = post_op(st, task, reps, task.part_body.repeat(5), task.part_C.repeat(5, 1, 1))
+    N = 70 * reps
+    assert got["pose_R"].shape == (N, 60, 3, 3) and 0 < base["is_reached"].sum() < 70
+    for lo, hi in ((0, 70), (N - 4, N)):
+        for k in POST_KEYS:
+            want = base[k][lo % 70:lo % 70 + hi - lo]
+            if k in ("pose_R", "pose_T"):
+                want = np.tile(want, (1, 5) + (1,) * (want.ndim - 2))
+            assert same_bits(got[k][lo:hi], want), (k, lo)
+
+
+def test_a_part_index_outside_the_bodies_gives_nan_rows_and_touches_nothing_else():
+    """part_body entries -1 and nb between valid ones: those parts' pose rows are NaN in every environment (the kernel never forms
+    their address), every other row and every other output has the bits of the run without them."""
+    N, nb, nd = 5, 14, 9
+    st = make_state(N, nb, nd, 7800)
+    task = build_task(st, 0, N, nb, nd, 12)
+    eye = torch.eye(3, device=DEV)[None]
+    good = post_op(st, task, 1, task.part_body, task.part_C)
+    bad_at, body = (3, 8), task.part_body.tolist()
+    keep = [k for k in range(14) if k not in bad_at]
+    body.insert(3, -1), body.insert(8, nb)
+    part_C = torch.cat([task.part_C[:3], eye, task.part_C[3:7], eye, task.part_C[7:]])
+    got = post_op(st, task, 1, torch.tensor(body, dtype=torch.int32, device=DEV), part_C.contiguous())
+    assert [body[k] for k in keep] == task.part_body.tolist() and not np.isnan(good["pose_R"]).any()
+    for k in ("pose_R", "pose_T"):
+        assert np.isnan(got[k][:, bad_at]).all(), k
+        assert same_bits(got[k][:, keep], good[k]), k
+    for k in POST_KEYS[:6]:
+        assert same_bits(got[k], good[k]), k
+
+
 @pytest.mark.parametrize("off", [1, 2, 3])
 def test_column_views_at_every_row_alignment_leave_everything_else_alone(off):
     from partmanip_amd import ops

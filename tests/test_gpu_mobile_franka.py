@@ -277,6 +277,13 @@ def test_sixteen_environments_per_block_give_the_bits_of_four():
     assert np.array_equal(bflags, flags)
 
 
+def test_eight_environments_per_block_set_by_the_lds_cap_give_the_bits_of_four():
+    """helpers.lds_cap_check: at M = 60 an environment costs 4352 B (nrb = 17, nd = 12), so 8 per block are what the 48 KB hold; the test
+    above reaches 16 through the grid rule alone."""
+    fx = load("mobile_franka_ref_70")
+    helpers.lds_cap_check(fx, make_task(fx), 13)
+
+
 # ------------------------------------------------------------------------------------------- 3. layouts
 @pytest.mark.parametrize("name,drive", [("mobile_franka_ref_70", "ik"), ("mobile_franka_ref_70", "pos"), ("mobile_franka_ref_small", "ik")])
 def test_actions_as_a_column_view_of_a_wider_buffer(name, drive):

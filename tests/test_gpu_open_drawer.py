@@ -213,6 +213,35 @@ def test_a_nan_stays_inside_its_environment():
         assert np.array_equal(npy(task.succ_objid_lst), fx["out64_succ_objid"])
 
 
+def test_eight_environments_per_block_set_by_the_lds_cap_give_the_bits_of_four():
+    """helpers.lds_cap_check: at M = 60 an environment costs 4096 B (nrb = 13, nd = 9), so 8 per block are what the 48 KB hold; no other
+    test here reaches a block size that the cap forces."""
+    fx = load("open_drawer_ref_70")
+    helpers.lds_cap_check(fx, make_task(fx), 13)
+
+
+def test_a_part_slot_outside_the_gathered_rows_gives_nan_rows_and_touches_nothing_else():
+    """part_slot entries -1 and nrb + 2 between valid ones: those parts' pose rows are NaN in every environment (the kernel never forms
+    their address), every other row and every other output has the bits of the run without them."""
+    fx = load("open_drawer_ref_small")
+    task = make_task(fx)
+    nrb = task.robot.num_rigid_body
+    eye = torch.eye(3, device=DEV)[None]
+    good = helpers.open_drawer_post_op(fx, task, 1, task.part_slot, task.part_C)
+    bad_at, slot = (3, 8), task.part_slot.tolist()
+    keep = [k for k in range(15) if k not in bad_at]
+    slot.insert(3, -1), slot.insert(8, nrb + 2)
+    part_C = torch.cat([task.part_C[:3], eye, task.part_C[3:7], eye, task.part_C[7:]]).contiguous()
+    got = helpers.open_drawer_post_op(fx, task, 1, torch.tensor(slot, dtype=torch.int32, device=DEV), part_C)
+    assert [slot[k] for k in keep] == task.part_slot.tolist() and not np.isnan(good["pose_R"]).any()
+    for k, v in good.items():
+        if k in ("pose_R", "pose_T"):
+            assert np.isnan(got[k][:, bad_at]).all(), k
+            assert same_bits(got[k][:, keep], v), k
+        else:
+            assert same_bits(got[k], v), k
+
+
 # ------------------------------------------------------------------------------------------- 3. layouts
 @pytest.mark.parametrize("off", [1, 2, 3])
 def test_column_views_leave_everything_else_alone(off):
