@@ -173,6 +173,19 @@ int pm_pointnet_enc_fwd_f32(const float* x, long ldx, int B, int P, int C, int s
                             int act /* PM_ACT_* of the two hidden layers (network.py:147-153 takes any of get_activation's
                                        seven; PM_ACT_TANH -- every shipped cfg -- runs the tuned packed-tanh kernels) */,
                             void* stream);
+/* Screened tanh forward (csrc/pointnet_enc_screen.h): same contract as pm_pointnet_enc_fwd_f32 with act = PM_ACT_TANH and the
+ * same fp32 result class.  Layers 1-2 are the dense kernel's (h2_save bit-identical); layer 3 is screened per 64-point tile on
+ * split-bf16 MFMAs with a rigorous per-channel error bound, and only the points that can still be a channel's maximum get
+ * their exact fp32 dot product; the mean is W3 * mean(h2) + b3.  `packed` as above (layer 2, and layer 3 of the dense
+ * fallback); `packed_screen` = pm_pointnet_packed_screen_bytes() bytes written by pm_pointnet_pack_weights_screen from the
+ * current W3 / b3 (16-byte aligned).  counters: NULL, or three device uint64 the kernel ADDS to (survivors evaluated, (wave,
+ * tile) pairs sent to the dense fallback, (tile, channel) pairs with a survivor) -- tests and timing only. */
+size_t pm_pointnet_packed_screen_bytes(void);
+int pm_pointnet_pack_weights_screen(const float* W3, const float* b3, void* packed, void* stream);
+int pm_pointnet_enc_fwd_screen_f32(const float* x, long ldx, int B, int P, int C, int sub_mean, const float* W1,
+                                   const float* b1, const float* b2, const float* b3, const float* packed,
+                                   const void* packed_screen, int max_mean, float* feat, long ldf, int32_t* argmax,
+                                   float* h2_save, unsigned long long* counters, void* stream);
 /* OPT-IN split-bf16 forward: same contract as pm_pointnet_enc_fwd_f32, but the two big per-point GEMMs run as
  * a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on bf16 MFMAs with fp32 accumulation (~1e-5 relative instead of ~1e-7;
  * 5.3x less matrix-pipe time).  P must be a multiple of 128.  `packed` = pm_pointnet_packed_bf3_bytes() bytes

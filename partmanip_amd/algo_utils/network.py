@@ -31,6 +31,8 @@ _SUPPORTED_ACT = {"tanh": ops.ACT_TANH}
 # resident work-groups waiting at a stripe counter hold CU slots the other network's short kernels would have filled.
 import os as _os
 CHAIN_LAUNCH = _os.environ.get("PARTMANIP_CHAIN", "0") == "1"
+# PointNet 'f32' tanh forward: screened layer 3 (csrc/pointnet_enc_screen.h) unless net_cfg['screen'] or PARTMANIP_PN_SCREEN says otherwise
+PN_SCREEN_DEFAULT = True
 
 
 def get_activation(act_name):
@@ -337,7 +339,16 @@ class PointNet(_HipNet):
         if (self.precision != 'f32' or self.precision_bwd != 'f32') and code != ops.ACT_TANH:
             raise NotImplementedError(f"PointNet precision '{self.precision}' / precision_bwd '{self.precision_bwd}' is a tanh "
                                       f"kernel; activation '{act}' runs on 'f32'")
+        # 'screen' (not a reference key; environment PARTMANIP_PN_SCREEN=0|1 overrides it for A/B in one build): the 'f32' tanh
+        # forward screens layer 3 on split-bf16 MFMAs and finishes the pooling's winners in exact fp32
+        # (csrc/pointnet_enc_screen.h) instead of running layer 3 densely; other activations always run the dense kernel
+        # (their h2 is unbounded, the screen's error bound needs |h2| <= 1).  `screen_counters`: None, or a 3 x int64 device
+        # tensor the screened kernel adds its survivor / fallback counts to (tests, tools/time_enc.py).
+        screen = _os.environ.get("PARTMANIP_PN_SCREEN")
+        self.screen = bool(net_cfg.get('screen', PN_SCREEN_DEFAULT)) if screen is None else screen == "1"
+        self.screen_counters = None
         object.__setattr__(self, "_act", code)
+        object.__setattr__(self, "_packed_s", None)
         object.__setattr__(self, "_head", _LinearChain([self.final_mlp[0], self.final_mlp[2], self.final_mlp[4]], code))
         object.__setattr__(self, "_enc_grads", None)
         object.__setattr__(self, "_packed", None)
@@ -389,6 +400,14 @@ class PointNet(_HipNet):
             ops.pointnet_enc_fwd_bf6(x, self.point_num, self.in_channels, self.substract_mean, self.mlp[0].weight.data,
                                      self.mlp[0].bias.data, self.mlp[2].bias.data, self.mlp[4].bias.data,
                                      self._packed6, self.max_mean_concat, feat, argmax, h2)
+        elif self.screen and self._act == ops.ACT_TANH and self.point_num % 64 == 0:
+            if self._packed_s is None or self._packed_s.device != x.device:
+                object.__setattr__(self, "_packed_s", torch.empty(ops.pointnet_packed_screen_bytes(), dtype=torch.uint8,
+                                                                  device=x.device))
+            ops.pointnet_pack_screen(self.mlp[4].weight.data, self.mlp[4].bias.data, self._packed_s)
+            ops.pointnet_enc_fwd_screen(x, self.point_num, self.in_channels, self.substract_mean, self.mlp[0].weight.data,
+                                        self.mlp[0].bias.data, self.mlp[2].bias.data, self.mlp[4].bias.data, packed,
+                                        self._packed_s, self.max_mean_concat, feat, argmax, h2, self.screen_counters)
         else:
             ops.pointnet_enc_fwd(x, self.point_num, self.in_channels, self.substract_mean, self.mlp[0].weight.data,
                                  self.mlp[0].bias.data, self.mlp[2].bias.data, self.mlp[4].bias.data, packed,

@@ -383,6 +383,8 @@ extern "C" int pm_pointnet_enc_fwd_f32(const float* x, long ldx, int B, int P, i
     return PM_OK;
 }
 
+#include "pointnet_enc_screen.h"      // the screened tanh forward: layer 3 only where the pooling can see it
+
 // ================================================================================== backward
 // Gradient of the pooled features w.r.t. the layer-3 output is structured:
 //   G[b,p,c] = dmean[b,c]/P  (every point)  +  dmax[b,c] * [p == argmax[b,c]]

@@ -1,0 +1,414 @@
+// Screened PointNet encoder forward (tanh, fp32 results): layers 1 and 2 are pn_fwd_kernel's, bit for bit; layer 3
+// (256 -> 512, 80 % of the dense kernel's MFMA time) is only evaluated where the pooling can see it.  Included by
+// pointnet_enc.hip after the dense forward, whose device pieces it reuses.
+//
+// Layer 3 is linear and feeds a max and a mean over the cloud's points:
+//   mean_p(W3 h2[p] + b3) = W3 mean_p(h2[p]) + b3        one 256 x 512 matrix-vector product per cloud;
+//   max_p                                                 only the winning point of every channel matters.
+// Per 64-point tile the kernel computes an APPROXIMATE layer 3 on split-bf16 MFMAs (hi = bf16(x), lo = bf16(x - hi);
+// z~ = b3 + hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16: 192 MFMAs of 32 cycles per wave against 512 of 64),
+// and with a rigorous per-channel bound eps_c >= |z~ - z^| (z^ = the fp32 dot product below) keeps only the points
+//   !(z~ < m~ - 2 eps_c)   and   !(z~ + eps_c <= vmax)           m~ = tile maximum of z~, vmax = running exact maximum
+// Both tests are written negated, so a NaN or infinite z~ / eps / vmax lands on the survivor side.  A skipped point p
+// has z^_p <= z~_p + eps < m~ - eps <= z^_q for the tile's q = argmax z~ (or z^_p <= vmax): it can neither beat nor tie.
+// Every survivor (p, c) is then evaluated exactly: eight lanes, lane j takes k = 4 j + 32 i + e (i = 0..7, e = 0..3) as
+// one fmaf chain in that order, the eight partial sums are combined by the xor-4, -2, -1 butterfly, and b3_c is added
+// last -- one fixed order, whatever the other survivors are.  The running maximum takes v when
+// v > vmax || (v == vmax && p < imax), so survivor order cannot change the result and ties go to the lowest point.
+// A wave whose tile has more than PS_CAP survivors (degenerate clouds: all points equal, zero padding) runs the dense
+// fp32 layer 3 of pn_fwd_kernel for that tile instead: such a tile costs the dense layer 3 PLUS the screen it already ran,
+// at this kernel's two waves per SIMD (a batch of all-equal clouds is timed in profiles/round7_pointnet_screen.md).
+//
+// eps_c (ps_pack_kernel).  With |h| <= 1 under tanh, S = sum_k |w_ck| |h_k| <= ||W3[c]||_1 =: L.
+//   split:  x = hi + lo + d, |lo| <= 2^-9 |x| (1 + 2^-9), |d| <= 2^-18 |x|; the products dropped from w h are
+//           w_lo h_lo + d_w h + w d_h (+ higher order) <= 3 * 2^-18 (1 + 2^-8) |w||h|          -> 4 * 2^-18 L taken
+//   z~:     769 terms (bias + 3 x 256 exact bf16 products, sum of magnitudes <= (1 + 2^-8) L + |b3|) accumulated in fp32 in
+//           the matrix unit's own order; one rounding of at most 2^-23 relative per accumulation (covers round-to-nearest
+//           and truncation)                                                                    -> 1538 * 2^-24 (L + |b3|)
+//   z^:     256 fmaf + 3 butterfly adds + the bias add, round-to-nearest                       -> 260 * 2^-24 (L + |b3|)
+//   eps_c = (2^-16 + 2048 * 2^-24) * (L + |b3_c|) * (1 + 2^-10), evaluated in double and rounded up to float
+// (the last factor covers the rounding of L itself).  The CPU emulation of the screen used 3 * 2^-18 + 1100 * 2^-24 and saw
+// errors 200x below it.
+//
+// Work-group: 8 waves own one cloud; wave w owns channels [64 w, 64 w + 64) in layer 3 and lane l of it keeps the running
+// (vmax, imax) of channel 64 w + l.  LDS: fp32 H tile 66.5 KB (H1, then H2) + bf16 hi / lo planes of H2 67.6 KB + survivor
+// lists 8 KB + 4 KB = 146.5 KB: one work-group per CU, two waves per SIMD.
+#pragma once
+
+typedef __bf16 ps_bf16x8 __attribute__((ext_vector_type(8)));
+
+#define PS_LDP (PN_C2 + 8)               // halfwords per plane row (528 B: 16 rows hit 16 distinct 16-B slots, as in pointnet_enc_bf3.hip)
+#define PS_CAP 128                       // survivors per wave and tile before the dense fallback (~100 cycles each against 32768 dense)
+#define PS_NW 8
+#define PS_P3 (16 * 16 * 64 * 8)         // halfwords of one W3 plane: [nb 16][step 16][lane 64][8]
+// packed buffer (bytes): W3 hi plane | W3 lo plane | 8 KB pad (the operand stream reads one step past the end) | W3 row-major fp32 | eps[512]
+#define PS_OFF_P3H 0
+#define PS_OFF_P3L (2 * PS_P3)
+#define PS_OFF_W3 (4 * PS_P3 + 8192)
+#define PS_OFF_EPS (PS_OFF_W3 + PN_C3 * PN_C2 * 4)
+#define PS_PACKED_BYTES (PS_OFF_EPS + PN_C3 * 4)
+
+extern "C" size_t pm_pointnet_packed_screen_bytes(void) { return PS_PACKED_BYTES; }
+
+__device__ __forceinline__ unsigned ps_cvt_pk(float a, float b) {          // {bf16(a) | bf16(b) << 16}, RNE
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));       // pure: the compiler may schedule and combine it
+    return r;
+}
+__device__ __forceinline__ void ps_split(float x, unsigned short& hi, unsigned short& lo) {
+    const unsigned h = ps_cvt_pk(x, 0.f) & 0xffffu;
+    const float xh = __uint_as_float(h << 16);
+    hi = (unsigned short)h;
+    lo = (unsigned short)(ps_cvt_pk(x - xh, 0.f) & 0xffffu);
+}
+
+__global__ __launch_bounds__(256) void ps_pack_kernel(const float* __restrict__ W3, const float* __restrict__ b3,
+                                                       unsigned char* __restrict__ packed) {
+    const int i = blockIdx.x * 256 + threadIdx.x;                          // one (nb, step, lane, e) plane slot = one W3 element
+    if (i >= PS_P3) return;
+    unsigned short* Ph = (unsigned short*)(packed + PS_OFF_P3H);
+    unsigned short* Pl = (unsigned short*)(packed + PS_OFF_P3L);
+    float* Wr = (float*)(packed + PS_OFF_W3);
+    const int e = i & 7, lane = (i >> 3) & 63, li = lane & 31, lq = lane >> 5, step = (i >> 9) & 15, nb = i >> 13;
+    unsigned short h, l;
+    ps_split(W3[(nb * 32 + li) * PN_C2 + step * 16 + lq * 8 + e], h, l);
+    Ph[i] = h;
+    Pl[i] = l;
+    Wr[i] = W3[i];
+    if (i < 4096) ((unsigned short*)(packed + 4 * PS_P3))[i] = 0;
+    if (i < PN_C3) {
+        double L = 0.0;
+        for (int k = 0; k < PN_C2; ++k) L += fabs((double)W3[i * PN_C2 + k]);
+        const double ed = (0x1p-16 + 2048.0 * 0x1p-24) * (L + fabs((double)b3[i])) * (1.0 + 0x1p-10);
+        float ef = (float)ed;
+        if ((double)ef < ed) ef = __uint_as_float(__float_as_uint(ef) + 1);   // round up (a NaN or inf eps stays what it is: the test is false)
+        ((float*)(packed + PS_OFF_EPS))[i] = ef;
+    }
+}
+
+extern "C" int pm_pointnet_pack_weights_screen(const float* W3, const float* b3, void* packed, void* stream) {
+    PM_REQUIRE(W3 && b3 && packed);
+    if (((uintptr_t)packed & 15) != 0) return PM_EALIGN;
+    hipLaunchKernelGGL(ps_pack_kernel, dim3(PS_P3 / 256), dim3(256), 0, pm_stream(stream), W3, b3, (unsigned char*)packed);
+    PM_CHECK_LAUNCH();
+    return PM_OK;
+}
+
+#define PS_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
+__device__ __forceinline__ ps_bf16x8 ps_bf(const uint4& v) { return *(const ps_bf16x8*)&v; }
+
+// acc[mb][nb] += A(64 rows, hi / lo planes in LDS) * B(packed hi / lo planes), K = 256 in 16 steps of 16: the operand
+// pipeline of pointnet_enc_bf3.hip (next step's B fetched before this step's MFMAs, pinned with sched_barrier).
+__device__ __forceinline__ void ps_stream(const unsigned short* __restrict__ Ah, const unsigned short* __restrict__ Al,
+                                          const uint4* __restrict__ Bh, const uint4* __restrict__ Bl, f32x16 (&acc)[2][2]) {
+    uint4 bh0[2], bl0[2], bh1[2], bl1[2];
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+        bh0[nb] = Bh[(size_t)(nb * 16) * 64];
+        bl0[nb] = Bl[(size_t)(nb * 16) * 64];
+    }
+#define PS_STEP(S_, BHC, BLC, BHN, BLN)                                                        \
+    {                                                                                          \
+        uint4 ah[2], al[2];                                                                    \
+        _Pragma("unroll") for (int mb = 0; mb < 2; ++mb) {                                     \
+            ah[mb] = *(const uint4*)(Ah + mb * 32 * PS_LDP + (S_) * 16);                       \
+            al[mb] = *(const uint4*)(Al + mb * 32 * PS_LDP + (S_) * 16);                       \
+        }                                                                                      \
+        _Pragma("unroll") for (int nb = 0; nb < 2; ++nb) {   /* next step (one step past the end on the last trip: padded) */ \
+            BHN[nb] = Bh[(size_t)(nb * 16 + (S_) + 1) * 64];                                   \
+            BLN[nb] = Bl[(size_t)(nb * 16 + (S_) + 1) * 64];                                   \
+        }                                                                                      \
+        __builtin_amdgcn_sched_barrier(0);                                                     \
+        _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                                       \
+            _Pragma("unroll") for (int mb = 0; mb < 2; ++mb) {                                 \
+                acc[mb][nb] = PS_MFMA(ps_bf(ah[mb]), ps_bf(BHC[nb]), acc[mb][nb]);             \
+                acc[mb][nb] = PS_MFMA(ps_bf(ah[mb]), ps_bf(BLC[nb]), acc[mb][nb]);             \
+                acc[mb][nb] = PS_MFMA(ps_bf(al[mb]), ps_bf(BHC[nb]), acc[mb][nb]);             \
+            }                                                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                     \
+    }
+#pragma unroll 1
+    for (int s = 0; s < 16; s += 2) {
+        PS_STEP(s, bh0, bl0, bh1, bl1)
+        PS_STEP(s + 1, bh1, bl1, bh0, bl0)
+    }
+#undef PS_STEP
+}
+
+// counters (optional, tests and timing only): [0] survivors evaluated, [1] (wave, tile) pairs sent to the dense
+// fallback, [2] (tile, channel) pairs with at least one survivor
+template <int CT>
+__global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
+    const float* __restrict__ x, long ldx, int P, int C, int sub_mean, const float* __restrict__ W1,
+    const float* __restrict__ b1, const float* __restrict__ b2, const float* __restrict__ b3,
+    const float* __restrict__ packed, const unsigned char* __restrict__ packed_s, int max_mean, float* __restrict__ feat,
+    long ldf, int32_t* __restrict__ argmax, float* __restrict__ h2_save, unsigned long long* __restrict__ counters) {
+    constexpr int NT = PS_NW * 64;
+    __shared__ __attribute__((aligned(16))) float H[PN_TM * PN_LD2];                  // H1 [64][132], then H2 [64][260]
+    __shared__ __attribute__((aligned(16))) unsigned short Hp[2 * PN_TM * PS_LDP];    // bf16 hi | lo planes of H2
+    __shared__ __attribute__((aligned(16))) float Xs[PN_TM * PN_MAXC];
+    __shared__ double red[16];
+    __shared__ double cs[PN_C2];                                                      // column sums of h2 over the cloud
+    __shared__ int skey[PS_NW][PS_CAP];                                               // survivors: (row << 6) | channel in wave
+    __shared__ float sval[PS_NW][PS_CAP];                                             // their exact layer-3 values
+    unsigned short* Hh = Hp;
+    unsigned short* Hl = Hp + PN_TM * PS_LDP;
+
+    const int b = blockIdx.x, tid = threadIdx.x, lane0 = tid & 63, wave = tid >> 6;
+    const float* xb = x + (long)b * ldx;
+    const float4* P2v = (const float4*)(packed + PN_P2_OFF);
+    const float4* P3v = (const float4*)(packed + PN_P3_OFF);
+    const uint4* S3h = (const uint4*)(packed_s + PS_OFF_P3H);
+    const uint4* S3l = (const uint4*)(packed_s + PS_OFF_P3L);
+    const float* W3r = (const float*)(packed_s + PS_OFF_W3);
+    const float* epsg = (const float*)(packed_s + PS_OFF_EPS);
+
+    float cen[3] = {0.f, 0.f, 0.f};
+    if (sub_mean) cloud_centroid<NT>(xb, P, C, red, cen);
+
+    float vmax = -INFINITY, pois = 0.f;      // lane l: channel 64 wave + l.  pois: sum of the non-finite exact values seen
+    int imax = 0;
+    double csum = 0.0;                       // lanes < 32: column 32 wave + lane of h2
+
+    const int ntiles = P / PN_TM;
+    stage_points<PN_TM, NT>(xb, 0, C, sub_mean, cen, Xs);
+    for (int tile = 0; tile < ntiles; ++tile) {
+        int lane = lane0;                    // laundered per tile: see pn_fwd_kernel
+        asm volatile("" : "+v"(lane));
+        const int li = lane & 31, lh = lane >> 5;
+        __syncthreads();                     // Xs staged; the previous tile's reads of H and the planes are done
+        layer1_tile<CT, PN_TM, NT, true>(Xs, W1, b1, C, H);
+        __syncthreads();
+        {
+            f32x16 acc2[2][1];
+            zero_acc<2, 1>(acc2);
+            layer2_mfma<2, 1>(H, P2v, wave, lane, acc2);
+            __syncthreads();                 // every wave has finished reading H1 (and Xs)
+            // layer-2 epilogue: layer2_store's arithmetic, plus the bf16 planes and this tile's column sum
+            const int col = wave * 32 + li;
+            const float b2c = b2[col];
+            float ts = 0.f;                  // fp32 within the tile, rows in increasing order
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const f32x2 v2 = pm_tanh2(acc2[mb][0][r] + b2c, acc2[mb][0][r + 1] + b2c);
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int row = mb * 32 + ((r + j) & 3) + 8 * ((r + j) >> 2) + 4 * lh;
+                        const float v = j ? v2.y : v2.x;
+                        unsigned short hi, lo;
+                        ps_split(v, hi, lo);
+                        H[row * PN_LD2 + col] = v;
+                        Hh[row * PS_LDP + col] = hi;
+                        Hl[row * PS_LDP + col] = lo;
+                        ts += v;
+                    }
+                }
+            ts += __shfl_xor(ts, 32, 64);    // the other 32 rows; both halves hold the same sum
+            csum += (double)ts;              // fp64 across tiles
+            if (tile + 1 < ntiles) stage_points<PN_TM, NT>(xb, tile + 1, C, sub_mean, cen, Xs);
+        }
+        __syncthreads();
+
+        // ---- screen: z~ for 64 points x this wave's 64 channels ---------------------------------------------
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const float b3c = b3[(wave * 2 + nb) * 32 + li];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[0][nb][r] = acc[1][nb][r] = b3c;
+        }
+        ps_stream(Hh + li * PS_LDP + lh * 8, Hl + li * PS_LDP + lh * 8, S3h + (size_t)(wave * 2 * 16) * 64 + lane,
+                  S3l + (size_t)(wave * 2 * 16) * 64 + lane, acc);
+
+        unsigned msk[2];
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            float m = -INFINITY;
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) m = fmaxf(m, acc[mb][nb][r]);
+            m = fmaxf(m, __shfl_xor(m, 32, 64));
+            const float e = epsg[(wave * 2 + nb) * 32 + li];
+            const float vm = __shfl(vmax, nb * 32 + li, 64);
+            const float thr = m - 2.f * e;
+            unsigned k = 0;
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float z = acc[mb][nb][r];
+                    const bool s = !(z < thr) && !(z + e <= vm);
+                    k |= (s ? 1u : 0u) << (mb * 16 + r);
+                }
+            msk[nb] = k;
+        }
+        const int n = __popc(msk[0]) + __popc(msk[1]);
+        int incl = n;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += t;
+        }
+        const int total = __builtin_amdgcn_readlane(incl, 63);
+
+        if (total <= PS_CAP) {
+            // ---- survivors -> list -> exact fp32 values -> running maximum ------------------------------------
+            int off = incl - n;
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                unsigned m = msk[nb];
+                while (m) {
+                    const int bit = __ffs(m) - 1;
+                    m &= m - 1;
+                    const int row = (bit >> 4) * 32 + (bit & 3) + 8 * ((bit & 15) >> 2) + 4 * lh;
+                    skey[wave][off++] = (row << 6) | (nb * 32 + li);
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            const int j = lane & 7, g = lane >> 3;
+            for (int e0 = 0; e0 < total; e0 += 8) {
+                const int e = e0 + g;
+                const int key = (e < total) ? skey[wave][e] : 0;
+                const int row = key >> 6, cl = key & 63;
+                const float* hp = H + row * PN_LD2 + 4 * j;
+                const float* wp = W3r + (size_t)(wave * 64 + cl) * PN_C2 + 4 * j;
+                float s = 0.f;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const float4 w = *(const float4*)(wp + 32 * i);
+                    const float4 h = *(const float4*)(hp + 32 * i);
+                    s = fmaf(w.x, h.x, s);
+                    s = fmaf(w.y, h.y, s);
+                    s = fmaf(w.z, h.z, s);
+                    s = fmaf(w.w, h.w, s);
+                }
+                s += __shfl_xor(s, 4, 64);
+                s += __shfl_xor(s, 2, 64);
+                s += __shfl_xor(s, 1, 64);
+                s += b3[wave * 64 + cl];
+                if (j == 0 && e < total) sval[wave][e] = s;
+            }
+            __builtin_amdgcn_wave_barrier();
+            for (int e = 0; e < total; ++e) {                 // wave-uniform: every lane picks its own channel's survivors
+                const int key = skey[wave][e];
+                const float v = sval[wave][e];
+                if ((key & 63) == lane) {
+                    const int p = tile * PN_TM + (key >> 6);
+                    if (!(fabsf(v) < INFINITY)) pois += v;
+                    if (v > vmax || (v == vmax && p < imax)) {
+                        vmax = v;
+                        imax = p;
+                    }
+                }
+            }
+            if (counters) {
+                const unsigned long long h0 = __ballot(msk[0] != 0), h1 = __ballot(msk[1] != 0);
+                if (lane == 0) {
+                    atomicAdd(counters + 0, (unsigned long long)total);
+                    atomicAdd(counters + 2, (unsigned long long)(__popc((unsigned)(h0 | (h0 >> 32))) + __popc((unsigned)(h1 | (h1 >> 32)))));
+                }
+            }
+        } else {
+            // ---- too many survivors: the dense fp32 layer 3 of pn_fwd_kernel for this wave and tile ----------
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                const float b3c = b3[(wave * 2 + nb) * 32 + li];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[0][nb][r] = acc[1][nb][r] = b3c;
+            }
+            mfma_stream<2, 2, 32>(H + li * PN_LD2 + lh * 128, PN_LD2, P3v + (size_t)(wave * 2) * 32 * 64 + lane, acc);
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                float bv = -INFINITY, ps = 0.f;
+                int bp = 0;
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {            // increasing point order: strict > keeps the lowest index
+                        const float v = acc[mb][nb][r];
+                        if (!(fabsf(v) < INFINITY)) ps += v;
+                        if (v > bv) {
+                            bv = v;
+                            bp = tile * PN_TM + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        }
+                    }
+                const float ov = __shfl_xor(bv, 32, 64), os = __shfl_xor(ps, 32, 64);
+                const int op = __shfl_xor(bp, 32, 64);
+                if (ov > bv || (ov == bv && op < bp)) {
+                    bv = ov;
+                    bp = op;
+                }
+                if (lh == nb) {                               // the lane that owns channel 64 wave + 32 nb + li
+                    pois += ps + os;
+                    if (bv > vmax || (bv == vmax && bp < imax)) {
+                        vmax = bv;
+                        imax = bp;
+                    }
+                }
+            }
+            if (counters && lane == 0) atomicAdd(counters + 1, 1ull);
+        }
+        // training forward: the H2 tile (still intact in LDS) also goes to HBM, as in pn_fwd_kernel
+        if (h2_save) {
+            float* dst = h2_save + ((long)b * P + (long)tile * PN_TM) * PN_C2;
+#pragma unroll 2
+            for (int i = 0; i < PN_TM * PN_C2 / 4 / NT; ++i) {
+                const int q = tid + NT * i, row = q >> 6, c4 = q & 63;
+                const f32x4 v = *(const f32x4*)(H + row * PN_LD2 + 4 * c4);
+                *(f32x4*)(dst + row * PN_C2 + 4 * c4) = v;
+            }
+        }
+    }
+    // ---- epilogue: thread tid owns channel tid --------------------------------------------------------------
+    if ((lane0 >> 5) == 0) cs[wave * 32 + lane0] = csum;
+    __syncthreads();
+    const int ch = tid;
+    // A non-finite layer-3 value always survives the screen (its z~ is NaN or infinite), so pois is the sum of ALL of this
+    // channel's non-finite values: NaN exactly when the dense kernel's column sum is (a NaN, or infinities of both signs),
+    // which is when that kernel, like torch.max on a NaN, returns NaN.
+    float v = vmax;
+    if (pois != pois) v = pois;
+    feat[(long)b * ldf + ch] = v;
+    argmax[(long)b * PN_C3 + ch] = imax;
+    if (max_mean) {
+        // mean_p z3[p] = W3 (sum_p h2[p]) / P + b3 in fp64 (k increasing), rounded to fp32 once
+        const float* wr = W3r + (size_t)ch * PN_C2;
+        double s = 0.0;
+#pragma unroll 4
+        for (int k = 0; k < PN_C2; k += 4) {
+            const float4 w = *(const float4*)(wr + k);
+            s = fma((double)w.x, cs[k], s);
+            s = fma((double)w.y, cs[k + 1], s);
+            s = fma((double)w.z, cs[k + 2], s);
+            s = fma((double)w.w, cs[k + 3], s);
+        }
+        float mv = (float)(s / (double)P + (double)b3[ch]);
+        if (pois != pois) mv = pois;
+        feat[(long)b * ldf + PN_C3 + ch] = mv;
+    }
+}
+
+extern "C" int pm_pointnet_enc_fwd_screen_f32(const float* x, long ldx, int B, int P, int C, int sub_mean, const float* W1,
+                                              const float* b1, const float* b2, const float* b3, const float* packed,
+                                              const void* packed_screen, int max_mean, float* feat, long ldf,
+                                              int32_t* argmax, float* h2_save, unsigned long long* counters, void* stream) {
+    PM_REQUIRE(x && W1 && b1 && b2 && b3 && packed && packed_screen && feat && argmax);
+    if (h2_save && ((uintptr_t)h2_save & 15) != 0) return PM_EALIGN;
+    PM_REQUIRE(B > 0 && P > 0 && P % PN_TM == 0 && C >= 1 && C <= PN_MAXC && ldx >= (long)P * C);
+    PM_REQUIRE(ldf >= PN_C3 * (max_mean ? 2 : 1));
+    PM_REQUIRE(!sub_mean || C >= 3);
+    if (((uintptr_t)packed & 15) != 0 || ((uintptr_t)packed_screen & 15) != 0 || ((uintptr_t)counters & 7) != 0) return PM_EALIGN;
+#define PS_LAUNCH(CT)                                                                                                 \
+    hipLaunchKernelGGL((pn_fwd_screen_kernel<CT>), dim3(B), dim3(PS_NW * 64), 0, pm_stream(stream), x, ldx, P, C, sub_mean, \
+                       W1, b1, b2, b3, packed, (const unsigned char*)packed_screen, max_mean, feat, ldf, argmax, h2_save,   \
+                       counters)
+    if (C == 3) PS_LAUNCH(3);
+    else if (C == 4) PS_LAUNCH(4);
+    else PS_LAUNCH(0);
+#undef PS_LAUNCH
+    PM_CHECK_LAUNCH();
+    return PM_OK;
+}

@@ -346,6 +346,30 @@ def pointnet_enc_fwd(x, P, Cc, sub_mean, w1, b1, b2, b3, packed, max_mean, feat,
               "pm_pointnet_enc_fwd_f32")
 
 
+def pointnet_packed_screen_bytes():
+    return int(lib.pm_pointnet_packed_screen_bytes())
+
+
+def pointnet_pack_screen(w3, b3, packed):
+    _req(w3, b3, packed)
+    check(lib.pm_pointnet_pack_weights_screen(_ptr(w3), _ptr(b3), _ptr(packed), _stream()), "pm_pointnet_pack_weights_screen")
+
+
+def pointnet_enc_fwd_screen(x, P, Cc, sub_mean, w1, b1, b2, b3, packed, packed_screen, max_mean, feat, argmax, h2_save=None,
+                            counters=None):
+    """The screened tanh forward (csrc/pointnet_enc_screen.h).  counters: optional 3 x int64 device tensor the kernel adds
+    [survivors, dense-fallback (wave, tile) pairs, (tile, channel) pairs with a survivor] to."""
+    _req(x, w1, b1, b2, b3, packed, packed_screen, feat, argmax, h2_save, counters)
+    if counters is not None and (counters.dtype != torch.int64 or counters.numel() < 3 or not counters.is_contiguous()):
+        raise ValueError("counters: expected a contiguous int64 tensor of 3 elements")
+    B = x.shape[0]
+    with TIMER.bracket("pointnet_enc_fwd"):
+        check(lib.pm_pointnet_enc_fwd_screen_f32(_ptr(x), _rows(x, "x"), B, P, Cc, int(sub_mean), _ptr(w1), _ptr(b1), _ptr(b2),
+                                                 _ptr(b3), _ptr(packed), _ptr(packed_screen), int(max_mean), _ptr(feat),
+                                                 _rows(feat, "feat"), _ptr(argmax), _ptr(h2_save), _ptr(counters), _stream()),
+              "pm_pointnet_enc_fwd_screen_f32")
+
+
 def pointnet_pack_bf3(w2, w3, packed):
     _req(w2, w3, packed)
     check(lib.pm_pointnet_pack_weights_bf3(_ptr(w2), _ptr(w3), _ptr(packed), _stream()), "pm_pointnet_pack_weights_bf3")
