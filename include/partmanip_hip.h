@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 158 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 159 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -543,6 +543,33 @@ int pm_mesh_sdf_bake_f32(const float* tri, int F, int X, int Y, int Z, float vox
  * out_stride < 3 K, sel == NULL with K != Q, a non-zero sel_stride < K. */
 int pm_mesh_pc_query_f32(const float* pts, const int32_t* part_of, int Q, const float* pose_R, const float* pose_T, int B, int M,
                          const int32_t* sel, long sel_stride, int K, float* out, long out_stride, void* stream);
+
+/* ------------------------------------------------------------------ depth camera over the posed part meshes (observation side)
+ * The producer of the depth observations of tasks/hand_base.py:312-343 (there: the simulator's camera sensors): out (B, V, H, W) =
+ * z-depth (not ray length) of the nearest surface along the ray through each pixel centre, `far` where nothing is hit -- with
+ * far = 100 the tensor that TSDFVolume.depth2pc / integrate / sparse_voxel take.  verts (NV, 3): canonical vertices of all parts,
+ * concatenated; vert_part (NV) int32: each vertex's part; faces (F, 3) int32 into verts; pose_R (B, M, 3, 3), pose_T (B, M, 3) as
+ * in pm_mesh_pc_query_f32; cam_pose (V, 4, 4) camera->world, the camera looking along +z with x right and y down (what
+ * TSDFVolume.register_camera takes).  All arithmetic fp32, every product, sum and difference rounded on its own, divisions IEEE:
+ *   world vertex of part j   xw = ((x0 R[j,0] + x1 R[j,1]) + x2 R[j,2]) + T[j]
+ *   camera vertex            d = xw - C[:,3],  p_k = (d0 C[0,k] + d1 C[1,k]) + d2 C[2,k]
+ *   triangle (p0, p1, p2)    n0 = p1 x p2, n1 = p2 x p0, n2 = p0 x p1, each component a b - c d in the usual order
+ *   pixel (row r, column c)  dx = (float(c) - cx) / fx, dy = (float(r) - cy) / fy, w_i = (dx n_i.x + dy n_i.y) + n_i.z,
+ *                            s = (w0 + w1) + w2
+ *   hit                      iff w0, w1, w2 are all >= 0 or all <= 0 (both faces count, inclusive), s != 0 and
+ *                            z = ((w0 p0.z + w1 p1.z) + w2 p2.z) / s satisfies near < z < far
+ *   out[b * out_stride + (v H + r) W + c] = min z over the triangles that hit, else far.
+ * The bits are defined and repeat: the minimum is order-free (integer min on the bits of the positive z, no float atomics), and
+ * two triangles sharing an edge see exactly opposite edge values, so no crack opens between them.  A triangle is skipped when a
+ * face index is outside [0, NV), a part outside [0, M) or a camera-space coordinate non-finite; nothing is read through a bad
+ * index.  A triangle with a corner at z <= near is tested against the whole image.  out_stride >= V H W in elements; floats of a
+ * row past V H W are not touched.  Two launches (fill, raster), no workspace, stream-ordered, never synchronises.
+ * PM_EINVAL (before any launch): a NULL pointer, NV, F, B, M, V, H or W < 1, near <= 0, far <= near, out_stride < V H W,
+ * W + H > 12288 (the per-block table of dx and dy), ceil(F / 256) V B >= 2^31. */
+int pm_mesh_depth_render_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F,
+                             const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V, float fx,
+                             float fy, float cx, float cy, int H, int W, float near, float far, float* out, long out_stride,
+                             void* stream);
 
 /* ------------------------------------------------------------------ grasp_cube task step (simulator side of the learner)
  * The tensor program of the reference's task layer (tasks/grasp_cube.py, tasks/load_robot.py, tasks/hand_base.py:363-392, 431-441)

@@ -104,6 +104,7 @@ SIGNATURES = {
     "pm_mesh_sdf_bake_workspace_bytes": (Z, [I]),
     "pm_mesh_sdf_bake_f32": (I, [P, I, I, I, I, F, F, F, F, F, I, P, P, Z, P]),
     "pm_mesh_pc_query_f32": (I, [P, P, I, P, P, I, I, P, L, I, P, L, P]),
+    "pm_mesh_depth_render_f32": (I, [P, P, I, P, I, P, P, I, I, P, I, F, F, F, F, I, I, F, F, P, L, P]),
     "pm_grasp_cube_post_f32": (I, [P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, F, P, P, P, I, P, L, P, L, P, P, P, P, L, P, P, P]),
     "pm_franka_control_f32": (I, [P, L, I, P, P, I, I, I, I, I, P, P, P, F, I, P, P, P, I, I, I, P, P, P, P, P, P, I, P]),
     "pm_franka_control_mobile_f32": (I, [P, L, I, P, P, I, I, I, I, I, P, P, P, F, I, I, P, P, P, P, I, I, I, P, P, P, P, P, P, I, P]),
@@ -204,7 +205,7 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
-ABI_VERSION = 158                      # == PM_ABI_VERSION in include/partmanip_hip.h (checked by tests/test_capi_symbols.py)
+ABI_VERSION = 159                      # == PM_ABI_VERSION in include/partmanip_hip.h (checked by tests/test_capi_symbols.py)
 if lib.pm_version() != ABI_VERSION:
     raise ImportError(f"{LIB_PATH} is stale: it reports ABI {lib.pm_version()}, this package needs {ABI_VERSION}. "
                       "Rebuild it with `python -m partmanip_amd.build`.")

@@ -1,0 +1,222 @@
+// Depth camera over the posed part meshes: the producer of the reference's depth observations (tasks/hand_base.py:312-343 takes
+// the image from the simulator's camera sensors; here it is rendered from the same (pose_R, pose_T) that query_pc and query_tsdf take).
+//
+// Definition (include/partmanip_hip.h has it in full).  All arithmetic is fp32, every product, sum and difference rounded on its
+// own, divisions IEEE.  Vertex x of part j: xw = ((x0 R[j,0] + x1 R[j,1]) + x2 R[j,2]) + T[j] (mesh_pc.hip's association), d = xw -
+// C[:,3], p_k = (d0 C[0,k] + d1 C[1,k]) + d2 C[2,k] (the reference's bmm(world - t, R), depth2tsdf.py:47).  Triangle (p0, p1, p2):
+// n0 = p1 x p2, n1 = p2 x p0, n2 = p0 x p1.  Pixel (row r, column c): dx = (float(c) - cx) / fx, dy = (float(r) - cy) / fy, w_i = (dx
+// n_i.x + dy n_i.y) + n_i.z, s = (w0 + w1) + w2.  Hit iff the w_i are all >= 0 or all <= 0, s != 0 and z = ((w0 p0.z + w1 p1.z) + w2
+// p2.z) / s lies in (near, far).  out = min z over the triangles that hit, else far.
+//
+// Properties that follow.
+//  * w_i is the edge function of the edge opposite corner i, and it depends on that edge's two corners only.  Reversing the order
+//    of the two corners negates the cross product exactly (a b - c d becomes c d - a b, both products rounded as before), so w_i is
+//    negated exactly: two triangles that share an edge see edge values of exactly opposite sign at every pixel, the inclusive test
+//    gives a pixel on the edge to both, and no crack opens between them.
+//  * The minimum over triangles does not depend on their order and every z is a function of (triangle, pixel) alone, so the image
+//    repeats bit for bit and a rasteriser and a ray caster give the same image -- as long as the rasteriser's pixel range is
+//    conservative, i.e. contains every pixel that passes the hit rule.  Here the range is the box of the three projected corners
+//    widened by one pixel on every side; a triangle with a corner at z <= near projects nowhere useful and gets the whole image.
+//
+// Shape.  One fill launch writes far; one raster launch follows in which a lane owns one (environment, view, triangle): it poses
+// and projects the three corners itself (no per-vertex workspace; the poses and the camera are a few hundred bytes that stay in
+// cache), sets up n0..n2 and its clamped pixel box, and walks it.  z is positive, so the unsigned order of its bits is the float
+// order: the depth minimum is an integer atomicMin on the bits (no float atomics: the bits repeat).  A relaxed read of the current
+// depth first skips a minimum that cannot win; a stale read only costs a redundant update.  A triangle whose box holds more than
+// MD_WAVE_BOX pixels is handed to the whole wave (ballot, then its record broadcast lane by lane), so that a cube face, or a
+// near-plane triangle with the whole image as its box, does not serialise on one lane; that is a schedule choice and cannot
+// change the image.  dx and dy of every column and row are computed once per block into LDS ((W + H) floats), so a pixel test costs
+// two ds_reads, 9 multiplies, 8 adds and the compares, and the division for z is paid by hits only.
+//
+// Memory safety.  A face index outside [0, NV), a part outside [0, M) or a non-finite camera-space coordinate skips the triangle;
+// nothing is read through a bad index.  The box is clamped to the image in float before it becomes an integer, so no loop bound
+// depends on an unclamped value, and every store lands in [0, V H W) of its environment's row: floats past V H W are never written.
+// No workspace, stream-ordered, never synchronises.
+//
+// Atomic shape.  One lane per triangle issues scattered atomics, the shape the programming guide prices as slow; a tiled variant
+// (a block owns an image tile, depths in LDS, every triangle tested against the tile) trades them for a bin pass or for F tests
+// per tile.  It was not built and not measured: here the relaxed read filters most updates (a pixel's depth settles after its
+// first few triangles; 17 % of the pixels are hit at all in the timed scene), and the figures below are what it would have to beat.
+//
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): raster 54 VGPRs, 64 SGPRs, no scratch, occupancy 8 waves / SIMD,
+// LDS (dynamic) 4 (W + H) bytes = 3.2 KB at 512 x 288; fill 28 VGPRs, 51 SGPRs, no scratch.
+// Measured A/B on one MI355X (tools/time_mesh_depth.py: 12 ellipsoids, 133 200 triangles, 1024 environments, random poses; the
+// shipped rig 3 x 288 x 512 / the image rig 1 x 72 x 128, ms per call), MD_WAVE_BOX = 16 / 64 / 256: 56.65 / 18.97 / 18.99 and
+// 10.63 / 2.85 / 2.85.  A box holds 27 / 18 pixels on average (a pixel-sized triangle widened by one pixel), so at 16 nearly every triangle
+// takes the whole wave in turn and the launch serialises; between 64 and 256 few boxes fall and nothing changes; kept = 64.  At 64
+// the shipped rig runs 1.10e10 pixel-triangle tests in 18.97 ms = 5.8e11 tests / s, 1.5 % of the output-bandwidth floor (0.288 ms for
+// 1.8 GB): the kernel is bound by the tests and the triangle set-up, not by its output.
+#include "common.h"
+
+#ifndef MD_WAVE_BOX
+#define MD_WAVE_BOX 64                                       // boxes above this many pixels are walked by the whole wave
+#endif
+#define MD_THREADS 256
+#define MD_MAX_TAB 12288                                     // W + H floats of LDS: 48 KB
+
+__global__ __launch_bounds__(MD_THREADS) void mesh_depth_fill_kernel(float* __restrict__ out, long out_stride, long n, long total,
+                                                                      float far) {
+    for (long i = (long)blockIdx.x * MD_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * MD_THREADS) {
+        const long b = i / n;
+        out[b * out_stride + (i - b * n)] = far;
+    }
+}
+
+struct md_cam {
+    float c[12];                                             // rows 0..2 of the camera->world matrix: c[4 j + k], c[4 j + 3] = t_j
+};
+
+// Camera-space position of vertex i; false if the vertex is to be skipped (bad index, bad part, non-finite result).
+__device__ __forceinline__ bool md_vertex(const float* __restrict__ verts, const int32_t* __restrict__ vert_part, int NV, int M,
+                                          const float* __restrict__ Rb, const float* __restrict__ Tb, const md_cam& cam, int i,
+                                          float& px, float& py, float& pz) {
+    px = py = pz = 0.f;
+    if (i < 0 || i >= NV) return false;
+    const int p = vert_part[i];
+    if (p < 0 || p >= M) return false;
+    const float x0 = verts[3L * i], x1 = verts[3L * i + 1], x2 = verts[3L * i + 2];
+    const float* R = Rb + 9L * p;
+    const float* T = Tb + 3L * p;
+    float d[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float xw = add_rn(add_rn(add_rn(mul_rn(x0, R[3 * j]), mul_rn(x1, R[3 * j + 1])), mul_rn(x2, R[3 * j + 2])), T[j]);
+        d[j] = sub_rn(xw, cam.c[4 * j + 3]);
+    }
+    px = add_rn(add_rn(mul_rn(d[0], cam.c[0]), mul_rn(d[1], cam.c[4])), mul_rn(d[2], cam.c[8]));
+    py = add_rn(add_rn(mul_rn(d[0], cam.c[1]), mul_rn(d[1], cam.c[5])), mul_rn(d[2], cam.c[9]));
+    pz = add_rn(add_rn(mul_rn(d[0], cam.c[2]), mul_rn(d[1], cam.c[6])), mul_rn(d[2], cam.c[10]));
+    return isfinite(px) && isfinite(py) && isfinite(pz);
+}
+
+struct md_tri {
+    float n0x, n0y, n0z, n1x, n1y, n1z, n2x, n2y, n2z, z0, z1, z2;
+    int x0, y0, bw, cnt;                                     // box origin, width and pixel count (0: nothing to do)
+};
+
+__device__ __forceinline__ float md_cross(float a, float b, float c, float d) { return sub_rn(mul_rn(a, b), mul_rn(c, d)); }
+
+// One (pixel, triangle) test and its depth minimum.  dst is this pixel's word of the image, holding the bits of a positive float.
+__device__ __forceinline__ void md_pixel(const md_tri& t, float dx, float dy, float near, float far, unsigned* dst) {
+    const float w0 = add_rn(add_rn(mul_rn(dx, t.n0x), mul_rn(dy, t.n0y)), t.n0z);
+    const float w1 = add_rn(add_rn(mul_rn(dx, t.n1x), mul_rn(dy, t.n1y)), t.n1z);
+    const float w2 = add_rn(add_rn(mul_rn(dx, t.n2x), mul_rn(dy, t.n2y)), t.n2z);
+    const bool pos = w0 >= 0.f && w1 >= 0.f && w2 >= 0.f, neg = w0 <= 0.f && w1 <= 0.f && w2 <= 0.f;
+    if (!(pos || neg)) return;
+    const float s = add_rn(add_rn(w0, w1), w2);
+    if (s == 0.f) return;
+    const float z = __fdiv_rn(add_rn(add_rn(mul_rn(w0, t.z0), mul_rn(w1, t.z1)), mul_rn(w2, t.z2)), s);
+    if (!(z > near && z < far)) return;                      // a NaN fails both
+    const unsigned zb = __float_as_uint(z);
+    if (zb < __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(dst, zb);
+}
+
+__device__ __forceinline__ float md_bcast(float x, int lane) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane));
+}
+
+__global__ __launch_bounds__(MD_THREADS) void mesh_depth_raster_kernel(
+    const float* __restrict__ verts, const int32_t* __restrict__ vert_part, int NV, const int32_t* __restrict__ faces, int F,
+    const float* __restrict__ pose_R, const float* __restrict__ pose_T, int M, const float* __restrict__ cam_pose, int V, int chunks,
+    float fx, float fy, float cx, float cy, int H, int W, float near, float far, float* out, long out_stride) {
+    extern __shared__ float md_tab[];                        // dx of the W columns, then dy of the H rows
+    const long blk = blockIdx.x;
+    const long bv = blk / chunks;
+    const int chunk = (int)(blk - bv * chunks);
+    const long b = bv / V;
+    const int v = (int)(bv - b * V);
+
+    for (int i = threadIdx.x; i < W + H; i += MD_THREADS)
+        md_tab[i] = i < W ? __fdiv_rn(sub_rn((float)i, cx), fx) : __fdiv_rn(sub_rn((float)(i - W), cy), fy);
+
+    md_cam cam;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) cam.c[i] = cam_pose[16L * v + i];
+    const float* Rb = pose_R + b * M * 9;
+    const float* Tb = pose_T + b * M * 3;
+    unsigned* img = (unsigned*)(out + b * out_stride + (long)v * H * W);
+
+    md_tri t = {};
+    const int f = chunk * MD_THREADS + threadIdx.x;
+    if (f < F) {
+        float ax, ay, az, bx, by, bz, qx, qy, qz;
+        const bool ok0 = md_vertex(verts, vert_part, NV, M, Rb, Tb, cam, faces[3L * f], ax, ay, az);
+        const bool ok1 = md_vertex(verts, vert_part, NV, M, Rb, Tb, cam, faces[3L * f + 1], bx, by, bz);
+        const bool ok2 = md_vertex(verts, vert_part, NV, M, Rb, Tb, cam, faces[3L * f + 2], qx, qy, qz);
+        if (ok0 && ok1 && ok2) {
+            t.n0x = md_cross(by, qz, bz, qy), t.n0y = md_cross(bz, qx, bx, qz), t.n0z = md_cross(bx, qy, by, qx);   // p1 x p2
+            t.n1x = md_cross(qy, az, qz, ay), t.n1y = md_cross(qz, ax, qx, az), t.n1z = md_cross(qx, ay, qy, ax);   // p2 x p0
+            t.n2x = md_cross(ay, bz, az, by), t.n2y = md_cross(az, bx, ax, bz), t.n2z = md_cross(ax, by, ay, bx);   // p0 x p1
+            t.z0 = az, t.z1 = bz, t.z2 = qz;
+            float ulo = 0.f, uhi = (float)(W - 1), vlo = 0.f, vhi = (float)(H - 1);
+            if (az > near && bz > near && qz > near) {       // else: the whole image
+                const float u0 = ax / az * fx + cx, u1 = bx / bz * fx + cx, u2 = qx / qz * fx + cx;
+                const float v0 = ay / az * fy + cy, v1 = by / bz * fy + cy, v2 = qy / qz * fy + cy;
+                ulo = fmaxf(floorf(fminf(fminf(u0, u1), u2)) - 1.f, ulo);
+                uhi = fminf(ceilf(fmaxf(fmaxf(u0, u1), u2)) + 1.f, uhi);
+                vlo = fmaxf(floorf(fminf(fminf(v0, v1), v2)) - 1.f, vlo);
+                vhi = fminf(ceilf(fmaxf(fmaxf(v0, v1), v2)) + 1.f, vhi);
+            }
+            if (ulo <= uhi && vlo <= vhi) {                  // all four lie in [0, W - 1] x [0, H - 1] here (a NaN fails the test)
+                t.x0 = (int)ulo, t.y0 = (int)vlo;
+                t.bw = (int)uhi - t.x0 + 1;
+                t.cnt = t.bw * ((int)vhi - t.y0 + 1);
+            }
+        }
+    }
+    __syncthreads();                                         // md_tab is complete
+
+    const float* tdx = md_tab;
+    const float* tdy = md_tab + W;
+    const int lane = threadIdx.x & (PM_WAVE - 1);
+    unsigned long long big = __ballot(t.cnt > MD_WAVE_BOX);
+    while (big) {
+        const int l = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)big) - 1);
+        big &= big - 1;
+        md_tri s;
+        s.n0x = md_bcast(t.n0x, l), s.n0y = md_bcast(t.n0y, l), s.n0z = md_bcast(t.n0z, l);
+        s.n1x = md_bcast(t.n1x, l), s.n1y = md_bcast(t.n1y, l), s.n1z = md_bcast(t.n1z, l);
+        s.n2x = md_bcast(t.n2x, l), s.n2y = md_bcast(t.n2y, l), s.n2z = md_bcast(t.n2z, l);
+        s.z0 = md_bcast(t.z0, l), s.z1 = md_bcast(t.z1, l), s.z2 = md_bcast(t.z2, l);
+        s.x0 = __builtin_amdgcn_readlane(t.x0, l), s.y0 = __builtin_amdgcn_readlane(t.y0, l);
+        s.bw = __builtin_amdgcn_readlane(t.bw, l), s.cnt = __builtin_amdgcn_readlane(t.cnt, l);
+        for (int i = lane; i < s.cnt; i += PM_WAVE) {
+            const int rr = i / s.bw;
+            const int r = s.y0 + rr, c = s.x0 + (i - rr * s.bw);
+            md_pixel(s, tdx[c], tdy[r], near, far, img + (long)r * W + c);
+        }
+    }
+    if (t.cnt > 0 && t.cnt <= MD_WAVE_BOX) {
+        const int bh = t.cnt / t.bw;
+        for (int rr = 0; rr < bh; ++rr) {
+            const int r = t.y0 + rr;
+            const float dy = tdy[r];
+            for (int cc = 0; cc < t.bw; ++cc) md_pixel(t, tdx[t.x0 + cc], dy, near, far, img + (long)r * W + t.x0 + cc);
+        }
+    }
+}
+
+extern "C" int pm_mesh_depth_render_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F,
+                                        const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V,
+                                        float fx, float fy, float cx, float cy, int H, int W, float near, float far, float* out,
+                                        long out_stride, void* stream) {
+    PM_REQUIRE(verts && vert_part && faces && pose_R && pose_T && cam_pose && out);
+    PM_REQUIRE(NV >= 1 && F >= 1 && B >= 1 && M >= 1 && V >= 1 && H >= 1 && W >= 1);
+    PM_REQUIRE(near > 0.f && far > near);                    // a NaN fails either
+    PM_REQUIRE((long)W + H <= MD_MAX_TAB);
+    const long n = (long)V * H * W;
+    PM_REQUIRE(out_stride >= n);
+    const int chunks = (F + MD_THREADS - 1) / MD_THREADS;
+    const long blocks = (long)chunks * V * B;
+    PM_REQUIRE(blocks < (1L << 31) && (long)H * W < (1L << 31));
+    const long total = n * B;
+    const long fill_blocks = (total + MD_THREADS - 1) / MD_THREADS;
+    hipLaunchKernelGGL(mesh_depth_fill_kernel, dim3((unsigned)(fill_blocks < (1L << 20) ? fill_blocks : (1L << 20))),
+                       dim3(MD_THREADS), 0, pm_stream(stream), out, out_stride, n, total, far);
+    PM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mesh_depth_raster_kernel, dim3((unsigned)blocks), dim3(MD_THREADS), (size_t)(W + H) * sizeof(float),
+                       pm_stream(stream), verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, V, chunks, fx, fy, cx, cy,
+                       H, W, near, far, out, out_stride);
+    PM_CHECK_LAUNCH();
+    return PM_OK;
+}

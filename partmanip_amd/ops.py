@@ -1344,6 +1344,49 @@ def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None):
     return out
 
 
+def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h, im_w, near=0.01, far=100.0, out=None):
+    """Depth images of the posed part meshes (pm_mesh_depth_render_f32): verts (NV, 3) canonical vertices of all parts, vert_part (NV)
+    int32, faces (F, 3) int32 into verts, pose_R (B, M, 3, 3), pose_T (B, M, 3), cam_pose (V, 4, 4) camera->world (camera looks along
+    +z, x right, y down).  out: None (a fresh (B, V h w)) or a 2-D float32 view (B, >= V h w) with unit inner stride -- columns past
+    V h w are left alone.  Returns out; out[b, (v h + r) w + c] = z-depth of the nearest surface through pixel (r, c) of view v, `far`
+    where nothing is hit; the fp32 arithmetic is fixed (include/partmanip_hip.h), so the bits repeat."""
+    _req(verts, vert_part, faces, pose_R, pose_T, cam_pose, out)
+    for t_, name in ((verts, "verts"), (pose_R, "pose_R"), (pose_T, "pose_T"), (cam_pose, "cam_pose")):
+        _f32c(t_, name)
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
+        raise ValueError(f"verts: expected (NV > 0, 3), got {tuple(verts.shape)}")
+    NV = verts.shape[0]
+    if vert_part.dtype != torch.int32 or not vert_part.is_contiguous() or tuple(vert_part.shape) != (NV,):
+        raise ValueError(f"vert_part: expected a contiguous int32 tensor ({NV},), got {vert_part.dtype} {tuple(vert_part.shape)}")
+    if faces.dtype != torch.int32 or not faces.is_contiguous() or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+        raise ValueError(f"faces: expected a contiguous int32 tensor (F > 0, 3), got {faces.dtype} {tuple(faces.shape)}")
+    if pose_R.dim() != 4 or tuple(pose_R.shape[2:]) != (3, 3) or pose_R.shape[0] == 0 or pose_R.shape[1] == 0:
+        raise ValueError(f"pose_R: expected (B, M, 3, 3), got {tuple(pose_R.shape)}")
+    B, M = pose_R.shape[0], pose_R.shape[1]
+    if tuple(pose_T.shape) != (B, M, 3):
+        raise ValueError(f"pose_T: expected ({B}, {M}, 3), got {tuple(pose_T.shape)}")
+    if cam_pose.dim() != 3 or tuple(cam_pose.shape[1:]) != (4, 4) or cam_pose.shape[0] == 0:
+        raise ValueError(f"cam_pose: expected (V > 0, 4, 4), got {tuple(cam_pose.shape)}")
+    V, im_h, im_w = cam_pose.shape[0], int(im_h), int(im_w)
+    if im_h < 1 or im_w < 1:
+        raise ValueError(f"image size: expected positive im_h and im_w, got {im_h} x {im_w}")
+    if not (near > 0 and far > near):
+        raise ValueError(f"clip planes: expected 0 < near < far, got near = {near}, far = {far}")
+    n = V * im_h * im_w
+    if out is None:
+        out = torch.empty(B, n, dtype=torch.float32, device=pose_R.device)
+    ldo = _rows(out, "out")
+    if out.shape[0] != B or out.shape[1] < n or (B > 1 and ldo < n):
+        raise ValueError(f"out: expected a ({B}, >= {n}) view with row stride >= {n}, got {tuple(out.shape)} {out.stride()}")
+    if any(t_.device != pose_R.device for t_ in (verts, vert_part, faces, pose_T, cam_pose, out)):
+        raise ValueError("mesh_depth_render: all tensors must live on one device")
+    with TIMER.bracket("mesh_depth_render"):
+        check(lib.pm_mesh_depth_render_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], _ptr(pose_R), _ptr(pose_T),
+                                           B, M, _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w,
+                                           float(near), float(far), _ptr(out), max(ldo, n), _stream()), "pm_mesh_depth_render_f32")
+    return out
+
+
 def _vec(t_, name, n, dtype=torch.float32):
     if t_.dtype != dtype or not t_.is_contiguous() or t_.numel() != n:
         raise ValueError(f"{name}: expected a contiguous {dtype} tensor of {n} elements, got {t_.dtype} {tuple(t_.shape)}")
