@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 159 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 160 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -694,6 +694,41 @@ int pm_open_drawer_reset_f32(const uint8_t* reset, const float* pos_act, const i
                              int random_reset, const float* u, float t_range, float r_range, const float* default_dof_pos,
                              const float* joint_lo, float* root, float* dof_state_all, long D, float* pos_act_all,
                              float* robot_dof_state, float* part_dof_state, void* stream);
+
+/* ------------------------------------------------------------------ kinematic articulation (a stand-in for the simulator's robot)
+ * The producer of the three tensors the task steps start from, for one robot per environment: position targets in, dof_state,
+ * rigid-body rows and the Jacobian out, in one launch (csrc/articulation.hip).  Kinematics only: no dynamics, contact or gravity.
+ * The tree (partmanip_amd/urdf.py; bodies ordered so that a parent precedes its children, DOFs numbered in body order):
+ *   parent, jtype, dof (nb) int32: the parent body (-1: the root, which hangs off base_pose), 0 fixed / 1 revolute / 2 prismatic,
+ *   the joint's DOF (-1 for a fixed joint);  origin_q (nb, 4) unit (x, y, z, w), origin_t (nb, 3): the joint origin in the parent's
+ *   frame;  axis (nb, 3) unit, in the joint's frame;  anc_mask (nb) 64-bit: bit d set where DOF d lies on the body's path to the root.
+ * dof_lo, dof_hi (nd);  vmax (nd) or NULL (exact tracking);  base_pose: 7 floats per environment, position and quaternion (x, y, z, w),
+ * base_stride floats apart (0: one pose for all); the quaternion is divided by its norm.
+ * dof_state: rows of (q, qd), dof_rows rows in all; environment e's nd rows start at row dof_row0[e], or at e * dof_stride with
+ * dof_row0 NULL.  rigid_body: rows of 13, rb_rows in all, environment e's nb rows from rb_row0[e] or e * rb_stride.  So the robot may
+ * sit inside a wider (N, nb_total, 13) tensor or inside flat (B, 13) / (D, 2) tensors; no other row is touched.  An environment whose
+ * rows would not lie inside [0, rows) is computed as NaN and stores no dof_state / rigid_body row.
+ * Per environment, with targets (N, nd) (row stride tgt_stride) given, dof_state is updated in place:
+ *   q' = q + clamp(t - q, -vmax dt, vmax dt) (vmax NULL: q' = t), then q' = clamp(q', dof_lo, dof_hi);  qd' = (q' - q) / dt
+ *   reset (N) bytes, where given and set: q' = clamp(t, dof_lo, dof_hi), qd' = 0, whatever vmax is
+ *   clamp passes a NaN through.  targets NULL: dof_state is only read (q' = q, qd' = qd): pure forward kinematics.
+ * Body frame = parent o origin o joint, in quaternion arithmetic (the chain of frames in float64, rounded to float32 once per body),
+ * each body's quaternion divided by its norm; the joint is a
+ * rotation by q' about axis (revolute) or a translation by q' axis (prismatic).
+ * jac (N, nb - 1, 6, nd): the world-frame geometric Jacobian at the body origin, row l = body l + 1, rows 0-2 linear, 3-5 angular;
+ * column d is exactly 0 unless bit d of the body's anc_mask is set, else (a x (p_body - p_joint), a) for a revolute DOF and (a, 0)
+ * for a prismatic one, a = the joint axis in the world.  rigid_body row = position 3, quaternion 4, linear velocity 3 = J[:3] qd',
+ * angular velocity 3 = J[3:] qd' (the root body: 0).  rigid_body and jac may each be NULL (skipped).
+ * An environment's outputs depend on its own rows only and do not depend on N.  No synchronisation, allocation or atomics;
+ * stream-ordered.  PM_EINVAL: a NULL required pointer (every table, the limits, base_pose, dof_state), N < 1, nb or nd outside
+ * [1, 64], a stride below its row width (base_stride other than 0 below 7, tgt_stride < nd, rb_stride < nb, dof_stride < nd), rows
+ * that N environments at the given stride would not fit, dt <= 0 with targets.  The tables' contents are the caller's to validate. */
+int pm_articulation_step_f32(const int32_t* parent, const int32_t* jtype, const int32_t* dof, const float* origin_q,
+                             const float* origin_t, const float* axis, const uint64_t* anc_mask, const float* dof_lo,
+                             const float* dof_hi, const float* vmax, float dt, const float* base_pose, long base_stride,
+                             float* dof_state, long dof_rows, const float* targets, long tgt_stride, const uint8_t* reset,
+                             const int32_t* rb_row0, long rb_stride, long rb_rows, const int32_t* dof_row0, long dof_stride, int N,
+                             int nb, int nd, float* rigid_body, float* jac, void* stream);
 
 /* ------------------------------------------------------------------ K15 fused set-abstraction level
  * One PointNet++ SA level (north_star; not in the reference snapshot, README.md:23,30) as one forward and

@@ -1564,6 +1564,80 @@ def franka_control(actions, dof_state, jac, jl, jr, dof_lo, dof_hi, default_dof_
     return pos_act
 
 
+def _rows_of(t_, name, width, N, n, row0):
+    """(rows in all, rows per environment) of a simulator tensor that holds n rows of `width` per environment: dense (N, >= n, width)
+    with row0 None, flat (rows, width) with the (N) int32 row table row0."""
+    _f32c(t_, name)
+    if row0 is None:
+        if t_.dim() != 3 or t_.shape[0] != N or t_.shape[1] < n or t_.shape[2] != width:
+            raise ValueError(f"{name}: expected ({N}, >= {n}, {width}), got {tuple(t_.shape)}")
+        return N * t_.shape[1], t_.shape[1]
+    if t_.dim() != 2 or t_.shape[1] != width or t_.shape[0] < n:
+        raise ValueError(f"{name}: expected (rows >= {n}, {width}) with a row table, got {tuple(t_.shape)}")
+    _vec(row0, f"{name}'s row table", N, torch.int32)
+    return t_.shape[0], 0
+
+
+def articulation_step(parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, base_pose, dof_state, targets=None,
+                      reset=None, vmax=None, dt=0.0, rigid_body=None, jac=None, rb_row0=None, dof_row0=None):
+    """One step of the kinematic articulation in one launch (pm_articulation_step_f32, include/partmanip_hip.h).  The tree tables
+    (nb) / (nb, 4) / (nb, 3) and anc_mask (nb) int64 come from kinematics.Articulation, which validates them; dof_lo, dof_hi, vmax
+    (nd); base_pose (7) or (N, 7); dof_state (N, >= nd, 2), or flat (D, 2) with dof_row0 (N) int32, updated in place when targets
+    (N, nd) is given (reset (N) bool / uint8 then snaps an environment to its clamped target); rigid_body (N, >= nb, 13) or flat
+    (B, 13) with rb_row0; jac (N, nb - 1, 6, nd).  rigid_body and jac may be None (skipped)."""
+    tensors = (parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, base_pose, dof_state, targets, reset, vmax,
+               rigid_body, jac, rb_row0, dof_row0)
+    _req(*tensors)
+    nb, nd = parent.numel(), dof_lo.numel()
+    if not (1 <= nb <= 64 and 1 <= nd <= 64):
+        raise ValueError(f"articulation_step: {nb} bodies / {nd} DOFs outside [1, 64]")
+    for t_, name in ((parent, "parent"), (jtype, "jtype"), (dof, "dof")):
+        _vec(t_, name, nb, torch.int32)
+    _vec(anc_mask, "anc_mask", nb, torch.int64)
+    _shape_f32c(origin_q, "origin_q", (nb, 4))
+    _shape_f32c(origin_t, "origin_t", (nb, 3))
+    _shape_f32c(axis, "axis", (nb, 3))
+    _vec(dof_hi, "dof_hi", nd)
+    _vec(dof_lo, "dof_lo", nd)
+    if vmax is not None:
+        _vec(vmax, "vmax", nd)
+    _f32c(base_pose, "base_pose")
+    if base_pose.dim() == 1 and base_pose.numel() == 7:
+        N, lbase = None, 0
+    elif base_pose.dim() == 2 and base_pose.shape[1] == 7 and base_pose.shape[0] > 0:
+        N, lbase = base_pose.shape[0], 7
+    else:
+        raise ValueError(f"base_pose: expected (7) or (N, 7), got {tuple(base_pose.shape)}")
+    if dof_row0 is not None:
+        N = dof_row0.numel() if N is None else N
+    elif dof_state.dim() == 3:
+        N = dof_state.shape[0] if N is None else N
+    if not N:
+        raise ValueError(f"dof_state: expected (N, >= {nd}, 2) or flat (D, 2) with dof_row0, got {tuple(dof_state.shape)}")
+    dof_rows, ldd = _rows_of(dof_state, "dof_state", 2, N, nd, dof_row0)
+    rb_rows, ldr = _rows_of(rigid_body, "rigid_body", 13, N, nb, rb_row0) if rigid_body is not None else (0, 0)
+    if jac is not None:
+        _shape_f32c(jac, "jac", (N, nb - 1, 6, nd))
+    ldt = 0
+    if targets is not None:
+        ldt = _row_view(targets, "targets", N, nd)
+        if not float(dt) > 0:
+            raise ValueError(f"dt: expected a positive step with targets, got {dt}")
+    elif reset is not None:
+        raise ValueError("reset is given without targets")
+    if reset is not None:
+        _flags(reset, "reset", N)
+    dev = dof_state.device
+    if any(t_ is not None and t_.device != dev for t_ in tensors):
+        raise ValueError("articulation_step: all tensors must live on one device")
+    with TIMER.bracket("articulation_step"):
+        check(lib.pm_articulation_step_f32(_ptr(parent), _ptr(jtype), _ptr(dof), _ptr(origin_q), _ptr(origin_t), _ptr(axis),
+                                           _ptr(anc_mask), _ptr(dof_lo), _ptr(dof_hi), _ptr(vmax), float(dt), _ptr(base_pose), lbase,
+                                           _ptr(dof_state), dof_rows, _ptr(targets), ldt, _ptr(reset), _ptr(rb_row0), ldr, rb_rows,
+                                           _ptr(dof_row0), ldd, N, nb, nd, _ptr(rigid_body), _ptr(jac), _stream()),
+              "pm_articulation_step_f32")
+
+
 def _index_table(t_, name, N):
     if t_.dtype != torch.int32 or t_.dim() != 2 or t_.shape[0] != N or not t_.is_contiguous():
         raise ValueError(f"{name}: expected a contiguous int32 tensor ({N}, width), got {t_.dtype} {tuple(t_.shape)}")
