@@ -69,6 +69,12 @@ __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, 
 __device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
 __device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
 
+// One coordinate of a canonical point x under a part's pose, ((x0 r0 + x1 r1) + x2 r2) + t with (r0, r1, r2) a row of R and t that
+// row's translation: the association the posed cloud (mesh_pc.hip) and the depth image (mesh_depth.hip) are specified bit for bit from.
+__device__ __forceinline__ float posed_coord(float x0, float x1, float x2, float r0, float r1, float r2, float t) {
+    return add_rn(add_rn(add_rn(mul_rn(x0, r0), mul_rn(x1, r1)), mul_rn(x2, r2)), t);
+}
+
 // ---- tanh -------------------------------------------------------------------------------
 // fp32 tanh as the odd rational x * P(x^2) / Q(x^2) (degree 13 / 6 minimax, the coefficients of Eigen's float
 // tanh), |x| clamped to 7.905 where it rounds to 1: branch-free, one transcendental (v_rcp_f32 + one Newton

@@ -2,7 +2,7 @@
 // the image from the simulator's camera sensors; here it is rendered from the same (pose_R, pose_T) that query_pc and query_tsdf take).
 //
 // Definition (include/partmanip_hip.h has it in full).  All arithmetic is fp32, every product, sum and difference rounded on its
-// own, divisions IEEE.  Vertex x of part j: xw = ((x0 R[j,0] + x1 R[j,1]) + x2 R[j,2]) + T[j] (mesh_pc.hip's association), d = xw -
+// own, divisions IEEE.  Vertex x of part j: xw = ((x0 R[j,0] + x1 R[j,1]) + x2 R[j,2]) + T[j] (common.h's posed_coord, shared with mesh_pc.hip), d = xw -
 // C[:,3], p_k = (d0 C[0,k] + d1 C[1,k]) + d2 C[2,k] (the reference's bmm(world - t, R), depth2tsdf.py:47).  Triangle (p0, p1, p2):
 // n0 = p1 x p2, n1 = p2 x p0, n2 = p0 x p1.  Pixel (row r, column c): dx = (float(c) - cx) / fx, dy = (float(r) - cy) / fy, w_i = (dx
 // n_i.x + dy n_i.y) + n_i.z, s = (w0 + w1) + w2.  Hit iff the w_i are all >= 0 or all <= 0, s != 0 and z = ((w0 p0.z + w1 p1.z) + w2
@@ -80,8 +80,7 @@ __device__ __forceinline__ bool md_vertex(const float* __restrict__ verts, const
     float d[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        const float xw = add_rn(add_rn(add_rn(mul_rn(x0, R[3 * j]), mul_rn(x1, R[3 * j + 1])), mul_rn(x2, R[3 * j + 2])), T[j]);
-        d[j] = sub_rn(xw, cam.c[4 * j + 3]);
+        d[j] = sub_rn(posed_coord(x0, x1, x2, R[3 * j], R[3 * j + 1], R[3 * j + 2], T[j]), cam.c[4 * j + 3]);
     }
     px = add_rn(add_rn(mul_rn(d[0], cam.c[0]), mul_rn(d[1], cam.c[4])), mul_rn(d[2], cam.c[8]));
     py = add_rn(add_rn(mul_rn(d[0], cam.c[1]), mul_rn(d[1], cam.c[5])), mul_rn(d[2], cam.c[9]));

@@ -4,7 +4,7 @@
 // parts' poses (bmm over (b*m, p, 3): 12 x 1024 points per environment, 600 MB written at 4096 environments) and then gathers a
 // random 1/12 of the result through a host index.  Here only the selected points are ever computed:
 //     q = sel[k], p = part_of[q], x = pts[q],  out[b, k, j] = ((x0 R[b,p,j,0] + x1 R[b,p,j,1]) + x2 R[b,p,j,2]) + T[b,p,j]
-// in fp32, every product and sum rounded on its own (mul_rn / add_rn), so the bits are defined and repeat from call to call.
+// in fp32, every product and sum rounded on its own (common.h's posed_coord), so the bits are defined and repeat from call to call.
 //
 // Shape: a memory-bound gather whose only large stream is the output (12 B K bytes).  One lane owns one output FLOAT e = 3 k + j of
 // a row, not one point: the 64 lanes of a wave then store 64 consecutive dwords (256 contiguous bytes) whatever the row's
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(MP_THREADS) void mesh_pc_kernel(const float* __rest
                     const float* R = pose_R + (b * M * 3 + pj) * 3;
                     r0 = R[0], r1 = R[1], r2 = R[2], t = pose_T[b * M * 3 + pj];
                 }
-                v = add_rn(add_rn(add_rn(mul_rn(pt[u].x0, r0), mul_rn(pt[u].x1, r1)), mul_rn(pt[u].x2, r2)), t);
+                v = posed_coord(pt[u].x0, pt[u].x1, pt[u].x2, r0, r1, r2, t);
             }
             row[e] = v;
         }

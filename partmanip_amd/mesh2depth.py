@@ -16,13 +16,10 @@ project's own and have not been checked against the simulator: `near` defaults t
 and culling is two-sided, both faces of a triangle count (for closed meshes the nearest hit is a front face either way).  Colour,
 segmentation masks and sensor noise are out of scope.
 """
-import os
-
 import numpy as np
 import torch
 
 from . import meshio, ops
-from .mesh2pc import FRANKA_MESH_DIR, FRANKA_MESHES, OBJ_MESH_PATH
 
 
 class DepthFromMesh:
@@ -52,9 +49,7 @@ class DepthFromMesh:
         self.num_view = int(pose.shape[0])
         self.cam_pose = torch.from_numpy(np.ascontiguousarray(pose)).to(self.device)
         if meshes is None:
-            paths = [os.path.join(asset_root, FRANKA_MESH_DIR, name) for name in FRANKA_MESHES]
-            paths.append(os.path.join(asset_root, OBJ_MESH_PATH))
-            meshes = [meshio.load_mesh(path) for path in paths]
+            meshes = [meshio.load_mesh(path) for path in meshio.scene_mesh_paths(asset_root)]
         if len(meshes) == 0:
             raise ValueError("meshes: at least one part is needed")
         verts, part, faces, base = [], [], [], 0
@@ -78,19 +73,12 @@ class DepthFromMesh:
         nearest surface through every pixel centre, `far` where nothing is hit.
         out: None, or a 2-D float32 view (b, >= V h w) with unit inner stride (e.g. the head of a depth_img observation buffer); the
         result is then a view of its first V h w columns."""
-        m = self.part_num
-        if pose_R.dim() != 4 or tuple(pose_R.shape[1:]) != (m, 3, 3) or pose_R.shape[0] == 0:
-            raise ValueError(f"pose_R: expected (b, {m}, 3, 3), got {tuple(pose_R.shape)}")
-        b = pose_R.shape[0]
-        if tuple(pose_T.shape) != (b, m, 3):
-            raise ValueError(f"pose_T: expected ({b}, {m}, 3), got {tuple(pose_T.shape)}")
-        if pose_R.dtype != torch.float32 or pose_T.dtype != torch.float32:
-            raise ValueError(f"poses: expected float32, got {pose_R.dtype} and {pose_T.dtype}")
+        b, _ = ops.check_poses(pose_R, pose_T, self.part_num)
+        n = self.num_view * self.im_h * self.im_w
+        if out is not None:
+            ops._out_rows(out, b, n)                                                           # a bad view is reported before the device
         ops._req(pose_R, pose_T, out, self.verts)
         pose_R, pose_T = pose_R.contiguous(), pose_T.contiguous()
-        n = self.num_view * self.im_h * self.im_w
-        if out is not None and (out.dim() != 2 or out.shape[0] != b or out.shape[1] < n):
-            raise ValueError(f"out: expected a 2-D view ({b}, >= {n}), got {tuple(out.shape)}")
         res = ops.mesh_depth_render(self.verts, self.vert_part, self.faces, pose_R, pose_T, self.cam_pose, self.fx, self.fy, self.cx,
                                     self.cy, self.im_h, self.im_w, self.near, self.far, out)
         return res[:, :n].unflatten(1, (self.num_view, self.im_h, self.im_w))

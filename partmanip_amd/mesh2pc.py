@@ -13,16 +13,11 @@ and with `out=` writes them straight into the left part of an (N, 3 * num_points
 One copy of the canonical points lives on the device (`part_pc (m, p, 3)`, its flat view `pts (m p, 3)`, `part_of (m p)`); the
 reference's per-environment repeat is the property `all_pc`, materialised on demand.
 """
-import os
-
 import numpy as np
 import torch
 
 from . import meshio, ops
 
-FRANKA_MESH_DIR = os.path.join("assets", "franka_description", "meshes", "visual")            # mesh2pc.py:20, 51
-FRANKA_MESHES = [f"link{i}.obj" for i in range(8)] + ["hand.obj", "finger.stl", "finger.stl"]   # mesh2pc.py:44-48
-OBJ_MESH_PATH = os.path.join("assets", "objs", "cube", "cube.obj")                            # mesh2pc.py:24
 SELECT_MODES = ("random", "all", "fps")
 
 
@@ -57,9 +52,7 @@ class PCfromMesh:
                 raise ValueError(f"part_pcs: expected (m, p, 3), got {pcs.shape}")
         else:
             if meshes is None:
-                paths = [os.path.join(asset_root, FRANKA_MESH_DIR, name) for name in FRANKA_MESHES]
-                paths.append(os.path.join(asset_root, OBJ_MESH_PATH))
-                meshes = [meshio.load_mesh(path) for path in paths]
+                meshes = [meshio.load_mesh(path) for path in meshio.scene_mesh_paths(asset_root)]
             if len(meshes) == 0:
                 raise ValueError("meshes: at least one part is needed")
             pcs = np.stack([self.load_pc_from_mesh(v, f, i) for i, (v, f) in enumerate(meshes)])
@@ -90,25 +83,24 @@ class PCfromMesh:
         covered as densely as small ones.  sel: an int32 device tensor (K,) or (b, K) used instead (no host generator, no copy).
         out: None, or a 2-D float32 view (b, >= 3K) with unit inner stride (e.g. obs[:, :3K] of an observation buffer); the result
         is then a view of its first 3K columns.  `last_sel` holds the selection that was used (None for 'all')."""
-        m, Q = self.part_num, self.pts.shape[0]
-        if pose_R.dim() != 4 or tuple(pose_R.shape[1:]) != (m, 3, 3) or pose_R.shape[0] == 0:
-            raise ValueError(f"pose_R: expected (b, {m}, 3, 3), got {tuple(pose_R.shape)}")
-        b = pose_R.shape[0]
-        if tuple(pose_T.shape) != (b, m, 3):
-            raise ValueError(f"pose_T: expected ({b}, {m}, 3), got {tuple(pose_T.shape)}")
-        if pose_R.dtype != torch.float32 or pose_T.dtype != torch.float32:
-            raise ValueError(f"poses: expected float32, got {pose_R.dtype} and {pose_T.dtype}")
-        ops._req(pose_R, pose_T, sel, out, self.pts)
-        pose_R, pose_T = pose_R.contiguous(), pose_T.contiguous()
+        Q = self.pts.shape[0]
+        b, _ = ops.check_poses(pose_R, pose_T, self.part_num)
         if sel is not None:
             if sel.dtype != torch.int32 or sel.dim() not in (1, 2) or (sel.dim() == 2 and sel.shape[0] != b) or sel.shape[-1] == 0:
                 raise ValueError(f"sel: expected an int32 tensor (K,) or ({b}, K), got {sel.dtype} {tuple(sel.shape)}")
+            K = sel.shape[-1]
         elif select not in SELECT_MODES:
             raise ValueError(f"select: expected one of {SELECT_MODES}, got {select!r}")
-        elif select == 'random':
+        else:
+            K = Q if select == 'all' else min(self.num_points, Q)
+        if out is not None:
+            ops._out_rows(out, b, 3 * K)                                                       # a bad view is reported before the device and any launch
+        ops._req(pose_R, pose_T, sel, out, self.pts)
+        pose_R, pose_T = pose_R.contiguous(), pose_T.contiguous()
+        if sel is None and select == 'random':
             randperm = torch.randperm(Q)
             sel = randperm[:self.num_points].to(torch.int32).to(self.device)
-        elif select == 'fps':
+        elif sel is None and select == 'fps':
             if self.num_points > Q:
                 raise ValueError(f"select='fps': num_points {self.num_points} exceeds the {Q} points of the scene")
             if self._full is None or self._full.shape[0] != b:
@@ -116,9 +108,6 @@ class PCfromMesh:
                 self._fps_ws = ops.Workspace(pose_R.device)
             ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, None, self._full)
             sel = ops.fps(self._full.view(b, Q, 3), self.num_points, self._fps_ws)
-        K = Q if sel is None else sel.shape[-1]
-        if out is not None and (out.dim() != 2 or out.shape[0] != b or out.shape[1] < 3 * K):
-            raise ValueError(f"out: expected a 2-D view ({b}, >= {3 * K}), got {tuple(out.shape)}")
         res = ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, sel, out)
         self.last_sel = sel
         return res[:, :3 * K].unflatten(1, (K, 3))

@@ -31,10 +31,7 @@ import torch
 
 from . import meshio, ops
 
-FRANKA_SDF_DIR = os.path.join("assets", "franka_description", "sdf", "visual")       # mesh2sdf.py:43,148-154
-FRANKA_PARTS = [f"link{i}" for i in range(8)] + ["hand", "finger", "finger"]       # mesh2sdf.py:142-145
 OBJ_SDF_PATH = os.path.join("assets", "objs", "cube", "sdf.npy")                     # mesh2sdf.py:48
-FRANKA_MESHES = [f"link{i}.obj" for i in range(8)] + ["hand.obj", "finger.stl", "finger.stl"]   # mesh2sdf.py:142-145
 
 
 def bake_grid_layout(vertices, trunc, voxel_size):
@@ -114,14 +111,14 @@ class TSDFfromMesh:
             self.sdf_dict_list.extend(sdf_dicts)
         else:
             self.load_franka(os.path.join(asset_root, "assets", "franka_description"))
-            self.load_sdf(os.path.join(asset_root, OBJ_SDF_PATH), os.path.join(asset_root, "assets", "objs", "cube", "cube.obj"))
+            self.load_sdf(os.path.join(asset_root, OBJ_SDF_PATH), os.path.join(asset_root, meshio.OBJ_MESH_PATH))
         self.merge_sdf_field()
 
     # ------------------------------------------------------------------------------------------------ loading
     def load_franka(self, hand_base_path):
         """Parts in the reference's order: link0..link7, hand, finger, finger (mesh2sdf.py:141-156); the mesh of a part is
         meshes/visual/<name>, its grid the same path with 'meshes' -> 'sdf' and the extension -> '.npy'."""
-        for name in FRANKA_MESHES:
+        for name in meshio.FRANKA_MESHES:
             mesh_path = os.path.join(hand_base_path, "meshes", "visual", name)
             preprocess_path = os.path.join(hand_base_path, "manifoldplus", "visual", name) if name.endswith(".obj") else None
             sdf_path = os.path.join(hand_base_path, "sdf", "visual", name[:-4] + ".npy")

@@ -17,6 +17,17 @@ import struct
 
 import numpy as np
 
+# The Franka scene's rigid parts in the reference's order (mesh2pc.py:20-24, 44-51; mesh2sdf.py:142-145): eight links, the hand, two
+# fingers (one file twice), then the object.
+FRANKA_MESH_DIR = os.path.join("assets", "franka_description", "meshes", "visual")
+FRANKA_MESHES = [f"link{i}.obj" for i in range(8)] + ["hand.obj", "finger.stl", "finger.stl"]
+OBJ_MESH_PATH = os.path.join("assets", "objs", "cube", "cube.obj")
+
+
+def scene_mesh_paths(asset_root):
+    """The mesh files of the scene's parts under `asset_root`, in part order."""
+    return [os.path.join(asset_root, FRANKA_MESH_DIR, name) for name in FRANKA_MESHES] + [os.path.join(asset_root, OBJ_MESH_PATH)]
+
 
 def load_obj(path):
     verts, faces = [], []

@@ -79,12 +79,29 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+_NO_CPU = "partmanip_amd ops run on MI355X only: got a CPU tensor (no CPU fallback exists)"
+
+
 def _req(*ts):
     for t in ts:
         if t is None:
             continue
         if not t.is_cuda:
-            raise RuntimeError("partmanip_amd ops run on MI355X only: got a CPU tensor (no CPU fallback exists)")
+            raise RuntimeError(_NO_CPU)
+
+
+def _one_device(fn, *ts):
+    """_req, and all the tensors (None entries skipped) of the wrapper `fn` on the same device; one pass, it runs on every call."""
+    dev = None
+    for t in ts:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(_NO_CPU)
+        if dev is None:
+            dev = t.device
+        elif t.device != dev:
+            raise ValueError(f"{fn}: all tensors must live on one device")
 
 
 def _f32c(t, name):
@@ -97,6 +114,32 @@ def _rows(t, name):
     if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] != 1 and t.stride(1) != 1):   # a size-1 inner dim may carry any stride
         raise ValueError(f"{name}: expected a 2-D float32 tensor with unit inner stride, got {tuple(t.shape)} {t.stride()}")
     return t.stride(0)
+
+
+def check_poses(pose_R, pose_T, M=None):
+    """The pose inputs of an observer: float32 pose_R (B > 0, M > 0, 3, 3) and pose_T (B, M, 3), with M parts when M is given.
+    Returns (B, M)."""
+    s = pose_R.shape
+    if len(s) != 4 or s[2] != 3 or s[3] != 3 or s[0] == 0 or (s[1] == 0 if M is None else s[1] != M):
+        raise ValueError(f"pose_R: expected (B, {'M' if M is None else M}, 3, 3), got {tuple(s)}")
+    if pose_T.shape != (s[0], s[1], 3):
+        raise ValueError(f"pose_T: expected ({s[0]}, {s[1]}, 3), got {tuple(pose_T.shape)}")
+    if pose_R.dtype != torch.float32 or pose_T.dtype != torch.float32:
+        raise ValueError(f"pose_R / pose_T: expected float32, got {pose_R.dtype} and {pose_T.dtype}")
+    return s[0], s[1]
+
+
+def _out_rows(out, B, n, device=None):
+    """The `out=` rule of the observers: None gives a fresh (B, n) on `device`; otherwise a 2-D float32 view (B, >= n) with unit inner
+    stride and row stride >= n.  Returns (out, the row stride to hand to C); a one-row view may carry any row stride, which counts
+    as n.  The check reads no memory, so the observer classes run it on a given `out` before they ask for the device."""
+    if out is None:
+        return torch.empty(B, n, dtype=torch.float32, device=device), n
+    s, st = out.shape, out.stride()
+    if len(s) != 2 or s[0] != B or s[1] < n or out.dtype != torch.float32 or (s[1] != 1 and st[1] != 1) or (B > 1 and st[0] < n):
+        raise ValueError(f"out: expected a float32 view ({B}, >= {n}) with unit inner stride and row stride >= {n}, got {out.dtype} "
+                         f"{tuple(s)} {st}")
+    return out, max(st[0], n)
 
 
 class Workspace:
@@ -1262,19 +1305,14 @@ def mesh_tsdf_query(fields, part_off, part_shape, part_bbox_min, part_voxel_size
     part_shape (M,3) int32, part_bbox_min (M,3), part_voxel_size (M), pose_R (B,M,3,3), pose_T (B,M,3), origin = 3 floats,
     base (res^3) or (B, res^3).  out: None (a fresh (B, res^3)) or a 2-D float32 view (B, >= res^3) with unit inner stride --
     columns past res^3 are left alone.  Returns out."""
-    _req(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, base, out)
+    _one_device("mesh_tsdf_query", fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, base, out)
     for t_, name in ((fields, "fields"), (part_bbox_min, "part_bbox_min"), (part_voxel_size, "part_voxel_size"),
                      (pose_R, "pose_R"), (pose_T, "pose_T"), (base, "base")):
         _f32c(t_, name)
     if part_off.dtype != torch.int64 or not part_off.is_contiguous():
         raise ValueError("part_off: expected a contiguous int64 tensor")
     _i32c(part_shape, "part_shape")
-    M = part_off.numel()
-    if pose_R.dim() != 4 or tuple(pose_R.shape[1:]) != (M, 3, 3):
-        raise ValueError(f"pose_R: expected (B, {M}, 3, 3), got {tuple(pose_R.shape)}")
-    B = pose_R.shape[0]
-    if tuple(pose_T.shape) != (B, M, 3):
-        raise ValueError(f"pose_T: expected ({B}, {M}, 3), got {tuple(pose_T.shape)}")
+    B, M = check_poses(pose_R, pose_T, part_off.numel())
     if tuple(part_shape.shape) != (M, 3) or tuple(part_bbox_min.shape) != (M, 3) or part_voxel_size.numel() != M:
         raise ValueError("part tables: expected part_shape (M,3), part_bbox_min (M,3), part_voxel_size (M)")
     n = int(res) ** 3
@@ -1284,19 +1322,13 @@ def mesh_tsdf_query(fields, part_off, part_shape, part_bbox_min, part_voxel_size
         per_env = 1
     else:
         raise ValueError(f"base: expected ({n},) or ({B}, {n}), got {tuple(base.shape)}")
-    if out is None:
-        out = torch.empty(B, n, dtype=torch.float32, device=pose_R.device)
-    ldo = _rows(out, "out")
-    if out.shape[0] != B or out.shape[1] < n or (B > 1 and ldo < n):
-        raise ValueError(f"out: expected a ({B}, >= {n}) view with row stride >= {n}, got {tuple(out.shape)} {out.stride()}")
-    if any(t_.device != pose_R.device for t_ in (fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_T, base, out)):
-        raise ValueError("mesh_tsdf_query: all tensors must live on one device")
+    out, ldo = _out_rows(out, B, n, pose_R.device)
     ox, oy, oz = (float(v) for v in origin)
     with TIMER.bracket("mesh_tsdf_query"):
         check(lib.pm_mesh_tsdf_query_f32(_ptr(fields), _ptr(part_off), _ptr(part_shape), _ptr(part_bbox_min), _ptr(part_voxel_size),
                                          _ptr(pose_R), _ptr(pose_T), B, M, int(p0), M if p1 is None else int(p1), int(res),
                                          float(vox_size), ox, oy, oz, float(sdf_trunc), _ptr(base), per_env, _ptr(out),
-                                         max(ldo, n), 1 if brick_skip else 0, _stream()), "pm_mesh_tsdf_query_f32")
+                                         ldo, 1 if brick_skip else 0, _stream()), "pm_mesh_tsdf_query_f32")
     return out
 
 
@@ -1305,7 +1337,7 @@ def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None):
     pose_T (B, M, 3); sel: None (every point, K = Q), (K) int32 shared by all environments or (B, K) int32 with unit inner stride.
     out: None (a fresh (B, 3K)) or a 2-D float32 view (B, >= 3K) with unit inner stride -- columns past 3K are left alone.
     Returns out; out[b, 3k + j] = coordinate j of point pts[sel[.., k]] under the pose of its part in environment b."""
-    _req(pts, part_of, pose_R, pose_T, sel, out)
+    _one_device("mesh_pc_query", pts, part_of, pose_R, pose_T, sel, out)
     for t_, name in ((pts, "pts"), (pose_R, "pose_R"), (pose_T, "pose_T")):
         _f32c(t_, name)
     if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
@@ -1313,11 +1345,7 @@ def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None):
     Q = pts.shape[0]
     if part_of.dtype != torch.int32 or not part_of.is_contiguous() or tuple(part_of.shape) != (Q,):
         raise ValueError(f"part_of: expected a contiguous int32 tensor ({Q},), got {part_of.dtype} {tuple(part_of.shape)}")
-    if pose_R.dim() != 4 or tuple(pose_R.shape[2:]) != (3, 3) or pose_R.shape[0] == 0 or pose_R.shape[1] == 0:
-        raise ValueError(f"pose_R: expected (B, M, 3, 3), got {tuple(pose_R.shape)}")
-    B, M = pose_R.shape[0], pose_R.shape[1]
-    if tuple(pose_T.shape) != (B, M, 3):
-        raise ValueError(f"pose_T: expected ({B}, {M}, 3), got {tuple(pose_T.shape)}")
+    B, M = check_poses(pose_R, pose_T)
     if sel is None:
         K, sel_stride = Q, 0
     else:
@@ -1330,17 +1358,10 @@ def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None):
             sel_stride = sel.stride(0) if B > 1 else K
             if sel.shape[0] != B or sel_stride < K:
                 raise ValueError(f"sel: expected ({B}, K) with row stride >= K, got {tuple(sel.shape)} {sel.stride()}")
-    n = 3 * K
-    if out is None:
-        out = torch.empty(B, n, dtype=torch.float32, device=pose_R.device)
-    ldo = _rows(out, "out")
-    if out.shape[0] != B or out.shape[1] < n or (B > 1 and ldo < n):
-        raise ValueError(f"out: expected a ({B}, >= {n}) view with row stride >= {n}, got {tuple(out.shape)} {out.stride()}")
-    if any(t_ is not None and t_.device != pose_R.device for t_ in (pts, part_of, pose_T, sel, out)):
-        raise ValueError("mesh_pc_query: all tensors must live on one device")
+    out, ldo = _out_rows(out, B, 3 * K, pose_R.device)
     with TIMER.bracket("mesh_pc_query"):
         check(lib.pm_mesh_pc_query_f32(_ptr(pts), _ptr(part_of), Q, _ptr(pose_R), _ptr(pose_T), B, M, _ptr(sel), sel_stride, K,
-                                       _ptr(out), max(ldo, n), _stream()), "pm_mesh_pc_query_f32")
+                                       _ptr(out), ldo, _stream()), "pm_mesh_pc_query_f32")
     return out
 
 
@@ -1350,7 +1371,7 @@ def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy,
     +z, x right, y down).  out: None (a fresh (B, V h w)) or a 2-D float32 view (B, >= V h w) with unit inner stride -- columns past
     V h w are left alone.  Returns out; out[b, (v h + r) w + c] = z-depth of the nearest surface through pixel (r, c) of view v, `far`
     where nothing is hit; the fp32 arithmetic is fixed (include/partmanip_hip.h), so the bits repeat."""
-    _req(verts, vert_part, faces, pose_R, pose_T, cam_pose, out)
+    _one_device("mesh_depth_render", verts, vert_part, faces, pose_R, pose_T, cam_pose, out)
     for t_, name in ((verts, "verts"), (pose_R, "pose_R"), (pose_T, "pose_T"), (cam_pose, "cam_pose")):
         _f32c(t_, name)
     if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
@@ -1360,11 +1381,7 @@ def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy,
         raise ValueError(f"vert_part: expected a contiguous int32 tensor ({NV},), got {vert_part.dtype} {tuple(vert_part.shape)}")
     if faces.dtype != torch.int32 or not faces.is_contiguous() or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
         raise ValueError(f"faces: expected a contiguous int32 tensor (F > 0, 3), got {faces.dtype} {tuple(faces.shape)}")
-    if pose_R.dim() != 4 or tuple(pose_R.shape[2:]) != (3, 3) or pose_R.shape[0] == 0 or pose_R.shape[1] == 0:
-        raise ValueError(f"pose_R: expected (B, M, 3, 3), got {tuple(pose_R.shape)}")
-    B, M = pose_R.shape[0], pose_R.shape[1]
-    if tuple(pose_T.shape) != (B, M, 3):
-        raise ValueError(f"pose_T: expected ({B}, {M}, 3), got {tuple(pose_T.shape)}")
+    B, M = check_poses(pose_R, pose_T)
     if cam_pose.dim() != 3 or tuple(cam_pose.shape[1:]) != (4, 4) or cam_pose.shape[0] == 0:
         raise ValueError(f"cam_pose: expected (V > 0, 4, 4), got {tuple(cam_pose.shape)}")
     V, im_h, im_w = cam_pose.shape[0], int(im_h), int(im_w)
@@ -1372,18 +1389,11 @@ def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy,
         raise ValueError(f"image size: expected positive im_h and im_w, got {im_h} x {im_w}")
     if not (near > 0 and far > near):
         raise ValueError(f"clip planes: expected 0 < near < far, got near = {near}, far = {far}")
-    n = V * im_h * im_w
-    if out is None:
-        out = torch.empty(B, n, dtype=torch.float32, device=pose_R.device)
-    ldo = _rows(out, "out")
-    if out.shape[0] != B or out.shape[1] < n or (B > 1 and ldo < n):
-        raise ValueError(f"out: expected a ({B}, >= {n}) view with row stride >= {n}, got {tuple(out.shape)} {out.stride()}")
-    if any(t_.device != pose_R.device for t_ in (verts, vert_part, faces, pose_T, cam_pose, out)):
-        raise ValueError("mesh_depth_render: all tensors must live on one device")
+    out, ldo = _out_rows(out, B, V * im_h * im_w, pose_R.device)
     with TIMER.bracket("mesh_depth_render"):
         check(lib.pm_mesh_depth_render_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], _ptr(pose_R), _ptr(pose_T),
                                            B, M, _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w,
-                                           float(near), float(far), _ptr(out), max(ldo, n), _stream()), "pm_mesh_depth_render_f32")
+                                           float(near), float(far), _ptr(out), ldo, _stream()), "pm_mesh_depth_render_f32")
     return out
 
 
@@ -1410,7 +1420,7 @@ def _root_dims(root, N=None):
     return root.shape[0], root.shape[1]
 
 
-def _part_poses(N, part, arg, part_C, pose_R, pose_T):
+def _pose_outputs(N, part, arg, part_C, pose_R, pose_T):
     """The part-pose arguments of a post wrapper: the part list `part` (M) int32 (the argument called `arg`), part_C (M, 3, 3) or
     None, pose_R (N, M, 3, 3) and pose_T (N, M, 3), either or both None.  Returns M, 0 where no pose is asked for."""
     if pose_R is None and pose_T is None:
@@ -1446,8 +1456,8 @@ def grasp_cube_post(rigid_body, dof_state, root, obj_actor, ltip, rtip, dof_lo, 
     None (skipped): normal_state (N, 19 + 2 nd), proprio (N, 7 + 2 nd) and extras (N, 8) may be column views of a wider buffer;
     rew (N) float32; success, is_reached (N) bool or uint8; pose_R (N, M, 3, 3), pose_T (N, M, 3) with part_body (M) int32 and
     part_C (M, 3, 3) or None."""
-    _req(rigid_body, dof_state, root, dof_lo, dof_hi, pose_lo, pose_hi, goal, obj_default_pos, part_body, part_C, normal_state,
-         proprio, rew, success, is_reached, extras, pose_R, pose_T)
+    _one_device("grasp_cube_post", rigid_body, dof_state, root, dof_lo, dof_hi, pose_lo, pose_hi, goal, obj_default_pos, part_body,
+                part_C, normal_state, proprio, rew, success, is_reached, extras, pose_R, pose_T)
     for t_, name in ((rigid_body, "rigid_body"), (dof_state, "dof_state"), (root, "root")):
         _f32c(t_, name)
     if rigid_body.dim() != 3 or rigid_body.shape[2] != 13 or rigid_body.shape[0] == 0 or rigid_body.shape[1] == 0:
@@ -1462,7 +1472,7 @@ def grasp_cube_post(rigid_body, dof_state, root, obj_actor, ltip, rtip, dof_lo, 
     for t_, name, n in ((dof_lo, "dof_lo", nd), (dof_hi, "dof_hi", nd), (pose_lo, "pose_lo", 7), (pose_hi, "pose_hi", 7),
                         (goal, "goal", 3), (obj_default_pos, "obj_default_pos", 3)):
         _vec(t_, name, n)
-    M = _part_poses(N, part_body, "part_body", part_C, pose_R, pose_T)
+    M = _pose_outputs(N, part_body, "part_body", part_C, pose_R, pose_T)
     lns = _row_view(normal_state, "normal_state", N, 19 + 2 * nd) if normal_state is not None else 0
     lpr = _row_view(proprio, "proprio", N, 7 + 2 * nd) if proprio is not None else 0
     lex = _row_view(extras, "extras", N, 8) if extras is not None else 0
@@ -1471,11 +1481,6 @@ def grasp_cube_post(rigid_body, dof_state, root, obj_actor, ltip, rtip, dof_lo, 
     for t_, name in ((success, "success"), (is_reached, "is_reached")):
         if t_ is not None:
             _flags(t_, name, N)
-    dev = rigid_body.device
-    if any(t_ is not None and t_.device != dev for t_ in (dof_state, root, dof_lo, dof_hi, pose_lo, pose_hi, goal, obj_default_pos,
-                                                          part_body, part_C, normal_state, proprio, rew, success, is_reached,
-                                                          extras, pose_R, pose_T)):
-        raise ValueError("grasp_cube_post: all tensors must live on one device")
     with TIMER.bracket("grasp_cube_post"):
         check(lib.pm_grasp_cube_post_f32(_ptr(rigid_body), _ptr(dof_state), _ptr(root), N, nb, nd, na, int(obj_actor), int(ltip),
                                          int(rtip), _ptr(dof_lo), _ptr(dof_hi), _ptr(pose_lo), _ptr(pose_hi), _ptr(goal),
@@ -1504,7 +1509,7 @@ def franka_control(actions, dof_state, jac, jl, jr, dof_lo, dof_hi, default_dof_
     tensors = (actions, dof_state, jac, dof_lo, dof_hi, default_dof_pos, rew, success, progress, pos_act, epis_max_rew, epis_max_step,
                reset, reset_succ, counters, base_R)
     if not nbase:                                             # the mobile path checks its shapes first, the device before the launch
-        _req(*tensors)
+        _one_device("franka_control", *tensors)
     if drive_mode not in DRIVE_MODES:
         raise ValueError(f"drive_mode: expected one of {tuple(DRIVE_MODES)}, got {drive_mode!r}")
     _f32c(dof_state, "dof_state")
@@ -1546,17 +1551,13 @@ def franka_control(actions, dof_state, jac, jl, jr, dof_lo, dof_hi, default_dof_
         _flags(t_, name, N)
     if slot not in (0, 1):
         raise ValueError(f"slot: expected 0 or 1, got {slot}")
-    dev = dof_state.device
-    if any(t_ is not None and t_.device != dev for t_ in (actions, jac, dof_lo, dof_hi, default_dof_pos, rew, success, progress,
-                                                          pos_act, epis_max_rew, epis_max_step, reset, reset_succ, counters, base_R)):
-        raise ValueError("franka_control: all tensors must live on one device")
     head = [_ptr(actions), lda, A, _ptr(dof_state), _ptr(jac), N, nd, nl, int(jl), int(jr), _ptr(dof_lo), _ptr(dof_hi),
             _ptr(default_dof_pos), float(dt), DRIVE_MODES[drive_mode]]
     tail = [_ptr(rew), _ptr(success), _ptr(progress), int(explore_step), int(max_episode_length), 1 if train else 0, _ptr(pos_act),
             _ptr(epis_max_rew), _ptr(epis_max_step), _ptr(reset), _ptr(reset_succ), _ptr(counters), int(slot)]
     entry = "pm_franka_control_f32"
     if nbase:                                                 # the mobile entry point takes (nbase, base_R) between the two
-        _req(*tensors)
+        _one_device("franka_control", *tensors)
         head += [nbase, _ptr(base_R)]
         entry = "pm_franka_control_mobile_f32"
     with TIMER.bracket("franka_control"):
@@ -1585,9 +1586,8 @@ def articulation_step(parent, jtype, dof, origin_q, origin_t, axis, anc_mask, do
     (nd); base_pose (7) or (N, 7); dof_state (N, >= nd, 2), or flat (D, 2) with dof_row0 (N) int32, updated in place when targets
     (N, nd) is given (reset (N) bool / uint8 then snaps an environment to its clamped target); rigid_body (N, >= nb, 13) or flat
     (B, 13) with rb_row0; jac (N, nb - 1, 6, nd).  rigid_body and jac may be None (skipped)."""
-    tensors = (parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, base_pose, dof_state, targets, reset, vmax,
-               rigid_body, jac, rb_row0, dof_row0)
-    _req(*tensors)
+    _one_device("articulation_step", parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, base_pose, dof_state,
+                targets, reset, vmax, rigid_body, jac, rb_row0, dof_row0)
     nb, nd = parent.numel(), dof_lo.numel()
     if not (1 <= nb <= 64 and 1 <= nd <= 64):
         raise ValueError(f"articulation_step: {nb} bodies / {nd} DOFs outside [1, 64]")
@@ -1627,9 +1627,6 @@ def articulation_step(parent, jtype, dof, origin_q, origin_t, axis, anc_mask, do
         raise ValueError("reset is given without targets")
     if reset is not None:
         _flags(reset, "reset", N)
-    dev = dof_state.device
-    if any(t_ is not None and t_.device != dev for t_ in tensors):
-        raise ValueError("articulation_step: all tensors must live on one device")
     with TIMER.bracket("articulation_step"):
         check(lib.pm_articulation_step_f32(_ptr(parent), _ptr(jtype), _ptr(dof), _ptr(origin_q), _ptr(origin_t), _ptr(axis),
                                            _ptr(anc_mask), _ptr(dof_lo), _ptr(dof_hi), _ptr(vmax), float(dt), _ptr(base_pose), lbase,
@@ -1682,7 +1679,7 @@ def open_drawer_post(rigid_body_all, dof_state_all, root, rigid_body_mask, dof_s
         _flags(succ_objid, "succ_objid", num_objs)
     if obj_id is not None:
         _vec(obj_id, "obj_id", N, torch.int32)
-    M = _part_poses(N, part_slot, "part_slot", part_C, pose_R, pose_T)
+    M = _pose_outputs(N, part_slot, "part_slot", part_C, pose_R, pose_T)
     lns = _row_view(normal_state, "normal_state", N, 29 + 2 * nd) if normal_state is not None else 0
     lex = _row_view(extras, "extras", N, 8) if extras is not None else 0
     if rew is not None:
@@ -1694,12 +1691,9 @@ def open_drawer_post(rigid_body_all, dof_state_all, root, rigid_body_mask, dof_s
                             (part_dof_state, "part_dof_state", (N, 2))):
         if t_ is not None:
             _shape_f32c(t_, name, shape)
-    every = (rigid_body_all, dof_state_all, root, rigid_body_mask, dof_state_mask, part_bbox_init, part_axis_dir_init, joint_lo,
-             joint_hi, dof_lo, dof_hi, obj_id, part_slot, part_C, normal_state, rew, success, is_reached, part_bbox, extras,
-             succ_objid, robot_dof_state, part_dof_state, pose_R, pose_T)
-    _req(*every)
-    if any(t_ is not None and t_.device != root.device for t_ in every):
-        raise ValueError("open_drawer_post: all tensors must live on one device")
+    _one_device("open_drawer_post", rigid_body_all, dof_state_all, root, rigid_body_mask, dof_state_mask, part_bbox_init,
+                part_axis_dir_init, joint_lo, joint_hi, dof_lo, dof_hi, obj_id, part_slot, part_C, normal_state, rew, success,
+                is_reached, part_bbox, extras, succ_objid, robot_dof_state, part_dof_state, pose_R, pose_T)
     with TIMER.bracket("open_drawer_post"):
         check(lib.pm_open_drawer_post_f32(_ptr(rigid_body_all), B, _ptr(dof_state_all), D, _ptr(root), N, nrb, nd, na, int(obj_actor),
                                           int(ltip), int(rtip), _ptr(rigid_body_mask), _ptr(dof_state_mask), _ptr(obj_id), num_objs,
@@ -1738,11 +1732,8 @@ def open_drawer_reset(reset, pos_act, dof_state_mask, root, dof_state_all, pos_a
     for t_, name, shape in ((robot_dof_state, "robot_dof_state", (N, nd, 2)), (part_dof_state, "part_dof_state", (N, 2))):
         if t_ is not None:
             _shape_f32c(t_, name, shape)
-    every = (reset, pos_act, dof_state_mask, root, dof_state_all, pos_act_all, robot_default_root, obj_default_root, default_dof_pos,
-             joint_lo, u, robot_dof_state, part_dof_state)
-    _req(*every)
-    if any(t_ is not None and t_.device != root.device for t_ in every):
-        raise ValueError("open_drawer_reset: all tensors must live on one device")
+    _one_device("open_drawer_reset", reset, pos_act, dof_state_mask, root, dof_state_all, pos_act_all, robot_default_root,
+                obj_default_root, default_dof_pos, joint_lo, u, robot_dof_state, part_dof_state)
     with TIMER.bracket("open_drawer_reset"):
         check(lib.pm_open_drawer_reset_f32(_ptr(reset), _ptr(pos_act), _ptr(dof_state_mask), N, nd, na, int(robot_actor),
                                            int(obj_actor), _ptr(robot_default_root), _ptr(obj_default_root), 0 if u is None else 1,

@@ -88,6 +88,12 @@ def npy(x):
     return x.detach().cpu().numpy()
 
 
+def bits(x):
+    """The float32 bit patterns of a tensor or an array as uint32, for comparisons that index or mask them."""
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
 def same_bits(a, b):
     """Equal arrays; float32 ones of one shape and dtype, compared as bit patterns (so NaN equals NaN and -0 differs from 0)."""
     a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)

@@ -19,7 +19,7 @@ import torch
 
 from tests import grasp_cube_ref as G
 from tests import helpers
-from tests.helpers import ROOT, load, npy, record_margin, same_bits, within
+from tests.helpers import ROOT, bits, load, npy, record_margin, same_bits, within
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -27,11 +27,6 @@ t = functools.partial(helpers.t, device=DEV)
 SENTINEL = -777.25
 EPS = float(np.finfo(np.float32).eps)
 GROUPS = ("normal_state", "proprio", "rew", "pose_R", "pose_T")
-
-
-def bits(x):
-    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def fixture_task(fx, drive="ik"):

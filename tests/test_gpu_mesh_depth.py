@@ -14,7 +14,7 @@ import torch
 
 from tests import depth_render_ref as D
 from tests import mesh_bake_ref as MB
-from tests.helpers import ROOT
+from tests.helpers import ROOT, bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -23,11 +23,6 @@ SENTINEL = -777.25
 
 def t(x, dtype=None):
     return torch.as_tensor(np.array(x), dtype=dtype).to(DEV)                   # a copy: the shared scene arrays are read-only
-
-
-def bits(x):
-    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def render_gpu(sc, out=None):
@@ -107,6 +102,14 @@ def test_odd_sizes_and_out_view_with_sentinel_tail():
     assert got.data_ptr() == buf.data_ptr()
     assert np.array_equal(bits(got), bits(want))
     assert (buf[:, n:] == SENTINEL).all()
+    # one environment: the row stride of a one-row view is arbitrary (n + 5, n + 5 and 1 here) and must reach the kernel as n
+    one = dict(sc, R=sc["R"][:1], T=sc["T"][:1])
+    want1 = render_gpu(one)
+    wide, flat, col = (torch.full(s, SENTINEL, device=DEV) for s in ((1, n + 5), (n + 5,), (n + 5, 1)))
+    for base, out in ((wide, wide[:, :n]), (flat, flat[None]), (col, col.t())):
+        got = render_gpu(one, out=out)
+        assert got.data_ptr() == base.data_ptr() and np.array_equal(bits(got), bits(want1))
+        assert (base.reshape(-1)[n:] == SENTINEL).all()
 
 
 def test_big_triangles_cover_the_frustum_without_a_crack():

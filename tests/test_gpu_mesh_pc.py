@@ -7,6 +7,7 @@ float64 run; the kernel must stay within 4 e_ref of out64 (this project's margin
 contract fixes the association and the rounding of every operation, so the uint32 views must be equal.
 Observed 2026-10-17 on 1x MI355X: e_ref = 1.58e-8 / 1.97e-8 (small / 1024 fixture), max |hip - out64| = 1.00 / 1.07 e_ref
 (profiles/mesh_pc_margins.json)."""
+import functools
 import json
 import os
 import shutil
@@ -18,26 +19,14 @@ import pytest
 import torch
 
 from tests import mesh_bake_ref as MB
-from tests.helpers import GOLDEN, ROOT, record_margin
+from tests import helpers
+from tests.helpers import GOLDEN, ROOT, bits, load, record_margin
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+t = functools.partial(helpers.t, device=DEV)
 FINGER = os.path.join(GOLDEN, "finger.stl")
 SENTINEL = -777.25
-
-
-def load(name):
-    with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
-        return {k: z[k] for k in z.files}
-
-
-def t(x, dtype=None):
-    return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype).to(DEV)
-
-
-def bits(x):
-    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def ref32(pts, part_of, R, T, sel):
@@ -139,6 +128,14 @@ def test_out_views_at_every_row_alignment_leave_the_tail_alone(off, K):
     assert np.array_equal(bits(view[:, :3 * K]), bits(want.reshape(B, -1)))
     assert bool((view[:, 3 * K:] == SENTINEL).all()) and bool((buf[:off] == SENTINEL).all())
     assert bool((buf[off + B * width:] == SENTINEL).all())
+    # one environment: the row stride of a one-row view is arbitrary (n + 5, n + 5 and 1 here) and must reach the kernel as n
+    n, R1, T1 = 3 * K, t(R[:1]), t(T[:1])
+    want1 = pc.query_pc(R1, T1, sel=t(sel))
+    wide, flat, col = (torch.full(s, SENTINEL, device=DEV) for s in ((1, n + 5), (n + 5,), (n + 5, 1)))
+    for base, out in ((wide, wide[:, :n]), (flat, flat[None]), (col, col.t())):
+        got = pc.query_pc(R1, T1, out=out, sel=t(sel))
+        assert got.data_ptr() == base.data_ptr() and np.array_equal(bits(got), bits(want1))
+        assert bool((base.reshape(-1)[n:] == SENTINEL).all())
 
 
 # ------------------------------------------------------------------------------------------- 3. guards

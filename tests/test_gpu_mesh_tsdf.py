@@ -124,6 +124,14 @@ def test_strided_output_lands_in_an_observation_buffer_and_leaves_the_tail_alone
     assert torch.equal(buf2[:, :N], want.reshape(2, -1)) and torch.isnan(buf2[:, N:]).all()
     with pytest.raises(ValueError):
         obj.query_tsdf(R, T, out=buf[:, :N - 1])
+    # one environment: the row stride of a one-row view is arbitrary (N + 5, N + 5 and 1 here) and must reach the kernel as N
+    want1 = obj.query_tsdf(R[:1], T[:1])
+    assert not torch.isnan(want1).any()
+    wide, flat, col = (torch.full(s, float("nan"), device=DEV) for s in ((1, N + 5), (N + 5,), (N + 5, 1)))
+    for base, out in ((wide, wide[:, :N]), (flat, flat[None]), (col, col.t())):
+        got = obj.query_tsdf(R[:1], T[:1], out=out)
+        assert got.data_ptr() == base.data_ptr() and torch.equal(got.view(torch.int32), want1.view(torch.int32))
+        assert torch.isnan(base.reshape(-1)[N:]).all()
 
 
 def test_repeatable_and_stream_independent():

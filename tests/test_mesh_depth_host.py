@@ -151,6 +151,11 @@ def test_render_refuses_cpu_tensors_and_wrong_shapes():
     for bad_R, bad_T in ((R[:, :2], T), (R, T[:, :2]), (R.reshape(3, 3, 9), T), (R, T[:2]), (R.double(), T.double())):
         with pytest.raises(ValueError):
             cam.render(bad_R, bad_T)
+    for bad_out in (torch.empty(3 * 1920), torch.empty(2, 1920), torch.empty(3, 1919)):  # 1-D, wrong row count, too few columns
+        with pytest.raises(ValueError, match="out"):
+            cam.render(R, T, out=bad_out)                    # the out view is checked before the device
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        cam.render(R, T, out=torch.empty(3, 1920))
     with pytest.raises(ValueError):
         DepthFromMesh(1, "cpu", sc["cam_pose"][0], intr, 24, 40, meshes=[finger])               # (4, 4), not (V, 4, 4)
     with pytest.raises(ValueError):

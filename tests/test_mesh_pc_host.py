@@ -13,15 +13,10 @@ import pytest
 import torch
 
 from tests import mesh_bake_ref as MB
-from tests.helpers import GOLDEN
+from tests.helpers import GOLDEN, load
 
 FINGER = os.path.join(GOLDEN, "finger.stl")
 FIXTURES = ("mesh_pc_ref_small", "mesh_pc_ref_1024")
-
-
-def load(name):
-    with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
-        return {k: z[k] for k in z.files}
 
 
 def restate64(part_pcs, R, T, sel):
@@ -175,6 +170,11 @@ def test_query_pc_refuses_cpu_tensors_and_wrong_shapes():
     for bad_R, bad_T in ((R[:, :11], T), (R, T[:, :11]), (R.reshape(3, 12, 9), T), (R, T[:2]), (R.double(), T.double())):
         with pytest.raises(ValueError):
             pc.query_pc(bad_R, bad_T)
+    for bad_out in (torch.empty(3 * 192), torch.empty(2, 192), torch.empty(3, 191)):    # 1-D, wrong row count, too few columns
+        with pytest.raises(ValueError, match="out"):
+            pc.query_pc(R, T, out=bad_out)                   # the out view is checked before the device
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        pc.query_pc(R, T, out=torch.empty(3, 192))
     with pytest.raises(ValueError):
         PCfromMesh(1, "cpu", part_pcs=np.zeros((12, 64, 2), dtype=np.float32))
     with pytest.raises(ValueError):

@@ -18,29 +18,14 @@ import sys
 
 import numpy as np
 import torch
-from torch.utils._python_dispatch import TorchDispatchMode
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partmanip_amd.tasks import GraspCubeTensors  # noqa: E402
+from tools.timing import HBM_BYTES_PER_S, count_ops, timed  # noqa: E402
 
 DEV = "cuda:0"
-HBM_BYTES_PER_S = 6.29e12
 NB, ND, NL, M = 14, 9, 12, 12
 IND = [[0, 1], [0, 2], [1, 2], [1, 0], [2, 0], [2, 1]] * 4
-VIEW_OPS = ("view", "reshape", "slice", "select", "unsqueeze", "squeeze", "expand", "transpose", "permute", "alias", "detach", "t.",
-            "unbind", "as_strided", "_unsafe_view", "unflatten", "size", "stride", "is_", "numel", "dim", "lift_fresh", "split")
-
-
-class OpCounter(TorchDispatchMode):
-    def __init__(self):
-        super().__init__()
-        self.n = 0
-
-    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-        name = str(func)
-        if not any(v in name for v in VIEW_OPS):
-            self.n += 1
-        return func(*args, **(kwargs or {}))
 
 
 def quat_to_mat(q):
@@ -146,22 +131,6 @@ def make_state(N, seed=31):
     jac = torch.randn(N, NL, 6, ND, device=DEV, generator=g)
     act = torch.rand(N, 7, device=DEV, generator=g) * 2 - 1
     return rb.contiguous(), dof.contiguous(), root.contiguous(), jac.contiguous(), act.contiguous()
-
-
-def timed(fn, calls):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / calls
-
-
-def count_ops(fn):
-    with OpCounter() as c:
-        fn()
-    return c.n
 
 
 def step_bytes():

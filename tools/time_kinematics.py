@@ -24,7 +24,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 from partmanip_amd.kinematics import KinematicSim  # noqa: E402
 from partmanip_amd.urdf import PRISMATIC, REVOLUTE, load_urdf  # noqa: E402
-from tools.time_grasp_cube import HBM_BYTES_PER_S, count_ops, timed  # noqa: E402
+from tools.timing import HBM_BYTES_PER_S, count_ops, timed  # noqa: E402
 
 DEV = "cuda:0"
 DT = 1.0 / 60.0

@@ -27,6 +27,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 from partmanip_amd import meshio, ops  # noqa: E402
 from partmanip_amd.mesh2sdf import bake_grid_layout  # noqa: E402
+from tools.timing import timed  # noqa: E402
 
 DEV = "cuda:0"
 TRUNC, VOXEL = 4 * 0.5 / 50, 0.002
@@ -78,16 +79,6 @@ def torch_bake(tri, pts, trunc, pairs_per_chunk=1 << 22):
         dist = torch.sqrt(d2)
         out[lo:lo + step] = torch.clamp(torch.where(turn.abs() >= math.pi, -dist, dist), -trunc, trunc)
     return out
-
-
-def timed(fn, calls):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / calls
 
 
 def main():

@@ -26,9 +26,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from partmanip_amd import camera  # noqa: E402
 from partmanip_amd.mesh2depth import DepthFromMesh  # noqa: E402
 from partmanip_amd.mesh2pc import random_poses  # noqa: E402
+from tools.timing import HBM_BYTES_PER_S, timed  # noqa: E402
 
 DEV = "cuda:0"
-HBM_BYTES_PER_S = 6.29e12
 M = 12
 CAM = dict(look_at=[0.0, 0.0, 0.0], radius=0.8)                               # the grasp_cube task's `cam` block
 
@@ -101,16 +101,6 @@ def torch_cast(cam, R, T, face_chunk=4096):
         hit = same & (s != 0) & (z > cam.near) & (z < cam.far)
         out = torch.minimum(out, torch.where(hit, z, torch.full_like(z, cam.far)).amin(dim=-1))
     return out
-
-
-def timed(fn, calls):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / calls
 
 
 def calls_for(fn, window_ms=400.0, most=20):

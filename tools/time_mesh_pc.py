@@ -18,9 +18,9 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partmanip_amd.mesh2pc import PCfromMesh, random_poses  # noqa: E402
+from tools.timing import HBM_BYTES_PER_S, timed  # noqa: E402
 
 DEV = "cuda:0"
-HBM_BYTES_PER_S = 6.29e12
 M, P = 12, 1024
 
 
@@ -43,16 +43,6 @@ def torch_query(all_pc, R, T, num_envs, num_points):
     posed = posed.reshape(num_envs, -1, 3)
     randperm = torch.randperm(posed.shape[1])
     return posed[:, randperm[:num_points], :]
-
-
-def timed(fn, calls):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / calls
 
 
 def main():

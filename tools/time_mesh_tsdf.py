@@ -16,9 +16,9 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partmanip_amd.mesh2sdf import TSDFfromMesh  # noqa: E402
+from tools.timing import HBM_BYTES_PER_S, timed  # noqa: E402
 
 DEV = "cuda:0"
-HBM_BYTES_PER_S = 6.29e12
 RES, SIZE, M = 50, 0.5, 12
 
 
@@ -78,16 +78,6 @@ def torch_query(obj, shapes, offs, R, T, out, chunk=64):
             best = torch.minimum(best, torch.where(ok, val, torch.ones_like(val)))
         out[b0:b0 + chunk] = torch.clamp(best / obj.sdf_trunc, -1, 1)
     return out
-
-
-def timed(fn, calls):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / calls
 
 
 def main():

@@ -22,7 +22,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partmanip_amd.tasks import Franka, MobileFranka, OpenDrawerTensors  # noqa: E402
 from partmanip_amd.tasks.open_drawer import build_masks  # noqa: E402
-from tools.time_grasp_cube import count_ops, timed  # noqa: E402
+from tools.timing import count_ops, timed  # noqa: E402
 
 DEV = "cuda:0"
 TYPES = ((3, 1, 1, 2, 0), (5, 3, 2, 4, 2), (4, 2, 3, 1, 1))

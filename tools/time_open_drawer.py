@@ -23,10 +23,10 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partmanip_amd.tasks import OpenDrawerTensors  # noqa: E402
 from partmanip_amd.tasks.open_drawer import build_masks  # noqa: E402
-from tools.time_grasp_cube import count_ops, quat_to_mat, timed  # noqa: E402
+from tools.time_grasp_cube import quat_to_mat  # noqa: E402
+from tools.timing import HBM_BYTES_PER_S, count_ops, timed  # noqa: E402
 
 DEV = "cuda:0"
-HBM_BYTES_PER_S = 6.29e12
 NRB, ND, NL, M = 13, 9, 12, 13
 TYPES = ((3, 1, 1, 2, 0), (5, 3, 2, 4, 2), (4, 2, 3, 1, 1))
 
