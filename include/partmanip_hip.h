@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 160 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 161 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -729,6 +729,46 @@ int pm_articulation_step_f32(const int32_t* parent, const int32_t* jtype, const 
                              float* dof_state, long dof_rows, const float* targets, long tgt_stride, const uint8_t* reset,
                              const int32_t* rb_row0, long rb_stride, long rb_rows, const int32_t* dof_row0, long dof_stride, int N,
                              int nb, int nd, float* rigid_body, float* jac, void* stream);
+
+/* ------------------------------------------------------------------ kinematic objects (a stand-in for the simulator's cabinets)
+ * One articulated object per environment, each environment a tree of its own out of a library of K, posed into the flat
+ * rigid_body (rb_rows, 13) and dof_state (dof_rows, 2) in one launch (csrc/articulation_objects.hip).  Kinematics only: no dynamics,
+ * contact, gravity or friction.  The library is K trees of pm_articulation_step_f32 laid end to end:
+ *   body_off, dof_off (K + 1) int32: tree k owns bodies [body_off[k], body_off[k + 1]) and DOFs [dof_off[k], dof_off[k + 1]) of
+ *   parent, jtype, dof, origin_q, origin_t, axis, anc_mask (total_bodies rows) and dof_lo, dof_hi (total_dofs); parent and dof are
+ *   LOCAL to their tree, and each tree obeys that entry's rules (root first, a parent precedes its children, at most 64 x 64).
+ *   max_nb, max_nd: the largest body and DOF count of the library (they size the launch; a tree above them is skipped).
+ * Per environment e: obj_type[e] in [0, K);  its pose, 7 floats at obj_pose + e * pose_stride (0: one pose for all), the quaternion
+ * divided by its norm (root[:, obj_actor, :7] with pose_stride = na * 13);  obj_rb_row0[e] / obj_dof_row0[e]: the first of its
+ * nb_k rows of rigid_body / nd_k rows of dof_state.  order (N) int32 or NULL: a permutation of the environments, grouped by type
+ * (kinematics.ObjectLibrary.order_of), that only chooses which lane computes which environment; the results do not depend on it.
+ * Output: environment e's nb_k body rows in pm_articulation_step_f32's format and by its rules: position and quaternion from the same
+ * float64 chain rounded once (a tree gives the same bits through either entry), linear and angular velocity = J qd over the
+ * ancestor DOFs, summed in ascending order.  No Jacobian is written.
+ * The hold group, all NULL (dof_state is only read: pure forward kinematics) or all given with dt > 0: hold, reset (N) bytes,
+ * target_dof (N) int32 local to the object, tip_rows (N, 2) int32: rows of rigid_body (the robot's left and right tip, which this
+ * launch must not write: they are read as they stand when it runs, i.e. after the robot's launch on the same stream).  Then for
+ * the target DOF, (q, qd) being its row:
+ *   hold[e] set and reset[e] not:  p, v = the means of the two tip rows' positions and linear velocities;  a = the joint's world axis,
+ *     p_j = the origin of its body (neither depends on q);  c = a (prismatic) or a x (p - p_j) (revolute);
+ *     dq = dt (c . v) / (c . c), 0 where c . c == 0 (float64);  q' = clamp(float(q + dq), lo, hi);  qd' = (q' - q) / dt
+ *   otherwise:  q' = q, qd' = 0
+ *   and (q', qd') is written to the target row.  No other DOF row is ever written.  clamp passes a NaN through.
+ * An environment's bits depend on its own rows only: not on N, on order, on its neighbours' types or on the block it lands in; a NaN
+ * stays in its environment.  No synchronisation, allocation or atomics; stream-ordered.  An environment whose obj_type is outside
+ * [0, K), whose offsets do not lie inside the tables, whose rows would not lie inside [0, rows), or (hold group given) whose
+ * target_dof is outside [0, nd_k) or whose tip rows are outside [0, rb_rows) stores nothing and reads nothing out of range.
+ * PM_EINVAL: a NULL required pointer (every table, obj_type, obj_pose, both row tables, dof_state, rigid_body), N or K < 1, max_nb or
+ * max_nd outside [1, 64], total_bodies or total_dofs < 1, pose_stride other than 0 below 7, rows < 1 or >= 2^31, a hold group given
+ * in part, dt <= 0 with it.  The tables' contents are the caller's to validate. */
+int pm_articulation_objects_step_f32(const int32_t* body_off, const int32_t* dof_off, int K, int total_bodies, int total_dofs,
+                                     int max_nb, int max_nd, const int32_t* parent, const int32_t* jtype, const int32_t* dof,
+                                     const float* origin_q, const float* origin_t, const float* axis, const uint64_t* anc_mask,
+                                     const float* dof_lo, const float* dof_hi, const int32_t* obj_type, const int32_t* order,
+                                     const float* obj_pose, long pose_stride, const int32_t* obj_rb_row0, const int32_t* obj_dof_row0,
+                                     float* dof_state, long dof_rows, float* rigid_body, long rb_rows, const uint8_t* hold,
+                                     const uint8_t* reset, const int32_t* target_dof, const int32_t* tip_rows, float dt, int N,
+                                     void* stream);
 
 /* ------------------------------------------------------------------ K15 fused set-abstraction level
  * One PointNet++ SA level (north_star; not in the reference snapshot, README.md:23,30) as one forward and

@@ -112,6 +112,7 @@ SIGNATURES = {
                                     P, P, P]),
     "pm_open_drawer_reset_f32": (I, [P, P, P, I, I, I, I, I, P, P, I, P, F, F, P, P, P, P, L, P, P, P, P]),
     "pm_articulation_step_f32": (I, [P, P, P, P, P, P, P, P, P, P, F, P, L, P, L, P, L, P, P, L, L, P, L, I, I, I, P, P, P]),
+    "pm_articulation_objects_step_f32": (I, [P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, L, P, P, P, L, P, L, P, P, P, P, F, I, P]),
     "pm_voxel_grid0_f32": (I, [P, L, I, I, I, I, P, P, P, P]),
     "pm_voxel_nbr27_i32": (I, [P, L, P, I, P, I, P]),
     "pm_voxel_mirror27_i32": (I, [P, L, P, P]),
@@ -206,7 +207,7 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
-ABI_VERSION = 160                      # == PM_ABI_VERSION in include/partmanip_hip.h (checked by tests/test_capi_symbols.py)
+ABI_VERSION = 161                      # == PM_ABI_VERSION in include/partmanip_hip.h (checked by tests/test_capi_symbols.py)
 if lib.pm_version() != ABI_VERSION:
     raise ImportError(f"{LIB_PATH} is stale: it reports ABI {lib.pm_version()}, this package needs {ABI_VERSION}. "
                       "Rebuild it with `python -m partmanip_amd.build`.")

@@ -29,44 +29,7 @@
 // TS_GRID_MIN or LDS over TS_LDS_MAX).
 #include "common.h"
 #include "task_common.h"                                      // ts_clamp, ts_envs_per_block, TS_LDS_MAX
-
-#define AR_THREADS 256
-#define AR_MAX 64                                             // bodies and DOFs at most: 64-bit ancestor masks, the static tables
-#define AR_REVOLUTE 1
-#define AR_PRISMATIC 2
-
-// Hamilton product of quaternions (x, y, z, w): the rotation b, then a
-__device__ __forceinline__ void ar_qmul(const double* a, const double* b, double* o) {
-    o[0] = ((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1];
-    o[1] = ((a[3] * b[1] - a[0] * b[2]) + a[1] * b[3]) + a[2] * b[0];
-    o[2] = ((a[3] * b[2] + a[0] * b[1]) - a[1] * b[0]) + a[2] * b[3];
-    o[3] = ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2];
-}
-
-// v turned by the unit quaternion q: v + 2 w (u x v) + 2 u x (u x v)
-__device__ __forceinline__ void ar_qrot(const double* q, const double* v, double* o) {
-    const double cx = q[1] * v[2] - q[2] * v[1], cy = q[2] * v[0] - q[0] * v[2], cz = q[0] * v[1] - q[1] * v[0];
-    const double dx = q[1] * cz - q[2] * cy, dy = q[2] * cx - q[0] * cz, dz = q[0] * cy - q[1] * cx;
-    o[0] = v[0] + 2.0 * (q[3] * cx + dx);
-    o[1] = v[1] + 2.0 * (q[3] * cy + dy);
-    o[2] = v[2] + 2.0 * (q[3] * cz + dz);
-}
-
-__device__ __forceinline__ void ar_qunit(double* q) {
-    const double s = 1.0 / sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    q[0] *= s, q[1] *= s, q[2] *= s, q[3] *= s;
-}
-
-// Entry (r, d) of body `body`'s Jacobian, for a DOF d that IS an ancestor: rb = the environment's staged body rows, ax its world axes.
-__device__ __forceinline__ float ar_jentry(const float* rb, const float* ax, int body, int r, int d, int info) {
-    const float* a = ax + d * 3;
-    if ((info >> 8) == AR_PRISMATIC) return r < 3 ? a[r] : 0.0f;
-    if (r >= 3) return a[r - 3];
-    const float* pb = rb + body * 13;
-    const float* pj = rb + (info & 0xff) * 13;
-    const int i = r == 2 ? 0 : r + 1, j = r == 0 ? 2 : r - 1;                       // (a x v)[r] = a[i] v[j] - a[j] v[i]
-    return a[i] * (pb[j] - pj[j]) - a[j] * (pb[i] - pj[i]);
-}
+#include "articulation_common.h"                              // the quaternion helpers, the frame step, ar_jentry
 
 __global__ __launch_bounds__(AR_THREADS) void articulation_step_kernel(
     const int32_t* __restrict__ parent, const int32_t* __restrict__ jtype, const int32_t* __restrict__ dof,
@@ -140,19 +103,12 @@ __global__ __launch_bounds__(AR_THREADS) void articulation_step_kernel(
             ar_qunit(base + 3);
             for (int b = 0; b < nb; ++b) {
                 const int p = parent[b];
-                double pp[3], pq[4], ot[3], oq[4], pos[3], fq[4];
+                double pp[3], pq[4], pos[3], fq[4];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) pp[c] = (p >= 0 && p < b) ? fr[p * 7 + c] : base[c];
 #pragma unroll
                 for (int c = 0; c < 4; ++c) pq[c] = (p >= 0 && p < b) ? fr[p * 7 + 3 + c] : base[3 + c];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) ot[c] = origin_t[b * 3 + c];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) oq[c] = origin_q[b * 4 + c];
-                ar_qrot(pq, ot, pos);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) pos[c] = pp[c] + pos[c];
-                ar_qmul(pq, oq, fq);
+                ar_frame_origin(pp, pq, origin_t, origin_q, b, pos, fq);
                 const int jt = jtype[b], d = dof[b];
                 if ((jt == AR_REVOLUTE || jt == AR_PRISMATIC) && d >= 0 && d < nd) {
                     const double al[3] = {axis[b * 3], axis[b * 3 + 1], axis[b * 3 + 2]};
@@ -160,18 +116,7 @@ __global__ __launch_bounds__(AR_THREADS) void articulation_step_kernel(
                     ar_qrot(fq, al, aw);
 #pragma unroll
                     for (int c = 0; c < 3; ++c) ax[d * 3 + c] = (float)aw[c];
-                    const double th = qs[d];
-                    if (jt == AR_REVOLUTE) {
-                        const double h = 0.5 * th, sn = sin(h), cs = cos(h);
-                        const double jq[4] = {al[0] * sn, al[1] * sn, al[2] * sn, cs};
-                        double t4[4];
-                        ar_qmul(fq, jq, t4);
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) fq[c] = t4[c];
-                    } else {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) pos[c] = pos[c] + aw[c] * th;
-                    }
+                    ar_frame_joint(jt, al, aw, (double)qs[d], pos, fq);
                 }
                 ar_qunit(fq);
 #pragma unroll

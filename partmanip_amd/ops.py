@@ -1635,6 +1635,66 @@ def articulation_step(parent, jtype, dof, origin_q, origin_t, axis, anc_mask, do
               "pm_articulation_step_f32")
 
 
+def articulation_objects_step(body_off, dof_off, parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, max_nb, max_nd,
+                              obj_type, obj_pose, obj_rb_row0, obj_dof_row0, dof_state, rigid_body, order=None, hold=None, reset=None,
+                              target_dof=None, tip_rows=None, dt=0.0):
+    """One object tree per environment, posed into the flat tensors in one launch (pm_articulation_objects_step_f32,
+    include/partmanip_hip.h).  The library tables come from kinematics.ObjectLibrary, which validates them: body_off, dof_off
+    (K + 1) int32, the per-body tables over all the trees' bodies, dof_lo / dof_hi over all their DOFs, max_nb / max_nd the largest
+    tree.  obj_type (N) int32; obj_pose (7), or an (N, 7) view with unit inner stride (root[:, obj_actor, :7]); obj_rb_row0,
+    obj_dof_row0 (N) int32; dof_state (D, 2) and rigid_body (B, 13) flat; order (N) int32 or None.  The hold group hold, reset (N)
+    bool / uint8, target_dof (N) int32, tip_rows (N, 2) int32 and dt > 0 comes together or not at all; without it dof_state is only
+    read."""
+    _one_device("articulation_objects_step", body_off, dof_off, parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi,
+                obj_type, obj_pose, obj_rb_row0, obj_dof_row0, dof_state, rigid_body, order, hold, reset, target_dof, tip_rows)
+    K, TB, TD, N = body_off.numel() - 1, parent.numel(), dof_lo.numel(), obj_type.numel()
+    if K < 1 or TB < 1 or TD < 1 or N < 1:
+        raise ValueError(f"articulation_objects_step: {K} trees, {TB} bodies, {TD} DOFs, {N} environments: expected at least one of each")
+    if not (1 <= int(max_nb) <= 64 and 1 <= int(max_nd) <= 64):
+        raise ValueError(f"articulation_objects_step: max_nb {max_nb} / max_nd {max_nd} outside [1, 64]")
+    _vec(body_off, "body_off", K + 1, torch.int32)
+    _vec(dof_off, "dof_off", K + 1, torch.int32)
+    for t_, name in ((parent, "parent"), (jtype, "jtype"), (dof, "dof")):
+        _vec(t_, name, TB, torch.int32)
+    _vec(anc_mask, "anc_mask", TB, torch.int64)
+    _shape_f32c(origin_q, "origin_q", (TB, 4))
+    _shape_f32c(origin_t, "origin_t", (TB, 3))
+    _shape_f32c(axis, "axis", (TB, 3))
+    _vec(dof_lo, "dof_lo", TD)
+    _vec(dof_hi, "dof_hi", TD)
+    for t_, name in ((obj_type, "obj_type"), (obj_rb_row0, "obj_rb_row0"), (obj_dof_row0, "obj_dof_row0")):
+        _vec(t_, name, N, torch.int32)
+    if order is not None:
+        _vec(order, "order", N, torch.int32)
+    if obj_pose.dim() == 1:
+        _shape_f32c(obj_pose, "obj_pose", (7,))
+        lpose = 0
+    else:
+        lpose = _row_view(obj_pose, "obj_pose", N, 7)
+    _shape_f32c(dof_state, "dof_state", (dof_state.shape[0], 2))
+    _shape_f32c(rigid_body, "rigid_body", (rigid_body.shape[0], 13))
+    if dof_state.shape[0] < 1 or rigid_body.shape[0] < 1:
+        raise ValueError("dof_state / rigid_body: expected at least one row")
+    group = (hold, reset, target_dof, tip_rows)
+    if any(g is not None for g in group):
+        if any(g is None for g in group):
+            raise ValueError("hold, reset, target_dof and tip_rows come together or not at all")
+        _flags(hold, "hold", N)
+        _flags(reset, "reset", N)
+        _vec(target_dof, "target_dof", N, torch.int32)
+        _vec(tip_rows, "tip_rows", 2 * N, torch.int32)
+        if not float(dt) > 0:
+            raise ValueError(f"dt: expected a positive step with the hold group, got {dt}")
+    with TIMER.bracket("articulation_objects_step"):
+        check(lib.pm_articulation_objects_step_f32(_ptr(body_off), _ptr(dof_off), K, TB, TD, int(max_nb), int(max_nd), _ptr(parent),
+                                                   _ptr(jtype), _ptr(dof), _ptr(origin_q), _ptr(origin_t), _ptr(axis), _ptr(anc_mask),
+                                                   _ptr(dof_lo), _ptr(dof_hi), _ptr(obj_type), _ptr(order), _ptr(obj_pose), lpose,
+                                                   _ptr(obj_rb_row0), _ptr(obj_dof_row0), _ptr(dof_state), dof_state.shape[0],
+                                                   _ptr(rigid_body), rigid_body.shape[0], _ptr(hold), _ptr(reset), _ptr(target_dof),
+                                                   _ptr(tip_rows), float(dt), N, _stream()),
+              "pm_articulation_objects_step_f32")
+
+
 def _index_table(t_, name, N):
     if t_.dtype != torch.int32 or t_.dim() != 2 or t_.shape[0] != N or not t_.is_contiguous():
         raise ValueError(f"{name}: expected a contiguous int32 tensor ({N}, width), got {t_.dtype} {tuple(t_.shape)}")

@@ -22,12 +22,15 @@ Left out: building a mobile base from the cfg alone (the cfg-only constructor ra
 pass robot=MobileFranka(...)), the drive modes 'ik_abs' (the reference's own code raises a shape error for more than one environment)
 and 'heuristic' (a debugging mode that ends the process): NotImplementedError naming them; the reference's random STREAM (see
 begin_step) and extras['step_id'] (it is `progress_buf.float()`)."""
+import json
 import math
+import os
 
 import numpy as np
 import torch
 
 from .. import ops
+from ..urdf import FIXED, load_urdf
 from .base import TaskTensors, franka_parts
 
 EXTRAS_COLUMNS = ("is_open", "is_open_notgrasp", "reaching_reward", "close_reward", "rot_reward", "joint_state_reward", "raw_reward",
@@ -62,6 +65,109 @@ def build_masks(num_robot_bodies, num_robot_dofs, obj_bodies, obj_dofs, target_l
         dof_count += num_robot_dofs + int(obj_dofs[i])
         rigid_count += num_robot_bodies + int(obj_bodies[i])
     return rb, dm, rigid_count, dof_count
+
+
+class DrawerEnvs:
+    """DrawerAssets.for_envs(N): every per-environment array that build_masks, OpenDrawerTensors and kinematics.KinematicSim take, as
+    numpy: obj_id, obj_bodies, obj_dofs, target_link, target_handle, target_dof (N) int32; part_bbox_init (N, 8, 3), part_axis_dir_init
+    (N, 3), part_joint_lower_limits, part_joint_upper_limits (N) float32; num_objs."""
+
+    def __init__(self, assets, N):
+        oid = (np.arange(int(N)) % assets.num_objs).astype(np.int32)          # open_drawer.py:145
+        self.num_envs, self.num_objs, self.obj_id = int(N), assets.num_objs, oid
+        pick = lambda a, dt: np.ascontiguousarray(np.asarray(a)[oid], dtype=dt)      # noqa: E731
+        self.obj_bodies, self.obj_dofs = pick(assets.num_bodies, np.int32), pick(assets.num_dofs, np.int32)
+        self.target_link, self.target_handle = pick(assets.target_link, np.int32), pick(assets.target_handle, np.int32)
+        self.target_dof = pick(assets.target_dof, np.int32)
+        self.part_bbox_init, self.part_axis_dir_init = pick(assets.part_bbox_init, np.float32), pick(assets.part_axis_dir_init, np.float32)
+        self.part_joint_lower_limits = pick(assets.part_joint_lower_limits, np.float32)
+        self.part_joint_upper_limits = pick(assets.part_joint_upper_limits, np.float32)
+
+    def masks(self, num_robot_bodies, num_robot_dofs):
+        """build_masks for these environments: (rigid_body_mask, dof_state_mask, B, D)."""
+        return build_masks(num_robot_bodies, num_robot_dofs, self.obj_bodies, self.obj_dofs, self.target_link, self.target_handle,
+                           self.target_dof)
+
+    def task_kwargs(self):
+        """The per-object keyword arguments of OpenDrawerTensors."""
+        return dict(obj_id=self.obj_id, part_bbox_init=self.part_bbox_init, part_axis_dir_init=self.part_axis_dir_init,
+                    part_joint_lower_limits=self.part_joint_lower_limits, part_joint_upper_limits=self.part_joint_upper_limits,
+                    num_objs=self.num_objs)
+
+
+class DrawerAssets:
+    """What load_drawer_assets read, per object k: trees[k] (urdf.KinematicTree at `scale`), names[k] = (asset, link, handle, joint),
+    target_link[k] / target_handle[k] (body rows of the tree), target_dof[k] (DOF of the tree), part_bbox_init (K, 8, 3),
+    part_axis_xyz_init, part_axis_dir_init (K, 3), part_joint_lower_limits, part_joint_upper_limits (K), num_bodies, num_dofs."""
+
+    def __init__(self, folders, scale, trees, names, target_link, target_handle, target_dof, bbox, axis_xyz, axis_dir, lower, upper):
+        self.folders, self.scale, self.trees, self.names, self.num_objs = list(folders), float(scale), list(trees), list(names), len(trees)
+        self.target_link, self.target_handle, self.target_dof = (np.asarray(a, dtype=np.int32) for a in (target_link, target_handle, target_dof))
+        self.part_bbox_init = np.asarray(bbox, dtype=np.float64).reshape(-1, 8, 3)
+        self.part_axis_xyz_init = np.asarray(axis_xyz, dtype=np.float64).reshape(-1, 3)
+        self.part_axis_dir_init = np.asarray(axis_dir, dtype=np.float64).reshape(-1, 3)
+        self.part_joint_lower_limits, self.part_joint_upper_limits = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+        self.num_bodies = np.array([t.num_bodies for t in trees], dtype=np.int32)
+        self.num_dofs = np.array([t.num_dofs for t in trees], dtype=np.int32)
+
+    def for_envs(self, N):
+        """Environment e holds object e % num_objs (open_drawer.py:145)."""
+        return DrawerEnvs(self, N)
+
+
+def load_drawer_assets(folders, scale=0.5):
+    """The reference's object folders (open_drawer.py:98-140) -> DrawerAssets, on the host.  A folder's name parses as
+    `...-asset-link-handle-joint-...` (`name.split('-')[-5:-1]`); it holds bbox_info.json (link_name, bbox_world, axis_xyz_world,
+    axis_dir_world) and mobility_new.urdf, loaded at `scale` (urdf.load_urdf: the effect of the reference's set_actor_scale, 0.5).
+    part_bbox_init = bbox_world[handle] * scale; the axes are those of the link; the limits are the reference's expressions: the
+    file's upper limit of the target joint times scale, its lower limit as in the file.
+
+    One difference from the reference, stated: it uses the json's link index as the BODY index too, trusting the simulator's body
+    order to be the json's.  Here the bbox and axis arrays are indexed by the json's order, and the body rows (target_link,
+    target_handle) by tree.body_index(name), i.e. this project's depth-first body order; nothing is claimed about Isaac Gym's.
+
+    ValueError, naming it: a missing file, a folder name that does not parse, a link missing from the json or from the URDF, an
+    unknown target joint, a target joint that is fixed."""
+    folders = [os.fspath(f) for f in folders]
+    if not folders:
+        raise ValueError("load_drawer_assets: expected at least one folder")
+    cols = {k: [] for k in ("trees", "names", "link", "handle", "dof", "bbox", "xyz", "dir", "lower", "upper")}
+    for folder in folders:
+        name = os.path.basename(os.path.normpath(folder))
+        parts = name.split("-")[-5:-1]
+        if len(parts) != 4:
+            raise ValueError(f"{name!r}: the folder name does not parse as ...-asset-link-handle-joint-...")
+        asset_id, link_name, handle_name, joint_name = parts
+        info_path, urdf_path = os.path.join(folder, "bbox_info.json"), os.path.join(folder, "mobility_new.urdf")
+        for path in (info_path, urdf_path):
+            if not os.path.isfile(path):
+                raise ValueError(f"{path}: missing file")
+        with open(info_path, "rb") as f:
+            info = json.load(f)
+        for key in ("link_name", "bbox_world", "axis_xyz_world", "axis_dir_world"):
+            if key not in info:
+                raise ValueError(f"{info_path}: no {key!r}")
+        for ln in (link_name, handle_name):
+            if ln not in info["link_name"]:
+                raise ValueError(f"{info_path}: unknown link {ln!r}; link_name: {info['link_name']}")
+        link_id, handle_id = info["link_name"].index(link_name), info["link_name"].index(handle_name)
+        tree, unscaled = load_urdf(urdf_path, scale=scale), load_urdf(urdf_path)
+        for ln in (link_name, handle_name):
+            if ln not in tree.names:
+                raise ValueError(f"{urdf_path}: unknown link {ln!r}; links: {tree.names}")
+        if joint_name not in tree.joint_names:
+            raise ValueError(f"{urdf_path}: unknown joint {joint_name!r}; joints: {[j for j in tree.joint_names if j]}")
+        jb = tree.joint_names.index(joint_name)
+        if tree.jtype[jb] == FIXED:
+            raise ValueError(f"{urdf_path}: the target joint {joint_name!r} is fixed")
+        d = int(tree.dof[jb])
+        cols["trees"].append(tree), cols["names"].append((asset_id, link_name, handle_name, joint_name))
+        cols["link"].append(tree.body_index(link_name)), cols["handle"].append(tree.body_index(handle_name)), cols["dof"].append(d)
+        cols["bbox"].append(np.asarray(info["bbox_world"][handle_id], dtype=np.float64).reshape(8, 3) * float(scale))
+        cols["xyz"].append(info["axis_xyz_world"][link_id]), cols["dir"].append(info["axis_dir_world"][link_id])
+        cols["lower"].append(float(unscaled.lower[d])), cols["upper"].append(float(unscaled.upper[d]) * float(scale))
+    return DrawerAssets(folders, scale, cols["trees"], cols["names"], cols["link"], cols["handle"], cols["dof"], cols["bbox"], cols["xyz"],
+                        cols["dir"], cols["lower"], cols["upper"])
 
 
 def _host_ints(x, name, shape):

@@ -97,8 +97,14 @@ def _has_mesh(link):
     return any(g.find("geometry/mesh") is not None for tag in ("collision", "visual") for g in link.findall(tag))
 
 
-def load_urdf(path_or_string):
-    """A URDF file's path, or its text (anything that starts with '<'), -> KinematicTree."""
+def load_urdf(path_or_string, scale=1.0):
+    """A URDF file's path, or its text (anything that starts with '<'), -> KinematicTree.  scale multiplies the joint-origin
+    translations and the lower / upper limits of prismatic joints, and nothing else (not rpy, axes, revolute limits or velocity
+    limits): what the simulator's actor scale does to a tree's kinematics (the reference's set_actor_scale, 0.5 for its cabinets);
+    prismatic joint positions are then in scaled metres.  The default changes nothing."""
+    scale = float(scale)
+    if not scale > 0 or not np.isfinite(scale):
+        raise ValueError(f"scale: expected a positive finite number, got {scale}")
     text = path_or_string
     if not str(text).lstrip().startswith("<"):
         with open(os.fspath(path_or_string), encoding="utf-8") as f:
@@ -145,6 +151,7 @@ def load_urdf(path_or_string):
             if o is not None:
                 t = _floats(o.get("xyz", "0 0 0"), 3, f"joint {jn!r} origin xyz")
                 rpy = _floats(o.get("rpy", "0 0 0"), 3, f"joint {jn!r} origin rpy")
+                t = t * scale
             if jt != FIXED:
                 a = j.find("axis")
                 ax = _floats(a.get("xyz", "1 0 0"), 3, f"joint {jn!r} axis") if a is not None else np.array([1.0, 0.0, 0.0])
@@ -155,6 +162,8 @@ def load_urdf(path_or_string):
                 le = j.find("limit")
                 if le is not None:
                     lo, hi = (-np.inf, np.inf) if j.get("type") == "continuous" else (float(le.get("lower", 0)), float(le.get("upper", 0)))
+                    if jt == PRISMATIC:
+                        lo, hi = lo * scale, hi * scale
                     lim = (lo, hi, float(le.get("velocity", np.inf)))
         joint_names.append(None if j is None else j.get("name"))
         jtype.append(jt), origin_t.append(t), origin_rpy.append(rpy), axis.append(ax), limits.append(lim)
