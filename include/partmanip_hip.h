@@ -770,6 +770,33 @@ int pm_articulation_objects_step_f32(const int32_t* body_off, const int32_t* dof
                                      const uint8_t* reset, const int32_t* target_dof, const int32_t* tip_rows, float dt, int N,
                                      void* stream);
 
+/* ------------------------------------------------------------------ kinematic free body (a stand-in for the simulator's cube)
+ * One free rigid body per environment, moved by a stated kinematic rule in one launch (csrc/free_body.hip): no dynamics, contact or
+ * friction.  It runs after the robot's launch on the same stream and reads the two tip rows as that launch left them.
+ * Per environment e: tip_rows (N, 2) int32, the robot's left and right tip as rows of rigid_body (rb_rows, 13), and body_row (N)
+ * int32, the body's own row (flat rows, as in pm_articulation_objects_step_f32; for a dense (N, nb, 13) tensor row = e nb + body);
+ * root (N, na, 13) whose row obj_actor holds the body's state (c, q_c, velocities), which is what the rules read;  hold, reset (N)
+ * bytes;  grip (N, 8) float32, the caller's state that this entry reads and writes: rel_t (3), rel_q (4), a latch (0 or 1);
+ * default_pose (7);  u (N, 3) in [0, 1) or NULL.
+ * The hand frame H = (p, q_H): p = (p_l + p_r) / 2, q_H = the left tip row's quaternion divided by its norm.  First match wins:
+ *   1. reset[e]:  pose = default_pose; with u:  x, y += (2 u[0, 1] - 1) reset_range, theta = 2 pi u[2] - pi,
+ *      q = default_q o (0, 0, sin theta, cos theta) (the reference's expressions, theta and not theta / 2; not renormalised);
+ *      velocity 0; the latch clears (grip[7] = 0, grip[0..6] kept)
+ *   2. hold[e], latch clear:  rel_t = R_H^T (c - p), rel_q = q_H* o q_c into grip, latch = 1;  the pose is kept, velocity 0
+ *   3. hold[e], latch set:  c' = p + R_H rel_t, q' = unit(q_H o rel_q);  linear velocity (c' - c) / dt, angular velocity the left tip
+ *      row's;  grip is only read
+ *   4. otherwise:  the latch clears, the orientation and x, y are kept;  where z > rest_z:  z' = max(rest_z, z - fall_speed dt) and the
+ *      velocity is (0, 0, (z' - z) / dt, 0, 0, 0);  else z is kept at velocity 0.  fall_speed = 0: a released body stays where it is.
+ * Every output is formed in float64 from the float32 inputs (quaternions (x, y, z, w), Hamilton products) and rounded once; a kept
+ * value keeps its bits.  The same 13 values are written to root[e, obj_actor] and to rigid_body[body_row[e]], and grip[e] as stated;
+ * nothing else is written.  An environment's bits depend on its own rows only and not on N; a NaN stays in its environment.  An
+ * environment with a tip row or body row outside [0, rb_rows) stores nothing and reads nothing out of range.  No synchronisation,
+ * allocation or atomics; stream-ordered.  PM_EINVAL: a NULL pointer other than u, N or na < 1, obj_actor outside [0, na), rb_rows < 1
+ * or >= 2^31, dt <= 0, fall_speed < 0, reset_range < 0, or a NaN among dt, fall_speed, reset_range, rest_z. */
+int pm_free_body_step_f32(float* rigid_body, long rb_rows, const int32_t* tip_rows, const int32_t* body_row, float* root, int na,
+                          int obj_actor, const uint8_t* hold, const uint8_t* reset, float* grip, const float* default_pose,
+                          const float* u, float reset_range, float dt, float rest_z, float fall_speed, int N, void* stream);
+
 /* ------------------------------------------------------------------ K15 fused set-abstraction level
  * One PointNet++ SA level (north_star; not in the reference snapshot, README.md:23,30) as one forward and
  * one backward kernel: ball-query groups of `nsample` = 32 rows [xyz[idx]-centre | feat[idx]] -> Linear C1,

@@ -1,0 +1,220 @@
+"""A vec-env over a task object and the kinematic stand-in: the duck type the runners consume (feeder.py's docstring: `reset() ->
+{mode: (N, D)}`, `step(a) -> (obs, rew, reset, extras)` and the attributes num_envs / num_obs / num_actions / max_episode_length /
+reset_succ / rew_buf / success / progress_buf / train_test_flag / dagger_reward_reset), so that `ppo` / `dagger` can `run()` on the
+simulator-free loop of INTEGRATION.md instead of on noise.
+
+    env = make_grasp_cube_env(cfg_task, num_envs, device, "franka_panda_sdf.urdf", dt, base_pose=..., observers={"mesh_pc": pc_observer(pc)})
+    obs = env.reset()
+    obs, rew, reset, extras = env.step(actions)               # begin_step, sim.step, end_step, the observers; no host synchronisation
+
+Not physics (kinematics.py says what the stand-in is).  What closes the grasp_cube loop is the free body's carry rule
+(csrc/free_body.hip) under the GRASP PREDICATE, a stated choice like `near = 0.01` elsewhere and not a contact:
+hold = is_reached & (|p_l - p_r| <= grasp_width), from the last end_step, grasp_width = 0.055 (the 0.05 cube plus 0.005).  For
+open_drawer the predicate is the task's own extras['is_grasped'] > 0 and the rule is the hold rule of kinematics.py.
+
+A returned observation stays valid until the second step after it (two sets of rows, used in turn): the runners store the previous
+observation after they have stepped."""
+import numpy as np
+import torch
+
+from .kinematics import KinematicSim, ObjectLibrary
+from .tasks import Franka, GraspCubeTensors, MobileFranka, OpenDrawerTensors
+from .urdf import load_urdf
+
+FORWARDED = ("num_envs", "num_actions", "max_episode_length", "reset_succ", "rew_buf", "success", "progress_buf", "train_test_flag",
+             "dagger_reward_reset")
+GRASP_WIDTH = 0.055
+
+
+class _Observer:
+    """width: the columns the observer fills at the head of a row; write(pose_R, pose_T, out): fill them, out a (N, >= width) view."""
+
+    def __init__(self, width, write):
+        self.width, self.write = int(width), write
+
+
+def pc_observer(pc, sel=None):
+    """mesh2pc.PCfromMesh -> 3 * num_points columns.  sel (K) int32 on the device: the subset of the scene's points, drawn once here
+    from torch's CPU generator where None (the reference draws one per call; a fixed one keeps the step free of host work)."""
+    if sel is None:
+        sel = torch.randperm(pc.pts.shape[0])[:pc.num_points].to(torch.int32).to(pc.device)
+    obs = _Observer(3 * sel.shape[-1], lambda R, T, out: pc.query_pc(R, T, out=out, sel=sel))
+    obs.sel = sel
+    return obs
+
+
+def tsdf_observer(tsdf):
+    """mesh2sdf.TSDFfromMesh -> resolution^3 columns."""
+    res = int(tsdf.resolution)
+    return _Observer(res ** 3, lambda R, T, out: tsdf.query_tsdf(R, T, out=out))
+
+
+def depth_pc_observer(cam, volume, num_points=1024):
+    """mesh2depth.DepthFromMesh and a depth2tsdf.TSDFVolume with the same cameras registered -> 3 * num_points columns: the rendered
+    depth images back-projected and thinned (depth2pc returns its own tensor, so this one copies into the row)."""
+    def write(R, T, out):
+        out[:, :3 * num_points].copy_(volume.depth2pc(cam.render(R, T), K=num_points).reshape(out.shape[0], -1))
+    return _Observer(3 * num_points, write)
+
+
+class KinematicEnv:
+    """task: GraspCubeTensors over sim = KinematicSim(free_body=True), or OpenDrawerTensors over KinematicSim(objects=...).
+    observers: {mode: pc_observer(...) / tsdf_observer(...) / depth_pc_observer(...)}; with add_proprio_obs the proprio row is the
+    tail of every such mode's row (for grasp_cube the first mode's tail is written by end_step(obs_out=) itself: no cat).
+    num_obs reports the widths returned.  grasp_width: the grasp predicate's (grasp_cube); hold=False switches the rule off (the
+    cube, or the drawer, then never moves), hold='always' sets the flag in every environment whatever the predicate says (the
+    "held" of kinematics.py: a flag the caller sets).  random_reset: the cube's reset draws u with torch.rand (default: the task cfg's `random_reset`, False)."""
+
+    def __init__(self, task, sim, observers=None, add_proprio_obs=False, grasp_width=GRASP_WIDTH, hold=True, random_reset=False):
+        self.task, self.sim = task, sim
+        self.grasp = isinstance(task, GraspCubeTensors)
+        if self.grasp != bool(getattr(sim, "free_body", False)) or (not self.grasp and sim.objects is None):
+            raise ValueError("KinematicEnv: a GraspCubeTensors needs KinematicSim(free_body=True), an OpenDrawerTensors KinematicSim(objects=...)")
+        if task.num_envs != sim.num_envs:
+            raise ValueError(f"KinematicEnv: the task has {task.num_envs} environments, the sim {sim.num_envs}")
+        self.device = sim.device
+        self.observers = dict(observers or {})
+        if hold not in (True, False, "always"):
+            raise ValueError(f"hold: expected True (the predicate), False or 'always', got {hold!r}")
+        self.add_proprio_obs, self.grasp_width, self.random_reset = bool(add_proprio_obs), float(grasp_width), bool(random_reset)
+        if not hasattr(task, "dagger_reward_reset"):
+            task.dagger_reward_reset = None                   # dagger.py sets it; like the feeder, nothing here reads it
+        N, nd = task.num_envs, task.robot.num_dofs
+        self._Wn, self._Wp = task.num_obs["normal_state"], 7 + 2 * nd
+        self.num_obs = {"normal_state": self._Wn, "proprio_state": self._Wp}
+        tail = self._Wp if self.add_proprio_obs else 0
+        for mode, ob in self.observers.items():
+            if mode in self.num_obs:
+                raise ValueError(f"observers: {mode!r} is the task's own mode")
+            self.num_obs[mode] = ob.width + tail
+        f = dict(dtype=torch.float32, device=self.device)
+        self._slots = [{mode: torch.zeros(N, w, **f) for mode, w in self.num_obs.items()} for _ in range(2)]
+        self._slot = 0
+        self._hold = torch.zeros(N, dtype=torch.bool, device=self.device)
+        self._fixed_hold = None if hold is True else torch.full((N,), hold == "always", dtype=torch.bool, device=self.device)
+        self._gap = torch.zeros(N, **f)
+        if not self.grasp:
+            self._pos_act_all = torch.zeros(sim.D, **f)
+
+    def __getattr__(self, name):                              # only reached for names the env itself does not hold
+        if name in FORWARDED:
+            return getattr(self.task, name)
+        raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        if name in FORWARDED:
+            setattr(self.task, name, value)                   # 'test' on the env switches the task's reset rule
+        else:
+            object.__setattr__(self, name, value)
+
+    # ------------------------------------------------------------------------------------------- the two halves of a step
+    def _observe(self):
+        """end_step into the next set of rows, then the observers and the grasp predicate for the next step."""
+        task, sim = self.task, self.sim
+        self._slot ^= 1
+        rows = self._slots[self._slot]
+        task.obs_buf["normal_state"] = rows["normal_state"]
+        first = next(iter(self.observers), None)
+        if self.grasp:
+            out = rows[first] if self.add_proprio_obs and first is not None else rows["proprio_state"]
+            task.end_step(sim.rigid_body, sim.dof_state, sim.root, obs_out=out)
+            proprio = task.obs_buf["proprio_state"]
+            if proprio.data_ptr() != rows["proprio_state"].data_ptr():
+                rows["proprio_state"].copy_(proprio)
+            r = task.robot
+            torch.linalg.vector_norm(sim.rigid_body[:, r.ltip_rb_index, :3] - sim.rigid_body[:, r.rtip_rb_index, :3], dim=-1, out=self._gap)
+            torch.logical_and(task.is_reached, self._gap <= self.grasp_width, out=self._hold)
+        else:
+            task.end_step(sim.rigid_body, sim.dof_state, sim.root)
+            ns = rows["normal_state"]                         # the tip's seven columns and the joint columns of normal_state
+            rows["proprio_state"][:, :7].copy_(ns[:, :7])
+            rows["proprio_state"][:, 7:].copy_(ns[:, self._Wn - (self._Wp - 7):])
+            torch.gt(task.extras["is_grasped"], 0, out=self._hold)
+        if self.observers:
+            R, T = task.compute_scene_pose()
+            for mode, ob in self.observers.items():
+                ob.write(R, T, rows[mode])
+                if self.add_proprio_obs and not (self.grasp and mode == first):
+                    rows[mode][:, ob.width:].copy_(rows["proprio_state"])
+        return dict(rows)
+
+    def reset(self):
+        """hand_base.reset: every environment starts over; the observation of the first frame.  progress_buf is 0 afterwards."""
+        task, sim = self.task, self.sim
+        if self.grasp:
+            task.reset()
+            sim.set_dof_state(task.robot.default_dof_pos)
+            sim.reset_free_body(u=self._u())
+        else:
+            sim.set_dof_state(task.robot.default_dof_pos)
+            task.reset(sim.dof_state, sim.root, self._pos_act_all)
+            sim.forward()
+        obs = self._observe()
+        task.progress_buf.zero_()
+        return obs
+
+    def _u(self):
+        return torch.rand(self.task.num_envs, 3, dtype=torch.float32, device=self.device) if self.random_reset else None
+
+    def step(self, actions, save_image_path=None):
+        task, sim = self.task, self.sim
+        hold = self._hold if self._fixed_hold is None else self._fixed_hold
+        if self.grasp:
+            pos_act, reset = task.begin_step(actions, sim.dof_state, sim.jacobian)
+            sim.step(pos_act, reset, hold=hold, u=self._u())
+        else:
+            _, reset = task.begin_step(actions, sim.jacobian, sim.dof_state, sim.root, self._pos_act_all)
+            sim.step(task.pos_act, reset, hold=hold)
+        obs = self._observe()
+        return obs, task.rew_buf, task.reset_buf, dict(task.extras)
+
+    def save_scene_pose(self, path=None):
+        """hand_base.save_scene_pose: the posed parts of the last step on the host (a synchronisation; the runners call it in eval)."""
+        rot, pos = self.task.compute_scene_pose()
+        return {"rot": rot.cpu().numpy(), "pos": pos.cpu().numpy()}
+
+
+def _scene(base_pose, dof):
+    bp = np.asarray((0, 0, 0, 0, 0, 0, 1) if base_pose is None else base_pose, dtype=np.float64).reshape(-1)
+    if bp.size != 7:
+        raise ValueError(f"base_pose: expected 7 numbers, got {bp.size}")
+    bp[3:] /= np.linalg.norm(bp[3:])
+    return tuple(float(v) for v in bp), None if dof is None else [float(v) for v in dof]
+
+
+def make_grasp_cube_env(cfg_task, num_envs, device, urdf, dt, base_pose=None, dof=None, observers=None, add_proprio_obs=False,
+                        grasp_width=GRASP_WIDTH, hold=True, max_velocity=None, free_body_pose=(0, 0, 0.025, 0, 0, 0, 1), rest_z=0.025,
+                        fall_speed=0.0, reset_range=0.15):
+    """GraspCubeTensors + KinematicSim(free_body=True) around the robot of `urdf` (a path or a loaded tree; fixed or mobile, through
+    tree.robot_kwargs()).  cfg_task: cfg/tasks/grasp_cube.yaml as a dict; base_pose (7), divided by its norm, and dof (the default
+    joint positions; None: cfg_task['robot']['dof'], else mid-range) place the robot."""
+    tree = load_urdf(urdf) if isinstance(urdf, str) else urdf
+    bp, dof = _scene(base_pose, dof)
+    rcfg = dict(cfg_task.get("robot", {}))
+    if dof is not None:
+        rcfg["dof"] = dof
+    kw = tree.robot_kwargs()
+    robot = (MobileFranka if "mesh_bodies" in kw else Franka)(rcfg, dt, num_envs, device, **kw)
+    task = GraspCubeTensors(num_envs, device, dict(cfg_task, robot=rcfg), dt, num_bodies=tree.num_bodies + 1, robot=robot,
+                            obj_default_pos=tuple(free_body_pose[:3]))
+    sim = KinematicSim(tree, num_envs, device, dt, base_pose=bp, max_velocity=max_velocity, free_body=True,
+                       tips=(robot.ltip_rb_index, robot.rtip_rb_index), free_body_pose=free_body_pose, rest_z=rest_z, fall_speed=fall_speed,
+                       reset_range=reset_range)
+    return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, grasp_width=grasp_width, hold=hold,
+                        random_reset=bool(cfg_task.get("random_reset", False)))
+
+
+def make_open_drawer_env(cfg_task, num_envs, device, urdf, assets, dt, observers=None, add_proprio_obs=False, hold=True,
+                         max_velocity=None):
+    """OpenDrawerTensors + KinematicSim(objects=...) wired as INTEGRATION.md's loop: assets = load_drawer_assets(folders, scale),
+    handed out as env % num_objs; the robot of `urdf` (the mobile Franka of the shipped config, or the fixed one)."""
+    tree = load_urdf(urdf) if isinstance(urdf, str) else urdf
+    envs = assets.for_envs(num_envs)
+    kw = tree.robot_kwargs()
+    robot = (MobileFranka if "mesh_bodies" in kw else Franka)(cfg_task.get("robot", {}), dt, num_envs, device, **kw)
+    rb_mask, dof_mask, B, D = envs.masks(robot.num_rigid_body, robot.num_dofs)
+    task = OpenDrawerTensors(num_envs, device, cfg_task, dt, rb_mask, dof_mask, num_rigid_bodies=B, num_dof_states=D, robot=robot,
+                             **envs.task_kwargs())
+    sim = KinematicSim(tree, num_envs, device, dt, max_velocity=max_velocity, objects=ObjectLibrary(assets.trees, device),
+                       obj_type=envs.obj_id, target_dof=envs.target_dof, tips=(robot.ltip_rb_index, robot.rtip_rb_index))
+    return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, hold=hold)

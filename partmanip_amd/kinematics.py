@@ -8,7 +8,13 @@
 
 It is not physics: no dynamics, no contact, no gravity; the joints follow their position targets (exactly, or at most max_velocity
 fast) inside their limits.  Rows of the tensors that are not the robot's (the cube, a cabinet) belong to the caller and are never
-written after construction.
+written after construction, unless one of the two scenes below is asked for.
+
+With `free_body=True` and tips=(ltip, rtip) every environment also holds one free rigid body (the cube of grasp_cube: the last body
+row, actor 1), and a second launch per step (csrc/free_body.hip through ops.free_body_step) moves it by a stated rule: reset puts it
+back at free_body_pose, `hold` latches its pose in the hand frame (the mean of the two tips, the left tip's orientation) and carries
+it from then on, a released body sinks at fall_speed down to rest_z or, at the default 0, stays where it is (include/partmanip_hip.h
+states it in full).  `grip` (N, 8), the latched relative pose and the latch, belongs to the sim.
 
 With `objects=` (an ObjectLibrary of cabinet trees, tasks.open_drawer.load_drawer_assets) every environment also holds one object of
 its own type, laid out after the robot's rows as tasks.open_drawer.build_masks lays them out, and a second launch per step
@@ -21,6 +27,8 @@ import torch
 
 from . import ops
 from .urdf import FIXED, PRISMATIC, REVOLUTE
+
+RESET_RANGE = 0.15                                            # the cube's random_reset range (the reference's grasp_cube.py:17-21)
 
 
 def _checked_tables(tree):
@@ -162,20 +170,44 @@ class KinematicSim:
     the nb_k rows of its object, its DOF rows likewise, exactly the rows of tasks.open_drawer.build_masks; rb_row0 / dof_row0 /
     obj_rb_row0 / obj_dof_row0 (N) int32 and the totals B and D are attributes.  The object is actor 1: root[:, 1, :7] starts as
     obj_pose ((7) or (N, 7)) and is read by every launch, so a task reset that rewrites it moves the cabinet.  target_dof (N), local to
-    the object, and tips=(ltip, rtip), the robot's tip bodies, are what step(hold=...) needs.  Without objects= nothing changes."""
+    the object, and tips=(ltip, rtip), the robot's tip bodies, are what step(hold=...) needs.  Without objects= nothing changes.
+
+    free_body=True with tips=(ltip, rtip) (the dense layout, or rb_row0 layouts without objects=): one free rigid body per environment,
+    actor 1 and the LAST body row of the dense tensor (num_bodies defaults to nb + 1; with rb_row0 the row after the robot's).  Its
+    rows start at free_body_pose; rest_z, fall_speed and reset_range are the rule's constants (defaults: the task's cube).  grip
+    (N, 8), free_body_row (N) and tip_rows (N, 2) (flat rows) are attributes.  forward() and set_dof_state() leave the body alone."""
 
     def __init__(self, tree, num_envs, device, dt, base_pose=(0, 0, 0, 0, 0, 0, 1), num_bodies=None, num_actors=None, max_velocity=None,
-                 rb_row0=None, dof_row0=None, num_dof_rows=None, objects=None, obj_type=None, obj_pose=None, target_dof=None, tips=None):
+                 rb_row0=None, dof_row0=None, num_dof_rows=None, objects=None, obj_type=None, obj_pose=None, target_dof=None, tips=None,
+                 free_body=False, free_body_pose=(0, 0, 0.025, 0, 0, 0, 1), rest_z=0.025, fall_speed=0.0, reset_range=RESET_RANGE):
         self.art = Articulation(tree, num_envs, device)
         N, nb, nd = int(num_envs), tree.num_bodies, tree.num_dofs
         self.num_envs, self.device, self.dt = N, device, float(dt)
         if not self.dt > 0:
             raise ValueError(f"dt: expected a positive step, got {dt}")
         f = dict(dtype=torch.float32, device=device)
-        self.objects = objects
+        self.objects, self.free_body = objects, bool(free_body)
+        fb_rows = 1 if self.free_body else 0                  # the free body's row comes right after the robot's
+        if self.free_body:
+            if objects is not None:
+                raise ValueError("free_body= and objects= are two scenes: one free body or one cabinet per environment")
+            if tips is None:
+                raise ValueError("free_body= needs tips=(ltip, rtip), the robot's tip bodies")
+            lt, rt = (int(v) for v in tips)
+            if not (0 <= lt < nb and 0 <= rt < nb):
+                raise ValueError(f"tips: expected two of the robot's {nb} bodies, got {tips}")
+            if not float(fall_speed) >= 0 or not float(reset_range) >= 0 or float(rest_z) != float(rest_z):
+                raise ValueError(f"fall_speed {fall_speed} and reset_range {reset_range}: expected non-negative numbers, rest_z {rest_z} a number")
+            self.rest_z, self.fall_speed, self.reset_range = float(rest_z), float(fall_speed), float(reset_range)
+            num_actors = 2 if num_actors is None else num_actors
+            if int(num_actors) < 2:
+                raise ValueError("num_actors: with free_body= the body is actor 1")
+            if rb_row0 is None and num_bodies is None:
+                num_bodies = nb + 1
+            tips = None
         if objects is None:
             if any(a is not None for a in (obj_type, obj_pose, target_dof, tips)):
-                raise ValueError("obj_type, obj_pose, target_dof and tips need objects=")
+                raise ValueError("obj_type, obj_pose, target_dof and tips need objects= (tips: or free_body=)")
             num_actors = 1 if num_actors is None else num_actors
         else:
             if rb_row0 is not None or dof_row0 is not None:
@@ -215,7 +247,7 @@ class KinematicSim:
             raise ValueError("rb_row0 and dof_row0 come together (flat layouts) or not at all")
         self.flat = rb_row0 is not None
         if self.flat:
-            self.rb_row0, need_rb = _row_table(rb_row0, "rb_row0", N, nb, device)
+            self.rb_row0, need_rb = _row_table(rb_row0, "rb_row0", N, nb + fb_rows, device)
             self.dof_row0, need_dof = _row_table(dof_row0, "dof_row0", N, nd, device)
             B = need_rb if num_bodies is None else int(num_bodies)
             D = need_dof if num_dof_rows is None else int(num_dof_rows)
@@ -226,8 +258,8 @@ class KinematicSim:
         else:
             self.rb_row0 = self.dof_row0 = None
             nbt = nb if num_bodies is None else int(num_bodies)
-            if nbt < nb:
-                raise ValueError(f"num_bodies {nbt} below the robot's {nb}")
+            if nbt < nb + fb_rows:
+                raise ValueError(f"num_bodies {nbt} below the robot's {nb}" + (" and the free body's row" if fb_rows else ""))
             self.rigid_body, self.dof_state = torch.zeros(N, nbt, 13, **f), torch.zeros(N, nd, 2, **f)
         self.rigid_body[..., 6] = 1.0
         bp = torch.as_tensor(base_pose, **f)
@@ -246,6 +278,20 @@ class KinematicSim:
                 raise ValueError(f"obj_pose: expected (7) or ({N}, 7), got {tuple(op.shape)}")
             self.root[:, 1, :7] = op
             self.B, self.D = self.rigid_body.shape[0], self.dof_state.shape[0]
+        if self.free_body:
+            # flat rows of rigid_body: dense, the LAST body row of each environment; with rb_row0, the row after the robot's
+            first = self.rb_row0.long() if self.flat else torch.arange(N, device=device) * self.rigid_body.shape[1]
+            body = first + nb if self.flat else first + self.rigid_body.shape[1] - 1
+            self.free_body_row = body.to(torch.int32).contiguous()
+            self.tip_rows = torch.stack([first + lt, first + rt], dim=1).to(torch.int32).contiguous()
+            fp = torch.as_tensor(free_body_pose, **f)
+            if tuple(fp.shape) != (7,):
+                raise ValueError(f"free_body_pose: expected (7), got {tuple(fp.shape)}")
+            self.free_body_pose = fp.contiguous()
+            self.grip = torch.zeros(N, 8, **f)                # rel_t, rel_q, latch: the free-body launch's own state
+            self.root[:, 1, :7] = fp
+            self.rigid_body.view(-1, 13)[self.free_body_row.long(), :7] = fp
+            self._no_flags = torch.zeros(N, dtype=torch.bool, device=device)
         self.jacobian = torch.zeros(N, nb - 1, 6, nd, **f)
         if max_velocity is None:
             self.max_velocity = None
@@ -304,16 +350,35 @@ class KinematicSim:
             self.dof_state.copy_(s)
         return self.forward()
 
-    def step(self, pos_act, reset=None, hold=None):
+    def _free_body_step(self, hold, reset, u):
+        ops.free_body_step(self.rigid_body, self.tip_rows, self.free_body_row, self.root, 1, self._no_flags if hold is None else hold,
+                           self._no_flags if reset is None else reset, self.grip, self.free_body_pose, self.dt, u=u,
+                           reset_range=self.reset_range, rest_z=self.rest_z, fall_speed=self.fall_speed)
+
+    def reset_free_body(self, u=None):
+        """The free body's launch alone with reset set everywhere: every environment's body goes back to free_body_pose, moved by u
+        (N, 3) in [0, 1) where given, at rest and unlatched.  The robot is not touched."""
+        if not self.free_body:
+            raise ValueError("reset_free_body needs free_body=")
+        self._free_body_step(None, ~self._no_flags, u)
+        return self.rigid_body, self.dof_state, self.jacobian
+
+    def step(self, pos_act, reset=None, hold=None, u=None):
         """One launch: the joints move towards pos_act (N, nd), environments with reset set snap to it at rest; returns
         (rigid_body, dof_state, jacobian), updated in place.  With objects= a second launch on the same stream then poses every
         environment's object from root[:, 1, :7] and its DOF rows as they stand (a task reset has already written them).  hold (N)
         bool / uint8, or None: where set (and reset is not) the object's target joint follows the tips' mean velocity of THIS step
-        (the hold rule); where not, it keeps its position at zero velocity; None: the objects' DOF rows are only read."""
+        (the hold rule); where not, it keeps its position at zero velocity; None: the objects' DOF rows are only read.
+        With free_body= the second launch is the free body's (ops.free_body_step): hold (None: nowhere) latches and carries it, reset
+        puts it back at free_body_pose, moved by u (N, 3) in [0, 1) where given (xy inside +-reset_range and a yaw)."""
+        if u is not None and not self.free_body:
+            raise ValueError("u needs free_body=")
         self.art.step(self.dof_state, self.base_pose, targets=pos_act, reset=reset, vmax=self.max_velocity, dt=self.dt,
                       rigid_body=self.rigid_body, jacobian=self.jacobian, rb_row0=self.rb_row0, dof_row0=self.dof_row0)
         if self.objects is not None:
             self._objects_step(reset, hold)
+        elif self.free_body:
+            self._free_body_step(hold, reset, u)
         elif hold is not None:
-            raise ValueError("hold needs objects=")
+            raise ValueError("hold needs objects= or free_body=")
         return self.rigid_body, self.dof_state, self.jacobian

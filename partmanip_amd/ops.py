@@ -1695,6 +1695,39 @@ def articulation_objects_step(body_off, dof_off, parent, jtype, dof, origin_q, o
               "pm_articulation_objects_step_f32")
 
 
+def free_body_step(rigid_body, tip_rows, body_row, root, obj_actor, hold, reset, grip, default_pose, dt, u=None, reset_range=0.15,
+                   rest_z=0.025, fall_speed=0.0):
+    """One free rigid body per environment, moved by the stated rule in one launch (pm_free_body_step_f32, include/partmanip_hip.h),
+    after the robot's launch on the same stream.  rigid_body (N, nb, 13) or flat (B, 13), contiguous; tip_rows (N, 2) and body_row (N)
+    int32 are FLAT rows of it either way; root (N, na, 13); hold, reset (N) bool / uint8; grip (N, 8) float32, read and written;
+    default_pose (7); u (N, 3) in [0, 1) or None.  Written in place: root[:, obj_actor], the body rows, grip."""
+    _one_device("free_body_step", rigid_body, tip_rows, body_row, root, hold, reset, grip, default_pose, u)
+    _f32c(rigid_body, "rigid_body")
+    if rigid_body.dim() not in (2, 3) or rigid_body.shape[-1] != 13 or rigid_body.numel() == 0:
+        raise ValueError(f"rigid_body: expected (N, nb, 13) or (B, 13), got {tuple(rigid_body.shape)}")
+    _f32c(root, "root")
+    N, na = _root_dims(root)
+    if not 0 <= int(obj_actor) < na:
+        raise ValueError(f"obj_actor {obj_actor} outside the {na} actors of root")
+    _vec(tip_rows, "tip_rows", 2 * N, torch.int32)
+    _vec(body_row, "body_row", N, torch.int32)
+    _flags(hold, "hold", N)
+    _flags(reset, "reset", N)
+    _shape_f32c(grip, "grip", (N, 8))
+    _vec(default_pose, "default_pose", 7)
+    if u is not None:
+        _shape_f32c(u, "u", (N, 3))
+    if not float(dt) > 0:
+        raise ValueError(f"dt: expected a positive step, got {dt}")
+    if not float(fall_speed) >= 0 or not float(reset_range) >= 0 or float(rest_z) != float(rest_z):
+        raise ValueError(f"fall_speed {fall_speed} and reset_range {reset_range}: expected non-negative numbers, rest_z {rest_z} a number")
+    with TIMER.bracket("free_body_step"):
+        check(lib.pm_free_body_step_f32(_ptr(rigid_body), rigid_body.numel() // 13, _ptr(tip_rows), _ptr(body_row), _ptr(root), na,
+                                        int(obj_actor), _ptr(hold), _ptr(reset), _ptr(grip), _ptr(default_pose), _ptr(u),
+                                        float(reset_range), float(dt), float(rest_z), float(fall_speed), N, _stream()),
+              "pm_free_body_step_f32")
+
+
 def _index_table(t_, name, N):
     if t_.dtype != torch.int32 or t_.dim() != 2 or t_.shape[0] != N or not t_.is_contiguous():
         raise ValueError(f"{name}: expected a contiguous int32 tensor ({N}, width), got {t_.dtype} {tuple(t_.shape)}")

@@ -62,6 +62,17 @@ class GraspCubeTensors(TaskTensors):
         self._control(actions, dof_state, jacobian)
         return self.pos_act, self.reset_buf
 
+    def reset(self):
+        """The buffer half of hand_base.reset's reset_idx(ones): every environment's targets, counters and flags start over.  The
+        caller then puts the robot at pos_act and the cube at its default pose (KinematicSim.reset_free_body) and calls end_step.
+        Returns pos_act."""
+        self.pos_act.copy_(self.robot.default_dof_pos.expand_as(self.pos_act))
+        self.progress_buf.zero_()
+        self.success.zero_()
+        self.epis_max_rew.fill_(-100.0)
+        self.epis_max_step.zero_()
+        return self.pos_act
+
     def end_step(self, rigid_body, dof_state, root, obs_out=None):
         """hand_base.post_physics_step: progress_buf += 1, then observation rows, reward, flags and part poses in one launch.
         obs_out: a 2-D float32 buffer (N, D) whose last 7 + 2 nd columns receive the proprio row (its head is for query_pc /

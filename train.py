@@ -3,10 +3,12 @@
 
     python train.py --algocfg ppo_pointnet --taskcfg open_drawer --exp_name run0 [--algo.lr 1e-4 ...]
 
-The Isaac Gym tasks are replaced by the synthetic rollout feeder (partmanip_amd/feeder.py);
+The Isaac Gym tasks are replaced by the synthetic rollout feeder (partmanip_amd/feeder.py, `env: feeder`, the default) or by the
+simulator-free task loop (partmanip_amd/envs.py, `--env kinematic --taskcfg grasp_cube --kinematic.urdf PATH [--kinematic.scene JSON]`);
 the runners are the MI355X learners behind the reference's `algorithms.ppo` / `dagger` API.
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N train.py ...`
 (each rank takes num_envs / N envs; gradients are all-reduced over RCCL)."""
+import json
 import os
 import random
 
@@ -62,6 +64,43 @@ def feeder_obs_dims(cfg):
     return dims
 
 
+def kinematic_env(cfg):
+    """`env: kinematic`: the grasp_cube task over the kinematic stand-in (partmanip_amd.envs.make_grasp_cube_env).  cfg['kinematic']:
+    urdf (the robot's file), scene (a json file with optional `dof`, the default joint positions, and `root`, the robot's base pose
+    (7)), dt.  Every argument is checked before anything touches the device."""
+    kin = cfg.get('kinematic') or {}
+    if cfg['task_name'] == 'open_drawer':
+        raise NotImplementedError("env 'kinematic' with --taskcfg open_drawer: the cabinet assets are not shipped, so there is no command "
+                                  "line for it; build the environment with partmanip_amd.envs.make_open_drawer_env(cfg_task, num_envs, "
+                                  "device, urdf, load_drawer_assets(folders), dt)")
+    if cfg['task_name'] != 'grasp_cube':
+        raise ValueError(f"env 'kinematic': expected --taskcfg grasp_cube, got {cfg['task_name']!r}")
+    if not kin.get('urdf'):
+        raise ValueError("env 'kinematic' needs the robot's URDF: pass --kinematic.urdf PATH")
+    mode = cfg['algo']['obs_mode']
+    if mode not in ('normal_state', 'proprio_state'):
+        raise NotImplementedError(f"env 'kinematic' through the command line serves the state modes; obs_mode {mode!r} needs part meshes: "
+                                  "build the environment with make_grasp_cube_env(..., observers={mode: pc_observer(...)})")
+    scene = {}
+    if kin.get('scene'):
+        with open(kin['scene']) as f:
+            scene = json.load(f)
+    from partmanip_amd.envs import make_grasp_cube_env
+    return make_grasp_cube_env(cfg['task'], cfg['algo']['num_envs'], cfg['device'], kin['urdf'], float(kin.get('dt') or 1.0 / 60.0),
+                               base_pose=scene.get('root'), dof=scene.get('dof'))
+
+
+def build_env(cfg, rank=0):
+    """cfg['env']: 'feeder' (the default: synthetic rollout tensors) or 'kinematic'."""
+    kind = cfg.get('env', 'feeder')
+    if kind == 'feeder':
+        return FeederEnv(cfg['algo']['num_envs'], feeder_obs_dims(cfg), num_actions(cfg['task']), cfg['device'],
+                         seed=cfg['seed'] + rank, max_episode_length=cfg['task']['maxEpisodeLength'])
+    if kind == 'kinematic':
+        return kinematic_env(cfg)
+    raise ValueError(f"env: expected 'feeder' or 'kinematic', got {kind!r}")
+
+
 def main():
     cfg = process_cfgs(root=os.path.dirname(os.path.abspath(__file__)))
     rank, world, local = pdist.init_from_env()
@@ -77,8 +116,7 @@ def main():
     if cfg['pretrain'] is not None:
         cfg['algo']['pretrain'] = cfg['pretrain'] = logger.update_resume_path(cfg['pretrain'])
     torch.cuda.set_device(cfg['device'])
-    env = FeederEnv(cfg['algo']['num_envs'], feeder_obs_dims(cfg), num_actions(cfg['task']), cfg['device'],
-                    seed=cfg['seed'] + rank, max_episode_length=cfg['task']['maxEpisodeLength'])
+    env = build_env(cfg, rank)
     runner = {'ppo': ppo, 'dagger': dagger, 'bc': bc}[cfg['algo_name']](env, cfg['algo'], logger)
     runner.run()
     return runner
