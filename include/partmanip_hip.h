@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 161 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 162 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -140,6 +140,37 @@ typedef struct pm_linear_bwd_weight_desc {
 int pm_linear_fwd_group_f32(int n, const pm_linear_fwd_desc* d, void* stream);
 int pm_linear_bwd_data_group_f32(int n, const pm_linear_bwd_data_desc* d, void* stream);
 int pm_linear_bwd_weight_group_f32(int n, const pm_linear_bwd_weight_desc* d, int splits, void* stream);
+/* Which kernel would this call run on?  Each query takes the arguments of its launch entry point without the stream (and
+ * without workspace_bytes), runs the SAME host selection the launch consumes and fills `out`; it launches nothing, makes no HIP
+ * call and needs no device.  Pointers are looked at for alignment only (made-up addresses are fine; the weight-gradient
+ * workspace may be NULL = 16-byte aligned).  Returns what the launch would return for bad arguments.  Tests use it to pin which
+ * member of the kernel family a shape exercises.  Not covered: the gathered / scattered sparse-convolution problems
+ * (pm_sparse_conv_*) and the chain launches (pm_linear_*_chain_f32), which have their own tests. */
+#define PM_LINEAR_PATH_SKINNY 0 /* row-wise VALU kernels, N <= 16 outputs and M >= 256 (forward, data gradient) */
+#define PM_LINEAR_PATH_REG 1    /* MFMA GEMM, operands staged through registers */
+#define PM_LINEAR_PATH_DMA 2    /* MFMA GEMM, operands by LDS-DMA (16-byte loadable, reduction a multiple of 32) */
+typedef struct pm_linear_variant {
+    int path;                          /* PM_LINEAR_PATH_* */
+    int tm, tn;                        /* work-group tile in output rows x columns of the GEMM (0 for the skinny kernels) */
+    int lay;                           /* 0, 1 = the 32 x 128 weight-gradient tile, 2 = the 128 x 32 forward tile */
+    int stages;                        /* LDS ring stages of the LDS-DMA kernels, else 0 */
+    int vec;                           /* 16-byte operand loads (all problems of a group, or none) */
+    int big;                           /* >= 512 tiles of 128 x 128, split-K slabs counted, over the whole group */
+    int grid;                          /* work-groups launched (a group pads every problem's range to a multiple of 8) */
+    int n;                             /* problems */
+    int vecC[PM_LINEAR_GROUP_MAX];     /* per problem: 16-byte epilogue stores (and bias / H loads) */
+    int splits[PM_LINEAR_GROUP_MAX];   /* per problem: split-K slabs */
+    int kchunk[PM_LINEAR_GROUP_MAX];   /* per problem: reduction range of one slab (a multiple of 32; 0 for the skinny kernels) */
+} pm_linear_variant;
+int pm_linear_fwd_variant_f32(const float* X, long ldx, const float* W, long ldw, const float* b, const float* Y, long ldy,
+                              int M, int N, int K, int act, pm_linear_variant* out);
+int pm_linear_bwd_data_variant_f32(const float* dY, long lddy, const float* W, long ldw, const float* H, long ldh,
+                                   const float* dX, long lddx, int M, int N, int K, int act, pm_linear_variant* out);
+int pm_linear_bwd_weight_variant_f32(const float* dY, long lddy, const float* X, long ldx, const float* dW, long lddw,
+                                     const float* db, int M, int N, int K, const void* workspace, pm_linear_variant* out);
+int pm_linear_fwd_group_variant_f32(int n, const pm_linear_fwd_desc* d, pm_linear_variant* out);
+int pm_linear_bwd_data_group_variant_f32(int n, const pm_linear_bwd_data_desc* d, pm_linear_variant* out);
+int pm_linear_bwd_weight_group_variant_f32(int n, const pm_linear_bwd_weight_desc* d, int splits, pm_linear_variant* out);
 /* Chains: n (2..4) CONSECUTIVE layers of one network in one launch -- d[i + 1].X must be d[i].Y (forward: network.py:53-54
  * `self.model(x)`), resp. d[i + 1].dY must be d[i].dX (data gradient, top layer first) -- for the small-step regime, where a
  * kernel boundary between two 15 us layers costs a third of a layer.  A 64-row stripe of layer l + 1 depends on the same 64

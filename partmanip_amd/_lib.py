@@ -37,6 +37,12 @@ SIGNATURES = {
     "pm_linear_fwd_chain_f32": (I, [I, P, P, C.c_size_t, P]),
     "pm_linear_bwd_data_chain_f32": (I, [I, P, P, C.c_size_t, P]),
     "pm_linear_bwd_weight_group_f32": (I, [I, P, I, P]),
+    "pm_linear_fwd_variant_f32": (I, [P, L, P, L, P, P, L, I, I, I, I, P]),
+    "pm_linear_bwd_data_variant_f32": (I, [P, L, P, L, P, L, P, L, I, I, I, I, P]),
+    "pm_linear_bwd_weight_variant_f32": (I, [P, L, P, L, P, L, P, I, I, I, P, P]),
+    "pm_linear_fwd_group_variant_f32": (I, [I, P, P]),
+    "pm_linear_bwd_data_group_variant_f32": (I, [I, P, P]),
+    "pm_linear_bwd_weight_group_variant_f32": (I, [I, P, I, P]),
     "pm_clip_adam_group_f32": (I, [I, P, P]),
     "pm_grad_slab_sum_f32": (I, [P, P, L, L, I, P]),
     "pm_pointnet_packed_elems": (Z, []),
@@ -190,6 +196,15 @@ class LinearBwdWeightDesc(C.Structure):
                 ("M", I), ("N", I), ("K", I), ("dy_cols", I), ("x_cols", I), ("pad_", I)]
 
 
+LINEAR_GROUP_MAX = 8                   # PM_LINEAR_GROUP_MAX
+LINEAR_PATHS = ("skinny", "reg", "dma")                      # PM_LINEAR_PATH_*
+
+
+class LinearVariant(C.Structure):
+    _fields_ = [("path", I), ("tm", I), ("tn", I), ("lay", I), ("stages", I), ("vec", I), ("big", I), ("grid", I), ("n", I),
+                ("vecC", I * LINEAR_GROUP_MAX), ("splits", I * LINEAR_GROUP_MAX), ("kchunk", I * LINEAR_GROUP_MAX)]
+
+
 class ClipAdamDesc(C.Structure):
     _fields_ = [("params", P), ("grads", P), ("exp_avg", P), ("exp_avg_sq", P), ("n", L), ("n_clip", L), ("extra", P),
                 ("extra_stride", L), ("n_sum", L), ("n_extra", I), ("max_norm", F), ("lr", D), ("b1", D), ("b2", D),
@@ -208,7 +223,7 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
-ABI_VERSION = 161                      # == PM_ABI_VERSION in include/partmanip_hip.h (checked by tests/test_capi_symbols.py)
+ABI_VERSION = 162                      # == PM_ABI_VERSION in include/partmanip_hip.h (checked by tests/test_capi_symbols.py)
 if lib.pm_version() != ABI_VERSION:
     raise ImportError(f"{LIB_PATH} is stale: it reports ABI {lib.pm_version()}, this package needs {ABI_VERSION}. "
                       "Rebuild it with `python -m partmanip_amd.build`.")

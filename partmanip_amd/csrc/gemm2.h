@@ -66,6 +66,20 @@ struct Gemm2Chain {
 // shapes do not fit the scheme (the caller then issues the layers one by one).
 int gemm2_chain_launch(Gemm2Chain& ch, bool b_kmajor, void* stream);
 
-// Launches the group (all problems share the orientation); big = 128x128 work-group tiles (for M*N >> chip), else 64x64.
-// Returns PM_OK / PM_E*.  `tag` only names the launch for profiling purposes.
+// Which kernel a group runs on: chosen ONCE, on the host, by gemm2_plan; gemm2_launch only reads it.
+enum { G2_PATH_REG = 1, G2_PATH_DMA = 2 };                                 // (the values of PM_LINEAR_PATH_* in the public header)
+struct Gemm2Plan {
+    int path;                     // G2_PATH_REG: register-staged gemm2_kernel, G2_PATH_DMA: gemm2_dma_kernel
+    int wm, wn, lay;              // template arguments of the kernel (lay: 0, 1 = 32 x 128, 2 = 128 x 32)
+    int TM, TN;                   // work-group tile
+    int stages;                   // LDS ring stages of the LDS-DMA kernels (0 for the register-staged ones)
+    int vec;                      // 16-byte operand loads
+    int big;                      // >= 512 tiles of 128 x 128, split-K slabs counted, over the whole group
+    int gather;                   // some problem has a gathered operand
+    int blocks;                   // grid size (every problem's range padded to a multiple of 8)
+};
+// Host only (no HIP call, pointers looked at for alignment only): checks the group, fills the launcher fields of every problem
+// (Mld / Nld / kchunk defaults, vecC, tiles_m / tiles_n, block0, gsh) and the plan.  Returns PM_OK / PM_E*.
+int gemm2_plan(Gemm2Group& g, bool a_kmajor, bool b_kmajor, Gemm2Plan& pl);
+// Launches the group (all problems share the orientation) as gemm2_plan says.  Returns PM_OK / PM_E*.
 int gemm2_launch(Gemm2Group& g, bool a_kmajor, bool b_kmajor, void* stream);

@@ -833,45 +833,60 @@ int gemm2_chain_launch(Gemm2Chain& ch, bool b_kmajor, void* stream) {
 #define G2_NBUF_DEFAULT 3
 #endif
 template <bool A_KM, bool B_KM, bool GATHER>
-static void g2_launch_dma(const Gemm2Group& g, int wm, int wn, int blocks, void* stream, bool lay1 = false, bool lay2 = false) {
-    const dim3 grid(blocks), blk(512);
+static void g2_launch_dma(const Gemm2Group& g, const Gemm2Plan& pl, void* stream) {
+    const dim3 grid(pl.blocks), blk(512);
+    const int wm = pl.wm, wn = pl.wn;
     if constexpr (A_KM && B_KM) {
-        if (lay1) {
+        if (pl.lay == 1) {
             hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 1, 1, GATHER, 1>), grid, blk, 0, pm_stream(stream), g);
             return;
         }
     }
     if constexpr (!A_KM && !B_KM) {
-        if (lay2) {
+        if (pl.lay == 2) {
             hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 1, 1, GATHER, 2>), grid, blk, 0, pm_stream(stream), g);
             return;
         }
     }
-    if constexpr (!GATHER) {
-        constexpr int nb2 = G2_NBUF_DEFAULT;                                // -DG2_NBUF_DEFAULT=2: the two-stage ring for 128 x 128 tiles (A/B builds)
-        if (wm == 2 && wn == 2 && nb2 == 2) {
-            hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 2, 2, false, 0, 2>), grid, blk, 0, pm_stream(stream), g);
-            return;
+    if (pl.stages == 2) {                                  // (gemm2_plan: -DG2_NBUF_DEFAULT=2, or PM_G2_NBUF=2 in an A/B build)
+        if constexpr (!GATHER) {
+            if (wm == 2 && wn == 2) {
+                hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 2, 2, false, 0, 2>), grid, blk, 0, pm_stream(stream), g);
+                return;
+            }
         }
-    }
-#ifdef G2_TILE_ENV                                         // A/B builds only: PM_G2_NBUF=2 for every tile shape, gathered operands included
-    if (const char* e = getenv("PM_G2_NBUF"); e && atoi(e) == 2) {
+#ifdef G2_TILE_ENV                                         // A/B builds only: two stages for every tile shape, gathered operands included
         if (wm == 2 && wn == 2) hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 2, 2, GATHER, 0, 2>), grid, blk, 0, pm_stream(stream), g);
         else if (wm == 2) hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 2, 1, GATHER, 0, 2>), grid, blk, 0, pm_stream(stream), g);
         else if (wn == 2) hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 1, 2, GATHER, 0, 2>), grid, blk, 0, pm_stream(stream), g);
         else hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 1, 1, GATHER, 0, 2>), grid, blk, 0, pm_stream(stream), g);
         return;
-    }
 #endif
+    }
     if (wm == 2 && wn == 2) hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 2, 2, GATHER>), grid, blk, 0, pm_stream(stream), g);
     else if (wm == 2) hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 2, 1, GATHER>), grid, blk, 0, pm_stream(stream), g);
     else if (wn == 2) hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 1, 2, GATHER>), grid, blk, 0, pm_stream(stream), g);
     else hipLaunchKernelGGL((gemm2_dma_kernel<A_KM, B_KM, 1, 1, GATHER>), grid, blk, 0, pm_stream(stream), g);
 }
 
-template <bool A_KM, bool B_KM>
-static int g2_launch_o(Gemm2Group& g, bool big, void* stream) {
-    bool vec = true;                                                       // 16-byte loads only if every operand of every problem allows them
+// The selection, host only: everything the launch below branches on is decided here and handed over in `pl`.
+int gemm2_plan(Gemm2Group& g, bool A_KM, bool B_KM, Gemm2Plan& pl) {
+    if (g.n < 1 || g.n > GEMM2_MAXP) return PM_EINVAL;
+    long big_tiles = 0;
+    for (int i = 0; i < g.n; ++i) {
+        Gemm2Prob& p = g.p[i];
+        if (p.splits < 1) p.splits = 1;
+        if (p.Mld < p.M) p.Mld = p.M;
+        if (p.Nld < p.N) p.Nld = p.N;
+        if (p.splits == 1) p.kchunk = ((p.K + G2_TK - 1) / G2_TK) * G2_TK;
+        if (p.kchunk <= 0 || p.kchunk % G2_TK != 0 || (long)(p.splits - 1) * p.kchunk >= p.K) return PM_EINVAL;
+        // 16-byte loads: k-contiguous needs K % 4 == 0 (and >= 4), k-major needs rows % 4 == 0 (and >= 4); the callers
+        // have already checked pointer / leading-dimension alignment
+        big_tiles += (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.splits;
+    }
+    const bool big = big_tiles >= 512;                                     // >= 2 work-groups of 128 x 128 per CU
+    if (A_KM && !B_KM) return PM_EUNSUPPORTED;
+    bool vec = true;                                                      // 16-byte loads only if every operand of every problem allows them
     for (int i = 0; i < g.n; ++i) vec = vec && g.p[i].vecA && g.p[i].vecB;
     bool dma = vec, gather = false;
     int maxM = 0, maxN = 0;
@@ -930,16 +945,39 @@ static int g2_launch_o(Gemm2Group& g, bool big, void* stream) {
             const bool kok = A_KM ? (q.kchunk % G2_TK == 0) : (q.K % G2_TK == 0 && q.kchunk % G2_TK == 0);
             if (!q.gidx || !q.gzero || !vec || !kok || q.gC % 4 != 0 || q.gJ < 1 || (long)q.gJ * q.gC != (A_KM ? q.N : q.K)) return PM_EINVAL;
         }
-        if constexpr (A_KM == B_KM) g2_launch_dma<A_KM, B_KM, true>(g, wm, wn, blocks, stream, lay1, lay2);
-        else return PM_EUNSUPPORTED;
+        if (A_KM != B_KM) return PM_EUNSUPPORTED;
+    }
+    pl.path = (dma || gather) ? G2_PATH_DMA : G2_PATH_REG;
+    pl.wm = wm; pl.wn = wn; pl.lay = lay1 ? 1 : (lay2 ? 2 : 0);
+    pl.TM = TM; pl.TN = TN;
+    pl.vec = vec; pl.big = big; pl.gather = gather; pl.blocks = blocks;
+    pl.stages = 0;
+    if (pl.path == G2_PATH_DMA) {
+        pl.stages = 3;
+        if (pl.lay == 0 && !gather && wm == 2 && wn == 2 && G2_NBUF_DEFAULT == 2) pl.stages = 2;   // -DG2_NBUF_DEFAULT=2 (A/B builds)
+#ifdef G2_TILE_ENV                                         // A/B builds only: PM_G2_NBUF=2 for every tile shape, gathered operands included
+        if (const char* e = getenv("PM_G2_NBUF"); e && atoi(e) == 2 && pl.lay == 0) pl.stages = 2;
+#endif
+    }
+    return PM_OK;
+}
+
+template <bool A_KM, bool B_KM>
+static int g2_launch_o(const Gemm2Group& g, const Gemm2Plan& pl, void* stream) {
+    if (pl.path == G2_PATH_DMA) {
+        if (pl.gather) {
+            if constexpr (A_KM == B_KM) g2_launch_dma<A_KM, B_KM, true>(g, pl, stream);
+            else return PM_EUNSUPPORTED;
+        } else {
+            g2_launch_dma<A_KM, B_KM, false>(g, pl, stream);
+        }
         PM_CHECK_LAUNCH();
         return PM_OK;
     }
-    const dim3 grid(blocks), blk(256);
-    if (dma) g2_launch_dma<A_KM, B_KM, false>(g, wm, wn, blocks, stream, lay1, lay2);
-    else if (big && vec) hipLaunchKernelGGL((gemm2_kernel<A_KM, B_KM, 2, 2, true>), grid, blk, 0, pm_stream(stream), g);
-    else if (big) hipLaunchKernelGGL((gemm2_kernel<A_KM, B_KM, 2, 2, false>), grid, blk, 0, pm_stream(stream), g);
-    else if (vec) hipLaunchKernelGGL((gemm2_kernel<A_KM, B_KM, 1, 1, true>), grid, blk, 0, pm_stream(stream), g);
+    const dim3 grid(pl.blocks), blk(256);
+    if (pl.wm == 2 && pl.vec) hipLaunchKernelGGL((gemm2_kernel<A_KM, B_KM, 2, 2, true>), grid, blk, 0, pm_stream(stream), g);
+    else if (pl.wm == 2) hipLaunchKernelGGL((gemm2_kernel<A_KM, B_KM, 2, 2, false>), grid, blk, 0, pm_stream(stream), g);
+    else if (pl.vec) hipLaunchKernelGGL((gemm2_kernel<A_KM, B_KM, 1, 1, true>), grid, blk, 0, pm_stream(stream), g);
     else hipLaunchKernelGGL((gemm2_kernel<A_KM, B_KM, 1, 1, false>), grid, blk, 0, pm_stream(stream), g);
     PM_CHECK_LAUNCH();
     return PM_OK;
@@ -957,21 +995,10 @@ int gemm2_launch(Gemm2Group& g, bool a_kmajor, bool b_kmajor, void* stream) {
 #else
     g.prof = nullptr;
 #endif
-    long big_tiles = 0;
-    for (int i = 0; i < g.n; ++i) {
-        Gemm2Prob& p = g.p[i];
-        if (p.splits < 1) p.splits = 1;
-        if (p.Mld < p.M) p.Mld = p.M;
-        if (p.Nld < p.N) p.Nld = p.N;
-        if (p.splits == 1) p.kchunk = ((p.K + G2_TK - 1) / G2_TK) * G2_TK;
-        if (p.kchunk <= 0 || p.kchunk % G2_TK != 0 || (long)(p.splits - 1) * p.kchunk >= p.K) return PM_EINVAL;
-        // 16-byte loads: k-contiguous needs K % 4 == 0 (and >= 4), k-major needs rows % 4 == 0 (and >= 4); the callers
-        // have already checked pointer / leading-dimension alignment
-        big_tiles += (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.splits;
-    }
-    const bool big = big_tiles >= 512;                                     // >= 2 work-groups of 128 x 128 per CU
-    if (!a_kmajor && !b_kmajor) return g2_launch_o<false, false>(g, big, stream);
-    if (!a_kmajor && b_kmajor) return g2_launch_o<false, true>(g, big, stream);
-    if (a_kmajor && b_kmajor) return g2_launch_o<true, true>(g, big, stream);
-    return PM_EUNSUPPORTED;
+    Gemm2Plan pl{};
+    const int rc = gemm2_plan(g, a_kmajor, b_kmajor, pl);
+    if (rc != PM_OK) return rc;
+    if (!a_kmajor && !b_kmajor) return g2_launch_o<false, false>(g, pl, stream);
+    if (!a_kmajor && b_kmajor) return g2_launch_o<false, true>(g, pl, stream);
+    return g2_launch_o<true, true>(g, pl, stream);
 }

@@ -61,50 +61,128 @@ __global__ __launch_bounds__(SK_T) void skinny_dgrad_kernel(const float* __restr
 }
 
 
+// ---- the selection: which kernel a call runs on ------------------------------------------------------------------------------
+// Each kind of call has ONE host function (`*_select`) that checks the arguments and fills a LinSel: the skinny kernel and its
+// grid, or the GEMM group with the operand orientation.  The launch entry point runs it and launches what it says (the GEMM
+// through gemm2_launch, which takes the tile shape, the loaders, the stores and the grid from gemm2_plan); the
+// pm_linear_*_variant_f32 query runs the same function and gemm2_plan and reports the result -- no HIP call, pointers looked at
+// for alignment only.  The gathered / scattered sparse-convolution problems and the chain launches have no query.
+struct LinSel {
+    int skinny, skinny_grid;             // the VALU kernels for N <= 16 outputs, and their grid
+    bool a_km, b_km;                     // operand orientation of the GEMM
+    Gemm2Group gg;
+};
+
+static int linear_variant_out(LinSel& s, pm_linear_variant* out) {
+    PM_REQUIRE(out);
+    *out = pm_linear_variant{};
+    if (s.skinny) {
+        out->path = PM_LINEAR_PATH_SKINNY;
+        out->vec = 1; out->n = 1; out->grid = s.skinny_grid;
+        out->splits[0] = 1;
+        out->vecC[0] = s.skinny == 2;                                // the data gradient stores float4, the forward one float per lane
+        return PM_OK;
+    }
+    Gemm2Plan pl{};
+    const int rc = gemm2_plan(s.gg, s.a_km, s.b_km, pl);
+    if (rc != PM_OK) return rc;
+    out->path = pl.path; out->tm = pl.TM; out->tn = pl.TN; out->lay = pl.lay; out->stages = pl.stages;
+    out->vec = pl.vec; out->big = pl.big; out->grid = pl.blocks; out->n = s.gg.n;
+    for (int i = 0; i < s.gg.n; ++i) {
+        out->vecC[i] = s.gg.p[i].vecC; out->splits[i] = s.gg.p[i].splits; out->kchunk[i] = s.gg.p[i].kchunk;
+    }
+    return PM_OK;
+}
+
+static int fwd_prob(const pm_linear_fwd_desc& q, Gemm2Prob& g) {
+    PM_REQUIRE(q.X && q.W && q.Y && q.M > 0 && q.N > 0 && q.K > 0 && q.ldx >= q.K && q.ldw >= q.K && q.ldy >= q.N);
+    PM_REQUIRE(q.act >= PM_ACT_NONE && q.act <= PM_ACT_MAX);
+    g.A = q.X; g.lda = q.ldx; g.B = q.W; g.ldb = q.ldw; g.C = q.Y; g.ldc = q.ldy; g.bias = q.b;
+    g.M = q.M; g.N = q.N; g.K = q.K; g.act = q.act; g.epi = G2_EPI_BIAS_ACT; g.splits = 1;
+    g.vecA = (q.K % 4 == 0) && (q.ldx % 4 == 0) && aligned16(q.X);
+    g.vecB = (q.K % 4 == 0) && (q.ldw % 4 == 0) && aligned16(q.W);
+    return PM_OK;
+}
+
+static int bwd_data_prob(const pm_linear_bwd_data_desc& q, Gemm2Prob& g) {
+    PM_REQUIRE(q.dY && q.W && q.dX && q.M > 0 && q.N > 0 && q.K > 0 && q.lddy >= q.N && q.ldw >= q.K && q.lddx >= q.K);
+    PM_REQUIRE(q.act == PM_ACT_NONE || (q.act > PM_ACT_NONE && q.act <= PM_ACT_MAX && q.H && q.ldh >= q.K));
+    // C[M x K] = dY[M x N] * W[N x K]: reduction over N; A = dY (k-contiguous), B = W (k-major)
+    g.A = q.dY; g.lda = q.lddy; g.B = q.W; g.ldb = q.ldw; g.C = q.dX; g.ldc = q.lddx; g.H = q.H; g.ldh = q.ldh;
+    g.M = q.M; g.N = q.K; g.K = q.N; g.act = q.act; g.epi = G2_EPI_MUL_DACT; g.splits = 1;
+    g.vecA = (q.N % 4 == 0) && (q.lddy % 4 == 0) && aligned16(q.dY);
+    g.vecB = (q.K % 4 == 0) && (q.ldw % 4 == 0) && aligned16(q.W);
+    return PM_OK;
+}
+
+static int fwd_select(const pm_linear_fwd_desc& q, LinSel& s) {
+    s = LinSel{};
+    s.gg.n = 1;
+    const int rc = fwd_prob(q, s.gg.p[0]);
+    if (rc != PM_OK) return rc;
+    if (q.M >= 256 && skinny_ok(q.N, q.K, q.X, q.ldx, q.W, q.ldw)) {
+        int nb = (q.M + 3) / 4;                                      // one row per wave (8 rows per work-group measured slower)
+        if (nb > 1024) nb = 1024;
+        s.skinny = 1; s.skinny_grid = nb;
+    }
+    return PM_OK;
+}
+
+static int bwd_data_select(const pm_linear_bwd_data_desc& q, LinSel& s) {
+    s = LinSel{};
+    s.gg.n = 1;
+    s.b_km = true;
+    const int rc = bwd_data_prob(q, s.gg.p[0]);
+    if (rc != PM_OK) return rc;
+    if (q.M >= 256 && skinny_ok(q.N, q.K, q.W, q.ldw, q.dX, q.lddx) && (q.act == PM_ACT_NONE || (q.ldh % 4 == 0 && aligned16(q.H)))) {
+        long nb = ((long)q.M * (q.K / 4) + SK_T - 1) / SK_T;
+        if (nb > 2048) nb = 2048;
+        s.skinny = 2; s.skinny_grid = (int)nb;
+    }
+    return PM_OK;
+}
+
 extern "C" int pm_linear_fwd_f32(const float* X, long ldx, const float* W, long ldw, const float* b, float* Y,
                                  long ldy, int M, int N, int K, int act, void* stream) {
-    PM_REQUIRE(X && W && Y && M > 0 && N > 0 && K > 0 && ldx >= K && ldw >= K && ldy >= N);
-    PM_REQUIRE(act >= PM_ACT_NONE && act <= PM_ACT_MAX);
-    if (M >= 256 && skinny_ok(N, K, X, ldx, W, ldw)) {
-        int nb = (M + 3) / 4;                                        // one row per wave (8 rows per work-group measured slower)
-        if (nb > 1024) nb = 1024;
-        hipLaunchKernelGGL(skinny_fwd_kernel, dim3(nb), dim3(SK_T), (size_t)N * K * 4, pm_stream(stream), X, ldx, W, ldw, b, Y, ldy, M,
-                           N, K, act);
+    LinSel s;
+    const int rc = fwd_select(pm_linear_fwd_desc{X, ldx, W, ldw, b, Y, ldy, M, N, K, act}, s);
+    if (rc != PM_OK) return rc;
+    if (s.skinny) {
+        hipLaunchKernelGGL(skinny_fwd_kernel, dim3(s.skinny_grid), dim3(SK_T), (size_t)N * K * 4, pm_stream(stream), X, ldx, W, ldw, b, Y,
+                           ldy, M, N, K, act);
         PM_CHECK_LAUNCH();
         return PM_OK;
     }
-    Gemm2Group gg{};
-    gg.n = 1;
-    Gemm2Prob& g = gg.p[0];
-    g.A = X; g.lda = ldx; g.B = W; g.ldb = ldw; g.C = Y; g.ldc = ldy; g.bias = b;
-    g.M = M; g.N = N; g.K = K; g.act = act; g.epi = G2_EPI_BIAS_ACT; g.splits = 1;
-    g.vecA = (K % 4 == 0) && (ldx % 4 == 0) && aligned16(X);
-    g.vecB = (K % 4 == 0) && (ldw % 4 == 0) && aligned16(W);
-    return gemm2_launch(gg, false, false, stream);
+    return gemm2_launch(s.gg, s.a_km, s.b_km, stream);
+}
+
+extern "C" int pm_linear_fwd_variant_f32(const float* X, long ldx, const float* W, long ldw, const float* b, const float* Y,
+                                         long ldy, int M, int N, int K, int act, pm_linear_variant* out) {
+    LinSel s;
+    const int rc = fwd_select(pm_linear_fwd_desc{X, ldx, W, ldw, b, (float*)Y, ldy, M, N, K, act}, s);
+    return rc != PM_OK ? rc : linear_variant_out(s, out);
 }
 
 extern "C" int pm_linear_bwd_data_f32(const float* dY, long lddy, const float* W, long ldw, const float* H,
                                       long ldh, float* dX, long lddx, int M, int N, int K, int act,
                                       void* stream) {
-    PM_REQUIRE(dY && W && dX && M > 0 && N > 0 && K > 0 && lddy >= N && ldw >= K && lddx >= K);
-    PM_REQUIRE(act == PM_ACT_NONE || (act > PM_ACT_NONE && act <= PM_ACT_MAX && H && ldh >= K));
-    if (M >= 256 && skinny_ok(N, K, W, ldw, dX, lddx) && (act == PM_ACT_NONE || (ldh % 4 == 0 && aligned16(H)))) {
-        long nb = ((long)M * (K / 4) + SK_T - 1) / SK_T;
-        if (nb > 2048) nb = 2048;
-        hipLaunchKernelGGL(skinny_dgrad_kernel, dim3((unsigned)nb), dim3(SK_T), (size_t)N * K * 4, pm_stream(stream), dY, lddy, W, ldw,
-                           H, ldh, dX, lddx, M, N, K, act);
+    LinSel s;
+    const int rc = bwd_data_select(pm_linear_bwd_data_desc{dY, lddy, W, ldw, H, ldh, dX, lddx, M, N, K, act}, s);
+    if (rc != PM_OK) return rc;
+    if (s.skinny) {
+        hipLaunchKernelGGL(skinny_dgrad_kernel, dim3((unsigned)s.skinny_grid), dim3(SK_T), (size_t)N * K * 4, pm_stream(stream), dY, lddy,
+                           W, ldw, H, ldh, dX, lddx, M, N, K, act);
         PM_CHECK_LAUNCH();
         return PM_OK;
     }
-    Gemm2Group gg{};
-    gg.n = 1;
-    Gemm2Prob& g = gg.p[0];
-    // C[M x K] = dY[M x N] * W[N x K]: reduction over N; A = dY (k-contiguous), B = W (k-major)
-    g.A = dY; g.lda = lddy; g.B = W; g.ldb = ldw; g.C = dX; g.ldc = lddx; g.H = H; g.ldh = ldh;
-    g.M = M; g.N = K; g.K = N; g.act = act; g.epi = G2_EPI_MUL_DACT; g.splits = 1;
-    g.vecA = (N % 4 == 0) && (lddy % 4 == 0) && aligned16(dY);
-    g.vecB = (K % 4 == 0) && (ldw % 4 == 0) && aligned16(W);
-    return gemm2_launch(gg, false, true, stream);
+    return gemm2_launch(s.gg, s.a_km, s.b_km, stream);
+}
+
+extern "C" int pm_linear_bwd_data_variant_f32(const float* dY, long lddy, const float* W, long ldw, const float* H, long ldh,
+                                              const float* dX, long lddx, int M, int N, int K, int act, pm_linear_variant* out) {
+    LinSel s;
+    const int rc = bwd_data_select(pm_linear_bwd_data_desc{dY, lddy, W, ldw, H, ldh, (float*)dX, lddx, M, N, K, act}, s);
+    return rc != PM_OK ? rc : linear_variant_out(s, out);
 }
 
 // ---- weight gradient: split-K over the batch, slab reduction, bias column sums -----------
@@ -182,33 +260,54 @@ __global__ __launch_bounds__(64 * SR_G) void slab_reduce_kernel(const float* __r
     }
 }
 
-extern "C" int pm_linear_bwd_weight_f32(const float* dY, long lddy, const float* X, long ldx, float* dW,
-                                        long lddw, float* db, int M, int N, int K, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
+// workspace_bytes: NULL in the query (the workspace is then looked at for alignment only, and may be absent: a 16-byte aligned one is assumed)
+static int bwd_weight_select(const float* dY, long lddy, const float* X, long ldx, float* dW, long lddw, float* db, int M, int N,
+                             int K, void* workspace, const size_t* workspace_bytes, LinSel& s) {
     PM_REQUIRE(dY && X && dW && M > 0 && N > 0 && K > 0 && lddy >= N && ldx >= K && lddw >= K);
     const int S = bww_splits(M, N, K);
-    if (S > 1 && (!workspace || workspace_bytes < pm_linear_bwd_weight_workspace_bytes(M, N, K))) return PM_EWORKSPACE;
-    Gemm2Group gg{};
-    gg.n = 1;
-    Gemm2Prob& g = gg.p[0];
+    if (workspace_bytes && S > 1 && (!workspace || *workspace_bytes < pm_linear_bwd_weight_workspace_bytes(M, N, K))) return PM_EWORKSPACE;
+    s = LinSel{};
+    s.a_km = s.b_km = true;
+    s.gg.n = 1;
+    Gemm2Prob& g = s.gg.p[0];
     // C[N x K] = dY^T[N x M] * X[M x K]: reduction over M; both operands k-major
     g.A = dY; g.lda = lddy; g.B = X; g.ldb = ldx;
     g.M = N; g.N = K; g.K = M; g.act = 0; g.epi = G2_EPI_PLAIN;
     g.vecA = (N % 4 == 0) && (lddy % 4 == 0) && aligned16(dY);
     g.vecB = (K % 4 == 0) && (ldx % 4 == 0) && aligned16(X);
-    float* bslabs = (float*)workspace + (size_t)S * N * K;
     if (S > 1) {
         int kchunk = (M + S - 1) / S;
         kchunk = ((kchunk + GB_K - 1) / GB_K) * GB_K;
         g.C = (float*)workspace; g.ldc = K; g.kchunk = kchunk; g.slab = (long)N * K; g.splits = S;
-        g.dbias = db ? bslabs : nullptr; g.bslab = N;
+        g.dbias = db ? (float*)workspace + (size_t)S * N * K : nullptr; g.bslab = N;     // the db slabs follow the dW slabs
         if ((long)(S - 1) * kchunk >= M) return PM_EINVAL;
     } else {
         g.C = dW; g.ldc = lddw; g.splits = 1; g.slab = 0;
         g.dbias = db; g.bslab = 0;                     // single slab: the column sums ARE the bias gradient
     }
+    return PM_OK;
+}
+
+extern "C" int pm_linear_bwd_weight_variant_f32(const float* dY, long lddy, const float* X, long ldx, const float* dW, long lddw,
+                                                const float* db, int M, int N, int K, const void* workspace,
+                                                pm_linear_variant* out) {
+    LinSel s;
+    const int rc = bwd_weight_select(dY, lddy, X, ldx, (float*)dW, lddw, (float*)db, M, N, K, (void*)workspace, nullptr, s);
+    return rc != PM_OK ? rc : linear_variant_out(s, out);
+}
+
+extern "C" int pm_linear_bwd_weight_f32(const float* dY, long lddy, const float* X, long ldx, float* dW,
+                                        long lddw, float* db, int M, int N, int K, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    LinSel s;
     {
-        const int rc = gemm2_launch(gg, true, true, stream);
+        const int rc = bwd_weight_select(dY, lddy, X, ldx, dW, lddw, db, M, N, K, workspace, &workspace_bytes, s);
+        if (rc != PM_OK) return rc;
+    }
+    const int S = s.gg.p[0].splits;
+    const float* bslabs = s.gg.p[0].dbias;             // (S > 1: the db slabs in the workspace, or null without db)
+    {
+        const int rc = gemm2_launch(s.gg, s.a_km, s.b_km, stream);
         if (rc != PM_OK) return rc;
     }
     if (S > 1) {
@@ -292,38 +391,51 @@ extern "C" int pm_mlp_bwd_f32(const float* X, long ldx, int M, int n_layers, con
     return PM_OK;
 }
 
-extern "C" int pm_linear_fwd_group_f32(int n, const pm_linear_fwd_desc* d, void* stream) {
+static int fwd_group_select(int n, const pm_linear_fwd_desc* d, LinSel& s) {
     PM_REQUIRE(d && n >= 1 && n <= PM_LINEAR_GROUP_MAX);
-    Gemm2Group gg{};
-    gg.n = n;
+    s = LinSel{};
+    s.gg.n = n;
     for (int i = 0; i < n; ++i) {
-        const pm_linear_fwd_desc& q = d[i];
-        PM_REQUIRE(q.X && q.W && q.Y && q.M > 0 && q.N > 0 && q.K > 0 && q.ldx >= q.K && q.ldw >= q.K && q.ldy >= q.N);
-        PM_REQUIRE(q.act >= PM_ACT_NONE && q.act <= PM_ACT_MAX);
-        Gemm2Prob& g = gg.p[i];
-        g.A = q.X; g.lda = q.ldx; g.B = q.W; g.ldb = q.ldw; g.C = q.Y; g.ldc = q.ldy; g.bias = q.b;
-        g.M = q.M; g.N = q.N; g.K = q.K; g.act = q.act; g.epi = G2_EPI_BIAS_ACT; g.splits = 1;
-        g.vecA = (q.K % 4 == 0) && (q.ldx % 4 == 0) && aligned16(q.X);
-        g.vecB = (q.K % 4 == 0) && (q.ldw % 4 == 0) && aligned16(q.W);
+        const int rc = fwd_prob(d[i], s.gg.p[i]);
+        if (rc != PM_OK) return rc;
     }
-    return gemm2_launch(gg, false, false, stream);
+    return PM_OK;
+}
+
+static int bwd_data_group_select(int n, const pm_linear_bwd_data_desc* d, LinSel& s) {
+    PM_REQUIRE(d && n >= 1 && n <= PM_LINEAR_GROUP_MAX);
+    s = LinSel{};
+    s.gg.n = n;
+    s.b_km = true;
+    for (int i = 0; i < n; ++i) {
+        const int rc = bwd_data_prob(d[i], s.gg.p[i]);
+        if (rc != PM_OK) return rc;
+    }
+    return PM_OK;
+}
+
+extern "C" int pm_linear_fwd_group_f32(int n, const pm_linear_fwd_desc* d, void* stream) {
+    LinSel s;
+    const int rc = fwd_group_select(n, d, s);
+    return rc != PM_OK ? rc : gemm2_launch(s.gg, s.a_km, s.b_km, stream);
+}
+
+extern "C" int pm_linear_fwd_group_variant_f32(int n, const pm_linear_fwd_desc* d, pm_linear_variant* out) {
+    LinSel s;
+    const int rc = fwd_group_select(n, d, s);
+    return rc != PM_OK ? rc : linear_variant_out(s, out);
 }
 
 extern "C" int pm_linear_bwd_data_group_f32(int n, const pm_linear_bwd_data_desc* d, void* stream) {
-    PM_REQUIRE(d && n >= 1 && n <= PM_LINEAR_GROUP_MAX);
-    Gemm2Group gg{};
-    gg.n = n;
-    for (int i = 0; i < n; ++i) {
-        const pm_linear_bwd_data_desc& q = d[i];
-        PM_REQUIRE(q.dY && q.W && q.dX && q.M > 0 && q.N > 0 && q.K > 0 && q.lddy >= q.N && q.ldw >= q.K && q.lddx >= q.K);
-        PM_REQUIRE(q.act == PM_ACT_NONE || (q.act > PM_ACT_NONE && q.act <= PM_ACT_MAX && q.H && q.ldh >= q.K));
-        Gemm2Prob& g = gg.p[i];
-        g.A = q.dY; g.lda = q.lddy; g.B = q.W; g.ldb = q.ldw; g.C = q.dX; g.ldc = q.lddx; g.H = q.H; g.ldh = q.ldh;
-        g.M = q.M; g.N = q.K; g.K = q.N; g.act = q.act; g.epi = G2_EPI_MUL_DACT; g.splits = 1;
-        g.vecA = (q.N % 4 == 0) && (q.lddy % 4 == 0) && aligned16(q.dY);
-        g.vecB = (q.K % 4 == 0) && (q.ldw % 4 == 0) && aligned16(q.W);
-    }
-    return gemm2_launch(gg, false, true, stream);
+    LinSel s;
+    const int rc = bwd_data_group_select(n, d, s);
+    return rc != PM_OK ? rc : gemm2_launch(s.gg, s.a_km, s.b_km, stream);
+}
+
+extern "C" int pm_linear_bwd_data_group_variant_f32(int n, const pm_linear_bwd_data_desc* d, pm_linear_variant* out) {
+    LinSel s;
+    const int rc = bwd_data_group_select(n, d, s);
+    return rc != PM_OK ? rc : linear_variant_out(s, out);
 }
 
 // ---- chains: consecutive layers of ONE network in one launch (gemm2.h: Gemm2Chain) ----------------------------------------
@@ -370,14 +482,15 @@ extern "C" int pm_linear_bwd_data_chain_f32(int n, const pm_linear_bwd_data_desc
     return gemm2_chain_launch(ch, true, stream);
 }
 
-extern "C" int pm_linear_bwd_weight_group_f32(int n, const pm_linear_bwd_weight_desc* d, int splits, void* stream) {
+static int bwd_weight_group_select(int n, const pm_linear_bwd_weight_desc* d, int splits, LinSel& s) {
     PM_REQUIRE(d && n >= 1 && n <= PM_LINEAR_GROUP_MAX && splits >= 1);
-    Gemm2Group gg{};
-    gg.n = n;
+    s = LinSel{};
+    s.a_km = s.b_km = true;
+    s.gg.n = n;
     for (int i = 0; i < n; ++i) {
         const pm_linear_bwd_weight_desc& q = d[i];
         PM_REQUIRE(q.dY && q.X && q.dW && q.M > 0 && q.N > 0 && q.K > 0 && q.lddy >= q.N && q.ldx >= q.K && q.lddw >= q.K);
-        Gemm2Prob& g = gg.p[i];
+        Gemm2Prob& g = s.gg.p[i];
         g.A = q.dY; g.lda = q.lddy; g.B = q.X; g.ldb = q.ldx; g.C = q.dW; g.ldc = q.lddw;
         g.M = q.N; g.N = q.K; g.K = q.M; g.act = 0; g.epi = G2_EPI_PLAIN;
         // loadable columns of the dY / X rows (0 = N / K): see Gemm2Prob::Mld
@@ -395,7 +508,19 @@ extern "C" int pm_linear_bwd_weight_group_f32(int n, const pm_linear_bwd_weight_
             g.kchunk = kchunk; g.slab = q.slab_stride; g.bslab = q.slab_stride;
         }
     }
-    return gemm2_launch(gg, true, true, stream);
+    return PM_OK;
+}
+
+extern "C" int pm_linear_bwd_weight_group_f32(int n, const pm_linear_bwd_weight_desc* d, int splits, void* stream) {
+    LinSel s;
+    const int rc = bwd_weight_group_select(n, d, splits, s);
+    return rc != PM_OK ? rc : gemm2_launch(s.gg, s.a_km, s.b_km, stream);
+}
+
+extern "C" int pm_linear_bwd_weight_group_variant_f32(int n, const pm_linear_bwd_weight_desc* d, int splits, pm_linear_variant* out) {
+    LinSel s;
+    const int rc = bwd_weight_group_select(n, d, splits, s);
+    return rc != PM_OK ? rc : linear_variant_out(s, out);
 }
 
 // ---- sparse convolution = gathered-operand GEMM (sparse_voxel.hip builds the tables) -----------------------------------

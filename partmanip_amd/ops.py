@@ -335,6 +335,42 @@ def linear_bwd_weight_group(items, splits=1):
     check(lib.pm_linear_bwd_weight_group_f32(len(items), arr, int(splits), _stream()), "pm_linear_bwd_weight_group_f32")
 
 
+def linear_variant(kind, problems, splits=1, workspace=0):
+    """Which kernel `kind` would run on (pm_linear_*_variant_f32: host only, no launch, no device needed).
+    kind: "fwd", "bwd_data", "bwd_weight" with ONE problem, or "fwd_group", "bwd_data_group", "bwd_weight_group" with a list.
+    A problem is a dict of the header's descriptor fields (fwd: X ldx W ldw b Y ldy M N K act; bwd_data: dY lddy W ldw H ldh dX
+    lddx M N K act; bwd_weight: dY lddy X ldx dW lddw db M N K, grouped also slab_stride dy_cols x_cols); a pointer field is an
+    address (only its alignment matters, 0 = NULL) or a tensor.  Returns the record as a dict: path ("skinny" / "reg" / "dma"),
+    tm, tn, lay, stages, vec, big, grid, and per-problem lists vecC, splits, kchunk."""
+    from ._lib import LinearFwdDesc, LinearBwdDataDesc, LinearBwdWeightDesc, LinearVariant, LINEAR_PATHS
+    group = kind.endswith("_group")
+    base = kind[:-6] if group else kind
+    cls = {"fwd": LinearFwdDesc, "bwd_data": LinearBwdDataDesc, "bwd_weight": LinearBwdWeightDesc}[base]
+    probs = list(problems) if group else [problems]
+    arr = (cls * len(probs))()
+    for d, q in zip(arr, probs):
+        for k, v in q.items():
+            setattr(d, k, _ptr(v) if isinstance(v, torch.Tensor) else (v or 0))
+    out = LinearVariant()
+    if group:
+        args = (len(probs), arr) + ((int(splits),) if base == "bwd_weight" else ()) + (C.byref(out),)
+    else:
+        d = arr[0]
+        if base == "fwd":
+            args = (d.X, d.ldx, d.W, d.ldw, d.b, d.Y, d.ldy, d.M, d.N, d.K, d.act, C.byref(out))
+        elif base == "bwd_data":
+            args = (d.dY, d.lddy, d.W, d.ldw, d.H, d.ldh, d.dX, d.lddx, d.M, d.N, d.K, d.act, C.byref(out))
+        else:
+            args = (d.dY, d.lddy, d.X, d.ldx, d.dW, d.lddw, d.db, d.M, d.N, d.K,
+                    _ptr(workspace) if isinstance(workspace, torch.Tensor) else workspace, C.byref(out))
+    name = f"pm_linear_{kind}_variant_f32"
+    check(getattr(lib, name)(*args), name)
+    n = out.n
+    return {"path": LINEAR_PATHS[out.path], "tm": out.tm, "tn": out.tn, "lay": out.lay, "stages": out.stages, "vec": out.vec,
+            "big": out.big, "grid": out.grid, "vecC": list(out.vecC[:n]), "splits": list(out.splits[:n]),
+            "kchunk": list(out.kchunk[:n])}
+
+
 def clip_adam_group(items):
     """items: [dict(p, g, m, v, n_clip, max_norm, lr, b1, b2, eps, state, skip_flag, gnorm, ws, extra, extra_stride, n_sum,
     n_extra)]: pm_clip_adam_step_f32 for several optimisers in two launches; `extra` = split-K slabs 1.. of g[:n_sum]."""

@@ -92,7 +92,11 @@ def test_moments_normalize_and_gather():
 # ------------------------------------------------------------------------------- Linear
 @pytest.mark.parametrize("M,N,K,act", [(2048, 512, 53, 1), (2048, 512, 512, 1), (2048, 10, 512, 0), (2048, 1, 512, 0),
                                        (63, 33, 19, 1), (15, 64, 64, 1), (2048, 128, 1031, 1), (300, 32, 128, 0),
-                                       # weight gradients of <= 32 rows: the LDS-DMA kernel's 32 x 128 tile (ragged in N, K, M)
+                                       # weight gradients of <= 32 rows.  What ops.linear_variant says they run on: (4096, 32, 864) and
+                                       # (2048, 16, 200) the LDS-DMA kernel's 32 x 128 tile, 32 slabs; (2048, 32, 64) its 64 x 64 tile (K <=
+                                       # 64); (70000, 32, 1728) and (1000, 28, 132) the register-staged 64 x 64 kernel with 16-byte loads,
+                                       # 32 and 16 slabs: their batch is no multiple of 32, which the LDS-DMA kernels need.  (70000's
+                                       # forward runs the 128 x 32 LDS-DMA tile, its data gradient the 128 x 64 one.)
                                        (4096, 32, 864, 0), (2048, 16, 200, 1), (70000, 32, 1728, 0), (1000, 28, 132, 0), (2048, 32, 64, 0)])
 def test_linear_fwd_bwd(M, N, K, act):
     o = ops()
