@@ -602,6 +602,42 @@ int pm_mesh_depth_render_f32(const float* verts, const int32_t* vert_part, int N
                              float fy, float cx, float cy, int H, int W, float near, float far, float* out, long out_stride,
                              void* stream);
 
+/* ------------------------------------------------------------------ frame camera over the posed part meshes (depth, part label, colour)
+ * The colour image and the IMAGE_SEGMENTATION image of the reference's camera sensors (tasks/hand_base.py:222-227, 355-357; the
+ * robot's bodies carry id 1, load_robot.py:83), rendered from the posed part meshes.  Geometry, pose and camera arguments, the
+ * arithmetic, the hit rule and z are those of pm_mesh_depth_render_f32 above, formula for formula.  Per pixel:
+ *   winner                   the triangle f (its row in faces) of the smallest key (bits(z) << 32) | f over the triangles that hit:
+ *                            nearer first, then the smaller face index -- the tie-break of coincident triangles and of pixel
+ *                            centres exactly on a shared edge.  z > 0, so the unsigned order of the key is that order.
+ *   miss (no triangle hits)  depth = far, seg = miss_label, rgb = (bg_r, bg_g, bg_b)
+ *   hit                      depth = the winner's z: the bits pm_mesh_depth_render_f32 writes
+ *                            p = vert_part[faces[3 f]];  seg = part_label[p], or p when part_label is NULL
+ *   shade (p0, p1, p2 the winner's camera vertices as above; every product, sum and difference rounded on its own, sqrt and / IEEE)
+ *                            e1 = p1 - p0,  e2 = p2 - p0,  g = e1 x e2 (each component a b - c d in the usual order)
+ *                            q = (gx gx + gy gy) + gz gz
+ *                            l = |gz| / sqrt(q) if q > 0 and q is finite, else 0     (a headlight along the optical axis, two-sided)
+ *                            k = ambient + one_minus_ambient l
+ *                            rgb[c] = (uint8)(int)(palette[p][c] k + 0.5f)            palette (M, 3) float32 in [0, 255]
+ *   depth[b * depth_stride + (v H + r) W + c], seg[b * seg_stride + (v H + r) W + c], rgb[b * rgb_stride + 3 ((v H + r) W + c) + ch]
+ * Every output is a function of (triangles, pixel) alone: the bits of all three are defined and repeat; a numpy float32 evaluation
+ * of these lines gives the same bytes.  The headlight and the palette are this project's choices, not Isaac Gym's renderer.
+ * Each of depth, seg and rgb may be NULL (not all three); palette may be NULL only when rgb is.  Strides are per environment, in
+ * elements (depth, seg: >= V H W) or bytes (rgb: >= 3 V H W); nothing past those columns of a row is written.  Skipped triangles
+ * as in pm_mesh_depth_render_f32: they never win a pixel.  workspace: pm_mesh_frame_workspace_bytes(B, V, H, W) = 8 B V H W bytes
+ * of 64-bit keys, 8-byte aligned, caller-owned; its content before and after the call is unspecified.  Three launches (fill,
+ * raster, resolve) on `stream`; 64-bit integer atomicMin, no float atomics; never synchronises.
+ * Before any launch -- PM_EINVAL: the conditions of pm_mesh_depth_render_f32 (with "out" read as: depth, seg and rgb all NULL, or
+ * a given output's stride too short), rgb without palette, ambient or one_minus_ambient < 0 or their sum > 1 (or NaN), a
+ * background component outside [0, 255]; PM_EWORKSPACE: workspace NULL or workspace_bytes too small; PM_EALIGN: workspace not
+ * 8-byte aligned. */
+size_t pm_mesh_frame_workspace_bytes(int B, int V, int H, int W);
+int pm_mesh_frame_render_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F,
+                             const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V, float fx,
+                             float fy, float cx, float cy, int H, int W, float near, float far, const int32_t* part_label,
+                             int miss_label, const float* palette, float ambient, float one_minus_ambient, int bg_r, int bg_g,
+                             int bg_b, float* depth, long depth_stride, int32_t* seg, long seg_stride, uint8_t* rgb,
+                             long rgb_stride, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ grasp_cube task step (simulator side of the learner)
  * The tensor program of the reference's task layer (tasks/grasp_cube.py, tasks/load_robot.py, tasks/hand_base.py:363-392, 431-441)
  * as one launch after physics and one before it.  Neither synchronises, allocates or uses float atomics; both are stream-ordered.

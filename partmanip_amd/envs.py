@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .kinematics import KinematicSim, ObjectLibrary
+from .png import write_png
 from .tasks import Franka, GraspCubeTensors, MobileFranka, OpenDrawerTensors
 from .urdf import load_urdf
 
@@ -57,16 +58,42 @@ def depth_pc_observer(cam, volume, num_points=1024):
     return _Observer(3 * num_points, write)
 
 
+def depth_img_observer(cam):
+    """mesh2depth.DepthFromMesh -> V * im_h * im_w columns: the depth images themselves, rendered straight into the row (the
+    `depth_img` mode of hand_base.py:337-341)."""
+    return _Observer(cam.num_view * cam.im_h * cam.im_w, lambda R, T, out: cam.render(R, T, out=out))
+
+
+def frame_recorder(cam, env=0, view=0):
+    """mesh2depth.DepthFromMesh -> record(pose_R, pose_T, path): the colour image of environment `env` in view `view` written to
+    `path` as a PNG (the image hand_base.py:355-357 saves).  Only that environment is rendered (b = 1, a slice of the poses, rgb
+    only).  The copy to the host SYNCHRONISES the stream; it happens only for a frame somebody asked for."""
+    env, view = int(env), int(view)
+    if not 0 <= view < cam.num_view:
+        raise ValueError(f"frame_recorder: view {view} outside [0, {cam.num_view})")
+
+    def record(pose_R, pose_T, path):
+        if not 0 <= env < pose_R.shape[0]:
+            raise ValueError(f"frame_recorder: environment {env} outside [0, {pose_R.shape[0]})")
+        frame = cam.render_frame(pose_R[env:env + 1], pose_T[env:env + 1], depth=False, seg=False, rgb=True)
+        write_png(path, frame.rgb[0, view].cpu().numpy())
+    return record
+
+
 class KinematicEnv:
     """task: GraspCubeTensors over sim = KinematicSim(free_body=True), or OpenDrawerTensors over KinematicSim(objects=...).
-    observers: {mode: pc_observer(...) / tsdf_observer(...) / depth_pc_observer(...)}; with add_proprio_obs the proprio row is the
+    observers: {mode: pc_observer(...) / tsdf_observer(...) / depth_pc_observer(...) / depth_img_observer(...)}; with add_proprio_obs the proprio row is the
     tail of every such mode's row (for grasp_cube the first mode's tail is written by end_step(obs_out=) itself: no cat).
     num_obs reports the widths returned.  grasp_width: the grasp predicate's (grasp_cube); hold=False switches the rule off (the
     cube, or the drawer, then never moves), hold='always' sets the flag in every environment whatever the predicate says (the
-    "held" of kinematics.py: a flag the caller sets).  random_reset: the cube's reset draws u with torch.rand (default: the task cfg's `random_reset`, False)."""
+    "held" of kinematics.py: a flag the caller sets).  random_reset: the cube's reset draws u with torch.rand (default: the task cfg's `random_reset`, False).
+    recorder: frame_recorder(cam, ...) or None; with one, step(actions, save_image_path=p) writes the frame after the step to p (the
+    runners pass such a path when `save_video` is set); without one the path is ignored."""
 
-    def __init__(self, task, sim, observers=None, add_proprio_obs=False, grasp_width=GRASP_WIDTH, hold=True, random_reset=False):
+    def __init__(self, task, sim, observers=None, add_proprio_obs=False, grasp_width=GRASP_WIDTH, hold=True, random_reset=False,
+                 recorder=None):
         self.task, self.sim = task, sim
+        self.recorder, self._scene_pose = recorder, None
         self.grasp = isinstance(task, GraspCubeTensors)
         if self.grasp != bool(getattr(sim, "free_body", False)) or (not self.grasp and sim.objects is None):
             raise ValueError("KinematicEnv: a GraspCubeTensors needs KinematicSim(free_body=True), an OpenDrawerTensors KinematicSim(objects=...)")
@@ -130,8 +157,9 @@ class KinematicEnv:
             rows["proprio_state"][:, :7].copy_(ns[:, :7])
             rows["proprio_state"][:, 7:].copy_(ns[:, self._Wn - (self._Wp - 7):])
             torch.gt(task.extras["is_grasped"], 0, out=self._hold)
+        self._scene_pose = None
         if self.observers:
-            R, T = task.compute_scene_pose()
+            R, T = self._scene_pose = task.compute_scene_pose()
             for mode, ob in self.observers.items():
                 ob.write(R, T, rows[mode])
                 if self.add_proprio_obs and not (self.grasp and mode == first):
@@ -157,6 +185,8 @@ class KinematicEnv:
         return torch.rand(self.task.num_envs, 3, dtype=torch.float32, device=self.device) if self.random_reset else None
 
     def step(self, actions, save_image_path=None):
+        """One step.  save_image_path: with a recorder set and a path given, the colour frame of the recorder's environment after this
+        step is written there as a PNG; that copies an image to the host and so synchronises, on those steps only."""
         task, sim = self.task, self.sim
         hold = self._hold if self._fixed_hold is None else self._fixed_hold
         if self.grasp:
@@ -166,6 +196,9 @@ class KinematicEnv:
             _, reset = task.begin_step(actions, sim.jacobian, sim.dof_state, sim.root, self._pos_act_all)
             sim.step(task.pos_act, reset, hold=hold)
         obs = self._observe()
+        if save_image_path is not None and self.recorder is not None:
+            R, T = self._scene_pose or task.compute_scene_pose()         # the observers' pose where there are observers
+            self.recorder(R, T, save_image_path)
         return obs, task.rew_buf, task.reset_buf, dict(task.extras)
 
     def save_scene_pose(self, path=None):
@@ -184,7 +217,7 @@ def _scene(base_pose, dof):
 
 def make_grasp_cube_env(cfg_task, num_envs, device, urdf, dt, base_pose=None, dof=None, observers=None, add_proprio_obs=False,
                         grasp_width=GRASP_WIDTH, hold=True, max_velocity=None, free_body_pose=(0, 0, 0.025, 0, 0, 0, 1), rest_z=0.025,
-                        fall_speed=0.0, reset_range=0.15):
+                        fall_speed=0.0, reset_range=0.15, recorder=None):
     """GraspCubeTensors + KinematicSim(free_body=True) around the robot of `urdf` (a path or a loaded tree; fixed or mobile, through
     tree.robot_kwargs()).  cfg_task: cfg/tasks/grasp_cube.yaml as a dict; base_pose (7), divided by its norm, and dof (the default
     joint positions; None: cfg_task['robot']['dof'], else mid-range) place the robot."""
@@ -201,11 +234,11 @@ def make_grasp_cube_env(cfg_task, num_envs, device, urdf, dt, base_pose=None, do
                        tips=(robot.ltip_rb_index, robot.rtip_rb_index), free_body_pose=free_body_pose, rest_z=rest_z, fall_speed=fall_speed,
                        reset_range=reset_range)
     return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, grasp_width=grasp_width, hold=hold,
-                        random_reset=bool(cfg_task.get("random_reset", False)))
+                        random_reset=bool(cfg_task.get("random_reset", False)), recorder=recorder)
 
 
 def make_open_drawer_env(cfg_task, num_envs, device, urdf, assets, dt, observers=None, add_proprio_obs=False, hold=True,
-                         max_velocity=None):
+                         max_velocity=None, recorder=None):
     """OpenDrawerTensors + KinematicSim(objects=...) wired as INTEGRATION.md's loop: assets = load_drawer_assets(folders, scale),
     handed out as env % num_objs; the robot of `urdf` (the mobile Franka of the shipped config, or the fixed one)."""
     tree = load_urdf(urdf) if isinstance(urdf, str) else urdf
@@ -217,4 +250,4 @@ def make_open_drawer_env(cfg_task, num_envs, device, urdf, assets, dt, observers
                              **envs.task_kwargs())
     sim = KinematicSim(tree, num_envs, device, dt, max_velocity=max_velocity, objects=ObjectLibrary(assets.trees, device),
                        obj_type=envs.obj_id, target_dof=envs.target_dof, tips=(robot.ltip_rb_index, robot.rtip_rb_index))
-    return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, hold=hold)
+    return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, hold=hold, recorder=recorder)

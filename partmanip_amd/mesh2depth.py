@@ -3,6 +3,7 @@
 
     cam = DepthFromMesh(num_envs, device, cam_pose (V, 4, 4), cam_intr (3, 3), im_h, im_w)     # register_camera's arguments
     depth = cam.render(pose_R (b, m, 3, 3), pose_T (b, m, 3))  -> (b, V, im_h, im_w)            # positive z-depth, misses at `far`
+    frame = cam.render_frame(pose_R, pose_T)  -> .depth (b, V, im_h, im_w), .seg int32 (b, V, im_h, im_w), .rgb uint8 (b, V, im_h, im_w, 3)
 
 The triangles of every rigid part (PCfromMesh's file list: eight Franka links, hand, two fingers, the object) are kept once on the
 device; every step one call of pm_mesh_depth_render_f32 (csrc/mesh_depth.hip) puts them under their parts' poses -- the same
@@ -13,22 +14,39 @@ unlike the mesh cloud it holds only what a camera sees: hidden surfaces are not 
 
 The image is defined bit for bit by a stated fp32 association (include/partmanip_hip.h), as the mesh cloud is.  Two choices are this
 project's own and have not been checked against the simulator: `near` defaults to 0.01 (Isaac Gym's clip planes are not reproduced),
-and culling is two-sided, both faces of a triangle count (for closed meshes the nearest hit is a front face either way).  Colour,
-segmentation masks and sensor noise are out of scope.
+and culling is two-sided, both faces of a triangle count (for closed meshes the nearest hit is a front face either way).
+
+render_frame (pm_mesh_frame_render_f32, csrc/mesh_frame.hip) keeps the winning triangle of every pixel as well and resolves it into
+the same depth, a part label (the reference's IMAGE_SEGMENTATION, hand_base.py:222-227; `labels=[1] * 11 + [0]` gives its robot
+mask, load_robot.py:83) and a shaded colour (the image hand_base.py:355-357 saves).  All three are defined bit for bit; the nearest
+triangle wins a pixel, the smaller row of `faces` on a tie.  The shading -- a headlight along the optical axis over a fixed palette
+-- is this project's choice, not Isaac Gym's renderer.  Sensor noise and `is_camera_rand` are out of scope.
 """
+import collections
+
 import numpy as np
 import torch
 
 from . import meshio, ops
+
+# The default colours of the parts, cycled: twelve well-separated hues at moderate saturation (0..255).
+PALETTE = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240), (240, 50, 230),
+           (210, 245, 60), (250, 190, 212), (0, 128, 128), (170, 110, 40))
+
+Frame = collections.namedtuple("Frame", "depth seg rgb")
 
 
 class DepthFromMesh:
     """cam_pose (V, 4, 4) camera->world (the camera looks along its +z axis, x to the right, y down), cam_intr (3, 3), im_h, im_w:
     exactly TSDFVolume.register_camera's arguments.  `meshes`: a list of (vertices, faces) used instead of the files under
     `asset_root` (assets/franka_description/meshes/visual/* and assets/objs/cube/cube.obj, read through meshio.load_mesh).
-    near = 0.01 is this project's choice, not Isaac Gym's clip plane; both faces of a triangle are hit (two-sided)."""
+    near = 0.01 is this project's choice, not Isaac Gym's clip plane; both faces of a triangle are hit (two-sided).
+    For render_frame: labels (M,) ints, the seg value of each part (None: the part index), miss_label the seg value where nothing
+    is hit; palette (M, 3) colours in 0..255 (None: PALETTE, cycled); ambient in [0, 1], the share of a colour that a surface seen
+    edge-on keeps; background, the colour where nothing is hit."""
 
-    def __init__(self, num_envs, device, cam_pose, cam_intr, im_h, im_w, asset_root='.', meshes=None, near=0.01, far=100.0):
+    def __init__(self, num_envs, device, cam_pose, cam_intr, im_h, im_w, asset_root='.', meshes=None, near=0.01, far=100.0,
+                 labels=None, miss_label=-1, palette=None, ambient=0.25, background=(255, 255, 255)):
         self.num_envs = num_envs
         self.device = device
         self.asset_root = asset_root
@@ -67,6 +85,26 @@ class DepthFromMesh:
         self.verts = torch.from_numpy(np.ascontiguousarray(np.concatenate(verts))).to(self.device)               # (NV, 3)
         self.vert_part = torch.from_numpy(np.concatenate(part)).to(self.device)                                  # (NV,) int32
         self.faces = torch.from_numpy(np.ascontiguousarray(np.concatenate(faces).astype(np.int32))).to(self.device)   # (F, 3) int32
+        m = self.part_num
+        self.labels = None
+        if labels is not None:
+            lab = np.asarray(labels)
+            if lab.shape != (m,) or lab.dtype.kind not in "iu":
+                raise ValueError(f"labels: expected {m} integers, one per part, got {lab.dtype} {lab.shape}")
+            self.labels = torch.from_numpy(lab.astype(np.int32)).to(self.device)
+        self.miss_label = int(miss_label)
+        pal = np.asarray([PALETTE[i % len(PALETTE)] for i in range(m)] if palette is None else palette, dtype=np.float32)
+        if pal.shape != (m, 3) or not (np.isfinite(pal).all() and pal.min() >= 0 and pal.max() <= 255):
+            raise ValueError(f"palette: expected ({m}, 3) values in [0, 255], got {pal.shape}")
+        self.palette = torch.from_numpy(np.ascontiguousarray(pal)).to(self.device)
+        if not 0.0 <= float(ambient) <= 1.0:
+            raise ValueError(f"ambient: expected a value in [0, 1], got {ambient}")
+        self.ambient = float(np.float32(ambient))                                               # the two float32 values the kernel takes
+        self.one_minus_ambient = float(np.float32(1) - np.float32(ambient))
+        self.background = tuple(int(c) for c in background)
+        if len(self.background) != 3 or min(self.background) < 0 or max(self.background) > 255:
+            raise ValueError(f"background: expected three values in 0..255, got {background}")
+        self._keys = ops.Workspace(self.device)                                                 # render_frame's 64-bit keys, grown on demand
 
     def render(self, pose_R, pose_T, out=None):
         """pose_R [b, m, 3, 3], pose_T [b, m, 3] (any b) -> [b, V, im_h, im_w] float32: the z-depth (not the ray length) of the
@@ -82,3 +120,30 @@ class DepthFromMesh:
         res = ops.mesh_depth_render(self.verts, self.vert_part, self.faces, pose_R, pose_T, self.cam_pose, self.fx, self.fy, self.cx,
                                     self.cy, self.im_h, self.im_w, self.near, self.far, out)
         return res[:, :n].unflatten(1, (self.num_view, self.im_h, self.im_w))
+
+    def render_frame(self, pose_R, pose_T, depth=True, seg=True, rgb=True, out_depth=None):
+        """pose_R [b, m, 3, 3], pose_T [b, m, 3] (any b) -> Frame(depth, seg, rgb) from one rasterisation, each None when switched off:
+        depth [b, V, im_h, im_w] float32, the bits render() gives; seg [b, V, im_h, im_w] int32, labels[part] of the nearest
+        triangle (the smaller row of `faces` on a tie), miss_label where nothing is hit; rgb [b, V, im_h, im_w, 3] uint8, the part's
+        palette colour times ambient + (1 - ambient) |n.z| with n the triangle's unit normal in camera space, `background`
+        where nothing is hit.  out_depth: as render()'s out.  The keys' workspace (8 b V im_h im_w bytes) belongs to this object and
+        is reused while b fits."""
+        b, _ = ops.check_poses(pose_R, pose_T, self.part_num)
+        if not (depth or seg or rgb):
+            raise ValueError("render_frame: depth, seg and rgb are all switched off")
+        if out_depth is not None and not depth:
+            raise ValueError("render_frame: out_depth given with depth switched off")
+        V, h, w = self.num_view, self.im_h, self.im_w
+        n = V * h * w
+        if out_depth is not None:
+            ops._out_rows(out_depth, b, n)                                                     # a bad view is reported before the device
+        ops._req(pose_R, pose_T, out_depth, self.verts)
+        pose_R, pose_T = pose_R.contiguous(), pose_T.contiguous()
+        d, s, c = ops.mesh_frame_render(self.verts, self.vert_part, self.faces, pose_R, pose_T, self.cam_pose, self.fx, self.fy, self.cx,
+                                        self.cy, h, w, self.near, self.far, self._keys.get(8 * b * n), part_label=self.labels,
+                                        miss_label=self.miss_label, palette=self.palette if rgb else None, ambient=self.ambient,
+                                        one_minus_ambient=self.one_minus_ambient, background=self.background,
+                                        depth=(True if out_depth is None else out_depth) if depth else False, seg=bool(seg),
+                                        rgb=bool(rgb))
+        return Frame(None if d is None else d[:, :n].unflatten(1, (V, h, w)), None if s is None else s.unflatten(1, (V, h, w)),
+                     None if c is None else c.unflatten(1, (V, h, w, 3)))

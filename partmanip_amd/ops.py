@@ -129,16 +129,17 @@ def check_poses(pose_R, pose_T, M=None):
     return s[0], s[1]
 
 
-def _out_rows(out, B, n, device=None):
-    """The `out=` rule of the observers: None gives a fresh (B, n) on `device`; otherwise a 2-D float32 view (B, >= n) with unit inner
-    stride and row stride >= n.  Returns (out, the row stride to hand to C); a one-row view may carry any row stride, which counts
-    as n.  The check reads no memory, so the observer classes run it on a given `out` before they ask for the device."""
+def _out_rows(out, B, n, device=None, dtype=torch.float32, name="out"):
+    """The `out=` rule of the observers: None gives a fresh (B, n) on `device`; otherwise a 2-D view (B, >= n) of `dtype` (float32;
+    the frame camera's seg and rgb images are int32 and uint8) with unit inner stride and row stride >= n.  Returns (out, the row
+    stride in elements to hand to C); a one-row view may carry any row stride, which counts as n.  The check reads no memory, so the
+    observer classes run it on a given `out` before they ask for the device."""
     if out is None:
-        return torch.empty(B, n, dtype=torch.float32, device=device), n
+        return torch.empty(B, n, dtype=dtype, device=device), n
     s, st = out.shape, out.stride()
-    if len(s) != 2 or s[0] != B or s[1] < n or out.dtype != torch.float32 or (s[1] != 1 and st[1] != 1) or (B > 1 and st[0] < n):
-        raise ValueError(f"out: expected a float32 view ({B}, >= {n}) with unit inner stride and row stride >= {n}, got {out.dtype} "
-                         f"{tuple(s)} {st}")
+    if len(s) != 2 or s[0] != B or s[1] < n or out.dtype != dtype or (s[1] != 1 and st[1] != 1) or (B > 1 and st[0] < n):
+        raise ValueError(f"{name}: expected a {str(dtype).replace('torch.', '')} view ({B}, >= {n}) with unit inner stride and row "
+                         f"stride >= {n}, got {out.dtype} {tuple(s)} {st}")
     return out, max(st[0], n)
 
 
@@ -1401,13 +1402,8 @@ def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None):
     return out
 
 
-def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h, im_w, near=0.01, far=100.0, out=None):
-    """Depth images of the posed part meshes (pm_mesh_depth_render_f32): verts (NV, 3) canonical vertices of all parts, vert_part (NV)
-    int32, faces (F, 3) int32 into verts, pose_R (B, M, 3, 3), pose_T (B, M, 3), cam_pose (V, 4, 4) camera->world (camera looks along
-    +z, x right, y down).  out: None (a fresh (B, V h w)) or a 2-D float32 view (B, >= V h w) with unit inner stride -- columns past
-    V h w are left alone.  Returns out; out[b, (v h + r) w + c] = z-depth of the nearest surface through pixel (r, c) of view v, `far`
-    where nothing is hit; the fp32 arithmetic is fixed (include/partmanip_hip.h), so the bits repeat."""
-    _one_device("mesh_depth_render", verts, vert_part, faces, pose_R, pose_T, cam_pose, out)
+def _mesh_camera_args(verts, vert_part, faces, pose_R, pose_T, cam_pose, im_h, im_w, near, far):
+    """The geometry, pose and camera checks the depth and the frame camera share.  Returns (NV, B, M, V, im_h, im_w)."""
     for t_, name in ((verts, "verts"), (pose_R, "pose_R"), (pose_T, "pose_T"), (cam_pose, "cam_pose")):
         _f32c(t_, name)
     if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
@@ -1425,12 +1421,72 @@ def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy,
         raise ValueError(f"image size: expected positive im_h and im_w, got {im_h} x {im_w}")
     if not (near > 0 and far > near):
         raise ValueError(f"clip planes: expected 0 < near < far, got near = {near}, far = {far}")
+    return NV, B, M, V, im_h, im_w
+
+
+def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h, im_w, near=0.01, far=100.0, out=None):
+    """Depth images of the posed part meshes (pm_mesh_depth_render_f32): verts (NV, 3) canonical vertices of all parts, vert_part (NV)
+    int32, faces (F, 3) int32 into verts, pose_R (B, M, 3, 3), pose_T (B, M, 3), cam_pose (V, 4, 4) camera->world (camera looks along
+    +z, x right, y down).  out: None (a fresh (B, V h w)) or a 2-D float32 view (B, >= V h w) with unit inner stride -- columns past
+    V h w are left alone.  Returns out; out[b, (v h + r) w + c] = z-depth of the nearest surface through pixel (r, c) of view v, `far`
+    where nothing is hit; the fp32 arithmetic is fixed (include/partmanip_hip.h), so the bits repeat."""
+    _one_device("mesh_depth_render", verts, vert_part, faces, pose_R, pose_T, cam_pose, out)
+    NV, B, M, V, im_h, im_w = _mesh_camera_args(verts, vert_part, faces, pose_R, pose_T, cam_pose, im_h, im_w, near, far)
     out, ldo = _out_rows(out, B, V * im_h * im_w, pose_R.device)
     with TIMER.bracket("mesh_depth_render"):
         check(lib.pm_mesh_depth_render_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], _ptr(pose_R), _ptr(pose_T),
                                            B, M, _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w,
                                            float(near), float(far), _ptr(out), ldo, _stream()), "pm_mesh_depth_render_f32")
     return out
+
+
+def mesh_frame_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h, im_w, near, far, workspace,
+                      part_label=None, miss_label=-1, palette=None, ambient=0.25, one_minus_ambient=None, background=(255, 255, 255),
+                      depth=True, seg=True, rgb=True):
+    """Depth, part-label and shaded colour images of the posed part meshes from one rasterisation (pm_mesh_frame_render_f32); the
+    geometry, pose and camera arguments are mesh_depth_render's.  part_label (M) int32 or None (the part index itself), miss_label
+    for pixels nothing hits; palette (M, 3) float32 in [0, 255], ambient and one_minus_ambient (default 1 - ambient) the headlight's
+    two weights, background three ints in 0..255.  depth / seg / rgb: False (not wanted), True (a fresh (B, V h w) float32 / (B, V h w)
+    int32 / (B, 3 V h w) uint8) or a 2-D view of that type with at least that many columns and unit inner stride; columns past
+    them are left alone.  workspace: a device tensor of at least pm_mesh_frame_workspace_bytes(B, V, h, w) bytes, 8-byte aligned
+    (the library checks both).  Returns (depth, seg, rgb) with None for the ones switched off.  The winner of a pixel is the nearest
+    triangle, the smaller row of `faces` on a tie; all three images are defined bit for bit (include/partmanip_hip.h)."""
+    outs = [o if torch.is_tensor(o) else None for o in (depth, seg, rgb)]
+    _one_device("mesh_frame_render", verts, vert_part, faces, pose_R, pose_T, cam_pose, workspace, part_label, palette, *outs)
+    NV, B, M, V, im_h, im_w = _mesh_camera_args(verts, vert_part, faces, pose_R, pose_T, cam_pose, im_h, im_w, near, far)
+    if depth is False and seg is False and rgb is False:
+        raise ValueError("mesh_frame_render: depth, seg and rgb are all switched off")
+    if part_label is not None and (part_label.dtype != torch.int32 or not part_label.is_contiguous() or tuple(part_label.shape) != (M,)):
+        raise ValueError(f"part_label: expected a contiguous int32 tensor ({M},), got {part_label.dtype} {tuple(part_label.shape)}")
+    if rgb is not False:
+        if palette is None:
+            raise ValueError("palette: needed for the rgb image")
+        _f32c(palette, "palette")
+        if tuple(palette.shape) != (M, 3):
+            raise ValueError(f"palette: expected ({M}, 3), got {tuple(palette.shape)}")
+    one_minus_ambient = 1.0 - float(ambient) if one_minus_ambient is None else float(one_minus_ambient)
+    if not (0.0 <= ambient <= 1.0 and 0.0 <= one_minus_ambient <= 1.0):
+        raise ValueError(f"ambient, one_minus_ambient: expected both in [0, 1], got {ambient}, {one_minus_ambient}")
+    bg = [int(c) for c in background]
+    if len(bg) != 3 or min(bg) < 0 or max(bg) > 255:
+        raise ValueError(f"background: expected three values in 0..255, got {background}")
+    n, dev = V * im_h * im_w, pose_R.device
+    ldd = lds = ldc = 0
+    if depth is not False:
+        depth, ldd = _out_rows(None if depth is True else depth, B, n, dev)
+    if seg is not False:
+        seg, lds = _out_rows(None if seg is True else seg, B, n, dev, torch.int32, "seg")
+    if rgb is not False:
+        rgb, ldc = _out_rows(None if rgb is True else rgb, B, 3 * n, dev, torch.uint8, "rgb")
+    d_, s_, c_ = (None if o is False else o for o in (depth, seg, rgb))
+    with TIMER.bracket("mesh_frame_render"):
+        check(lib.pm_mesh_frame_render_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], _ptr(pose_R), _ptr(pose_T),
+                                           B, M, _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w,
+                                           float(near), float(far), _ptr(part_label), int(miss_label), _ptr(palette), float(ambient),
+                                           one_minus_ambient, bg[0], bg[1], bg[2], _ptr(d_), ldd, _ptr(s_), lds, _ptr(c_), ldc,
+                                           _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
+              "pm_mesh_frame_render_f32")
+    return d_, s_, c_
 
 
 def _vec(t_, name, n, dtype=torch.float32):
