@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 162 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 163 /* bumped whenever an entry point is added or a signature changes */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -144,8 +144,8 @@ int pm_linear_bwd_weight_group_f32(int n, const pm_linear_bwd_weight_desc* d, in
  * without workspace_bytes), runs the SAME host selection the launch consumes and fills `out`; it launches nothing, makes no HIP
  * call and needs no device.  Pointers are looked at for alignment only (made-up addresses are fine; the weight-gradient
  * workspace may be NULL = 16-byte aligned).  Returns what the launch would return for bad arguments.  Tests use it to pin which
- * member of the kernel family a shape exercises.  Not covered: the gathered / scattered sparse-convolution problems
- * (pm_sparse_conv_*) and the chain launches (pm_linear_*_chain_f32), which have their own tests. */
+ * member of the kernel family a shape exercises.  The gathered / scattered sparse-convolution problems have the same query
+ * (pm_sparse_conv_*_variant_f32, below).  Not covered: the chain launches (pm_linear_*_chain_f32), which have their own tests. */
 #define PM_LINEAR_PATH_SKINNY 0 /* row-wise VALU kernels, N <= 16 outputs and M >= 256 (forward, data gradient) */
 #define PM_LINEAR_PATH_REG 1    /* MFMA GEMM, operands staged through registers */
 #define PM_LINEAR_PATH_DMA 2    /* MFMA GEMM, operands by LDS-DMA (16-byte loadable, reduction a multiple of 32) */
@@ -1039,14 +1039,31 @@ int pm_sparse_conv_bwd_data_f32(const float* dY, long lddy, const int32_t* idxT,
 /* Data gradient by scatter, for convolutions whose patches do not overlap (stride == kernel size): every input row is
  * idx[r][j] for at most one (r, j), so  dX[idx[r][j]][c] = (sum_co dY[r][co] * W[co][j*C + c]) * act'(H[idx[r][j]][c])
  * is one GEMM whose epilogue stores each 16-byte piece at its destination row (idx < 0: dropped; rows nobody maps to keep
- * their contents).  W = the tap-major weight (Cout x J*C) of the forward.  accumulate: 0 = overwrite dsrc; 1 = add the (already multiplied) result to what dsrc holds; 2 = dsrc holds a RAW
- * contribution that is added to the gathered sum BEFORE the activation derivative ((skip + strided) * act'). */
+ * their contents).  W = the tap-major weight (Cout x J*C) of the forward. */
 int pm_sparse_conv_bwd_data_scatter_f32(const float* dY, long lddy, const float* W, long ldw, const int32_t* idx, long rows,
                                         int J, int C, int Cout, const float* H, float* dX, int act, void* stream);
 size_t pm_sparse_conv_bwd_weight_workspace_bytes(long rows, int N, int J, int C);
 int pm_sparse_conv_bwd_weight_f32(const float* dY, long lddy, const float* src, long lds, const int32_t* idx, long rows, int J,
                                   int C, float* dW, long lddw, float* db, int N, const float* zero, void* workspace,
                                   size_t workspace_bytes, void* stream);
+/* Which kernel would a pm_sparse_conv_* call run on?  As pm_linear_*_variant_f32: the launch's arguments without the stream (and
+ * without workspace_bytes; the workspace may be NULL = 16-byte aligned), the SAME host selection the launch consumes, no HIP call,
+ * no device, pointers looked at for alignment only; returns what the launch would return for bad arguments.  The weight-gradient
+ * query reports the slab count and the reduction range per slab the call chooses for itself. */
+int pm_sparse_conv_fwd_variant_f32(const float* src, long lds, const int32_t* idx, long rows, int J, int C, const float* W, long ldw,
+                                   const float* b, const float* Y, long ldy, int N, int act, const float* zero,
+                                   pm_linear_variant* out);
+int pm_sparse_conv_bwd_data_variant_f32(const float* dY, long lddy, const int32_t* idxT, long rows, int J, int Cout, const float* Wt,
+                                        long ldwt, const float* H, long ldh, const float* dX, long lddx, int Cin, int act,
+                                        const float* zero, pm_linear_variant* out);
+int pm_sparse_conv_bwd_data_scatter_variant_f32(const float* dY, long lddy, const float* W, long ldw, const int32_t* idx, long rows,
+                                                int J, int C, int Cout, const float* H, const float* dX, int act,
+                                                pm_linear_variant* out);
+int pm_sparse_conv_bwd_weight_variant_f32(const float* dY, long lddy, const float* src, long lds, const int32_t* idx, long rows,
+                                          int J, int C, const float* dW, long lddw, const float* db, int N, const float* zero,
+                                          const void* workspace, pm_linear_variant* out);
+/* accumulate: 0 = overwrite dsrc; 1 = add the (already multiplied) result to what dsrc holds; 2 = dsrc holds a RAW
+ * contribution that is added to the gathered sum BEFORE the activation derivative ((skip + strided) * act'). */
 int pm_rows_gather_bwd_f32(const float* dcols, long ldc, const int32_t* tidx, const int32_t* tslot, int mode, int reverse,
                            int self_col, long rows, int J, int C, const float* y_tanh, long ldy, int accumulate, float* dsrc,
                            long lds, void* stream);

@@ -134,6 +134,10 @@ SIGNATURES = {
     "pm_sparse_conv_bwd_data_scatter_f32": (I, [P, L, P, L, P, L, I, I, I, P, P, I, P]),
     "pm_sparse_conv_bwd_weight_workspace_bytes": (Z, [L, I, I, I]),
     "pm_sparse_conv_bwd_weight_f32": (I, [P, L, P, L, P, L, I, I, P, L, P, I, P, P, Z, P]),
+    "pm_sparse_conv_fwd_variant_f32": (I, [P, L, P, L, I, I, P, L, P, P, L, I, I, P, P]),
+    "pm_sparse_conv_bwd_data_variant_f32": (I, [P, L, P, L, I, I, P, L, P, L, P, L, I, I, P, P]),
+    "pm_sparse_conv_bwd_data_scatter_variant_f32": (I, [P, L, P, L, P, L, I, I, I, P, P, I, P]),
+    "pm_sparse_conv_bwd_weight_variant_f32": (I, [P, L, P, L, P, L, I, I, P, L, P, I, P, P, P]),
     "pm_rows_gather_bwd_f32": (I, [P, L, P, P, I, I, I, L, I, I, P, L, I, P, L, P]),
     "pm_rows_gather_bwd_mapped_f32": (I, [P, L, P, P, I, I, I, L, I, I, P, L, I, P, L, P, P]),
     "pm_rows_gather_bwd_skip_f32": (I, [P, L, P, P, I, I, I, L, I, I, P, L, P, L, P, L, P, P]),
@@ -226,7 +230,7 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
-ABI_VERSION = 162                      # == PM_ABI_VERSION in include/partmanip_hip.h (checked by tests/test_capi_symbols.py)
+ABI_VERSION = 163                      # == PM_ABI_VERSION in include/partmanip_hip.h (checked by tests/test_capi_symbols.py)
 if lib.pm_version() != ABI_VERSION:
     raise ImportError(f"{LIB_PATH} is stale: it reports ABI {lib.pm_version()}, this package needs {ABI_VERSION}. "
                       "Rebuild it with `python -m partmanip_amd.build`.")

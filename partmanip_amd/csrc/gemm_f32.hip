@@ -66,7 +66,7 @@ __global__ __launch_bounds__(SK_T) void skinny_dgrad_kernel(const float* __restr
 // grid, or the GEMM group with the operand orientation.  The launch entry point runs it and launches what it says (the GEMM
 // through gemm2_launch, which takes the tile shape, the loaders, the stores and the grid from gemm2_plan); the
 // pm_linear_*_variant_f32 query runs the same function and gemm2_plan and reports the result -- no HIP call, pointers looked at
-// for alignment only.  The gathered / scattered sparse-convolution problems and the chain launches have no query.
+// for alignment only.  The gathered / scattered sparse-convolution problems do the same further down; the chain launches have no query.
 struct LinSel {
     int skinny, skinny_grid;             // the VALU kernels for N <= 16 outputs, and their grid
     bool a_km, b_km;                     // operand orientation of the GEMM
@@ -527,20 +527,38 @@ extern "C" int pm_linear_bwd_weight_group_variant_f32(int n, const pm_linear_bwd
 // forward:  Y[r][n] = act(sum_{j,c} src[idx[r][j]][c] * W[n][j*C + c] + b[n])        (absent neighbours, idx < 0, contribute 0)
 // weight:   dW[n][j*C + c] = sum_r dY[r][n] * src[idx[r][j]][c],  db[n] = sum_r dY[r][n]
 // The (rows x J*C) operand is gathered by the GEMM's LDS-DMA loader and never exists in HBM.
-extern "C" int pm_sparse_conv_fwd_f32(const float* src, long lds, const int32_t* idx, long rows, int J, int C, const float* W,
-                                      long ldw, const float* b, float* Y, long ldy, int N, int act, const float* zero, void* stream) {
+// Like the Linear calls, each kind has ONE host function (`sparse_*_select`) that checks the arguments and fills the LinSel; the
+// launch consumes it and the pm_sparse_conv_*_variant_f32 query reports it through gemm2_plan (no HIP call, pointers looked at
+// for alignment only).
+static int sparse_fwd_select(const float* src, long lds, const int32_t* idx, long rows, int J, int C, const float* W, long ldw,
+                             const float* b, float* Y, long ldy, int N, int act, const float* zero, LinSel& s) {
     PM_REQUIRE(src && idx && W && Y && zero && rows > 0 && rows < 0x7fffffffL && J > 0 && C > 0 && N > 0 && lds >= C && ldw >= (long)J * C &&
                ldy >= N && act >= PM_ACT_NONE && act <= PM_ACT_MAX);
     PM_REQUIRE(C % 4 == 0 && (J * C) % 32 == 0 && lds % 4 == 0 && ldw % 4 == 0);
     if (!aligned16(src) || !aligned16(W) || !aligned16(zero)) return PM_EALIGN;
-    Gemm2Group gg{};
-    gg.n = 1;
-    Gemm2Prob& g = gg.p[0];
+    s = LinSel{};
+    s.gg.n = 1;
+    Gemm2Prob& g = s.gg.p[0];
     g.A = src; g.lda = lds; g.B = W; g.ldb = ldw; g.C = Y; g.ldc = ldy; g.bias = b;
     g.M = (int)rows; g.N = N; g.K = J * C; g.act = act; g.epi = G2_EPI_BIAS_ACT; g.splits = 1;
     g.vecA = g.vecB = 1;
     g.gidx = idx; g.gzero = zero; g.gJ = J; g.gC = C;
-    return gemm2_launch(gg, false, false, stream);
+    return PM_OK;
+}
+
+extern "C" int pm_sparse_conv_fwd_f32(const float* src, long lds, const int32_t* idx, long rows, int J, int C, const float* W,
+                                      long ldw, const float* b, float* Y, long ldy, int N, int act, const float* zero, void* stream) {
+    LinSel s;
+    const int rc = sparse_fwd_select(src, lds, idx, rows, J, C, W, ldw, b, Y, ldy, N, act, zero, s);
+    return rc != PM_OK ? rc : gemm2_launch(s.gg, s.a_km, s.b_km, stream);
+}
+
+extern "C" int pm_sparse_conv_fwd_variant_f32(const float* src, long lds, const int32_t* idx, long rows, int J, int C, const float* W,
+                                              long ldw, const float* b, const float* Y, long ldy, int N, int act, const float* zero,
+                                              pm_linear_variant* out) {
+    LinSel s;
+    const int rc = sparse_fwd_select(src, lds, idx, rows, J, C, W, ldw, b, (float*)Y, ldy, N, act, zero, s);
+    return rc != PM_OK ? rc : linear_variant_out(s, out);
 }
 
 // data gradient of a submanifold convolution as a gathered GEMM of its own (no (rows x J*C_in) column matrix in HBM):
@@ -549,24 +567,40 @@ extern "C" int pm_sparse_conv_fwd_f32(const float* src, long lds, const int32_t*
 // neighbour J-1-j; rows that are nobody's neighbour -- duplicates -- carry -1 everywhere) and the per-tap transposed weight
 // view Wt[ci][j*Cout + co] = W[co][j*Cin + ci] (row idxT[s][j] read s through ITS tap j), both built by the caller.  H = the layer input's activation (NULL / act
 // NONE: no factor).
-extern "C" int pm_sparse_conv_bwd_data_f32(const float* dY, long lddy, const int32_t* idxT, long rows, int J, int Cout,
-                                           const float* Wt, long ldwt, const float* H, long ldh, float* dX, long lddx, int Cin,
-                                           int act, const float* zero, void* stream) {
+static int sparse_bwd_data_select(const float* dY, long lddy, const int32_t* idxT, long rows, int J, int Cout, const float* Wt,
+                                  long ldwt, const float* H, long ldh, float* dX, long lddx, int Cin, int act, const float* zero,
+                                  LinSel& s) {
     PM_REQUIRE(dY && idxT && Wt && dX && zero && rows > 0 && rows < 0x7fffffffL && J > 0 && Cout > 0 && Cin > 0 && lddy >= Cout &&
                ldwt >= (long)J * Cout && lddx >= Cin && act >= PM_ACT_NONE && act <= PM_ACT_MAX);
     PM_REQUIRE(Cout % 4 == 0 && (J * Cout) % 32 == 0 && lddy % 4 == 0 && ldwt % 4 == 0);
     PM_REQUIRE(!H || ldh >= Cin);
     if (!aligned16(dY) || !aligned16(Wt) || !aligned16(zero)) return PM_EALIGN;
-    Gemm2Group gg{};
-    gg.n = 1;
-    Gemm2Prob& g = gg.p[0];
+    s = LinSel{};
+    s.gg.n = 1;
+    Gemm2Prob& g = s.gg.p[0];
     g.A = dY; g.lda = lddy; g.B = Wt; g.ldb = ldwt; g.C = dX; g.ldc = lddx;
     g.M = (int)rows; g.N = Cin; g.K = J * Cout; g.splits = 1;
     g.epi = (H && act != PM_ACT_NONE) ? G2_EPI_MUL_DACT : G2_EPI_PLAIN;
     g.act = act; g.H = H; g.ldh = ldh;
     g.vecA = g.vecB = 1;
     g.gidx = idxT; g.gzero = zero; g.gJ = J; g.gC = Cout;
-    return gemm2_launch(gg, false, false, stream);
+    return PM_OK;
+}
+
+extern "C" int pm_sparse_conv_bwd_data_f32(const float* dY, long lddy, const int32_t* idxT, long rows, int J, int Cout,
+                                           const float* Wt, long ldwt, const float* H, long ldh, float* dX, long lddx, int Cin,
+                                           int act, const float* zero, void* stream) {
+    LinSel s;
+    const int rc = sparse_bwd_data_select(dY, lddy, idxT, rows, J, Cout, Wt, ldwt, H, ldh, dX, lddx, Cin, act, zero, s);
+    return rc != PM_OK ? rc : gemm2_launch(s.gg, s.a_km, s.b_km, stream);
+}
+
+extern "C" int pm_sparse_conv_bwd_data_variant_f32(const float* dY, long lddy, const int32_t* idxT, long rows, int J, int Cout,
+                                                   const float* Wt, long ldwt, const float* H, long ldh, const float* dX, long lddx,
+                                                   int Cin, int act, const float* zero, pm_linear_variant* out) {
+    LinSel s;
+    const int rc = sparse_bwd_data_select(dY, lddy, idxT, rows, J, Cout, Wt, ldwt, H, ldh, (float*)dX, lddx, Cin, act, zero, s);
+    return rc != PM_OK ? rc : linear_variant_out(s, out);
 }
 
 // data gradient of a convolution whose patches do not overlap (stride == kernel size), by SCATTER: output row r wrote to /
@@ -575,63 +609,102 @@ extern "C" int pm_sparse_conv_bwd_data_f32(const float* dY, long lddy, const int
 // is one plain GEMM (K = Cout) whose epilogue stores each 16-byte piece at its destination row -- no column-gradient matrix,
 // no col2im pass.  W is the layer's tap-major weight (Cout x J*C), the forward's B operand as it is.  Destination rows that
 // no (r, j) maps to keep their contents (the caller zero-fills when the geometry leaves any).
-extern "C" int pm_sparse_conv_bwd_data_scatter_f32(const float* dY, long lddy, const float* W, long ldw, const int32_t* idx,
-                                                   long rows, int J, int C, int Cout, const float* H, float* dX, int act,
-                                                   void* stream) {
+static int sparse_bwd_scatter_select(const float* dY, long lddy, const float* W, long ldw, const int32_t* idx, long rows, int J, int C,
+                                     int Cout, const float* H, float* dX, int act, LinSel& s) {
     PM_REQUIRE(dY && W && idx && dX && rows > 0 && rows < 0x7fffffffL && J > 0 && C > 0 && Cout > 0 && lddy >= Cout &&
                ldw >= (long)J * C && act >= PM_ACT_NONE && act <= PM_ACT_MAX);
     PM_REQUIRE(C % 4 == 0 && Cout % 4 == 0 && lddy % 4 == 0 && ldw % 4 == 0);
     if (!aligned16(dY) || !aligned16(W) || !aligned16(dX) || (H && !aligned16(H))) return PM_EALIGN;
-    Gemm2Group gg{};
-    gg.n = 1;
-    Gemm2Prob& g = gg.p[0];
+    s = LinSel{};
+    s.b_km = true;
+    s.gg.n = 1;
+    Gemm2Prob& g = s.gg.p[0];
     g.A = dY; g.lda = lddy; g.B = W; g.ldb = ldw; g.C = dX; g.ldc = C;
     g.M = (int)rows; g.N = J * C; g.K = Cout; g.splits = 1;
     g.epi = (H && act != PM_ACT_NONE) ? G2_EPI_MUL_DACT : G2_EPI_PLAIN;
     g.act = act; g.H = H; g.ldh = C;
     g.vecA = g.vecB = 1;
     g.sidx = idx; g.sJ = J; g.sC = C;
-    return gemm2_launch(gg, false, true, stream);
+    return PM_OK;
+}
+
+extern "C" int pm_sparse_conv_bwd_data_scatter_f32(const float* dY, long lddy, const float* W, long ldw, const int32_t* idx,
+                                                   long rows, int J, int C, int Cout, const float* H, float* dX, int act,
+                                                   void* stream) {
+    LinSel s;
+    const int rc = sparse_bwd_scatter_select(dY, lddy, W, ldw, idx, rows, J, C, Cout, H, dX, act, s);
+    return rc != PM_OK ? rc : gemm2_launch(s.gg, s.a_km, s.b_km, stream);
+}
+
+extern "C" int pm_sparse_conv_bwd_data_scatter_variant_f32(const float* dY, long lddy, const float* W, long ldw, const int32_t* idx,
+                                                           long rows, int J, int C, int Cout, const float* H, const float* dX, int act,
+                                                           pm_linear_variant* out) {
+    LinSel s;
+    const int rc = sparse_bwd_scatter_select(dY, lddy, W, ldw, idx, rows, J, C, Cout, H, (float*)dX, act, s);
+    return rc != PM_OK ? rc : linear_variant_out(s, out);
 }
 
 extern "C" size_t pm_sparse_conv_bwd_weight_workspace_bytes(long rows, int N, int J, int C) {
     return pm_linear_bwd_weight_workspace_bytes((int)rows, N, J * C);
 }
 
-extern "C" int pm_sparse_conv_bwd_weight_f32(const float* dY, long lddy, const float* src, long lds, const int32_t* idx, long rows,
-                                             int J, int C, float* dW, long lddw, float* db, int N, const float* zero,
-                                             void* workspace, size_t workspace_bytes, void* stream) {
+// workspace_bytes: NULL in the query (as in bwd_weight_select)
+static int sparse_bwd_weight_select(const float* dY, long lddy, const float* src, long lds, const int32_t* idx, long rows, int J, int C,
+                                    float* dW, long lddw, float* db, int N, const float* zero, void* workspace,
+                                    const size_t* workspace_bytes, LinSel& s) {
     PM_REQUIRE(dY && src && idx && dW && zero && rows > 0 && rows < 0x7fffffffL && J > 0 && C > 0 && N > 0 && lds >= C && lddy >= N &&
                lddw >= (long)J * C);
     PM_REQUIRE(C % 4 == 0 && N % 4 == 0 && lds % 4 == 0 && lddy % 4 == 0);
     if (!aligned16(src) || !aligned16(dY) || !aligned16(zero)) return PM_EALIGN;
     const int M = (int)rows, K = J * C;
     const int S = bww_splits(M, N, K);
-    if (S > 1 && (!workspace || workspace_bytes < pm_linear_bwd_weight_workspace_bytes(M, N, K))) return PM_EWORKSPACE;
-    Gemm2Group gg{};
-    gg.n = 1;
-    Gemm2Prob& g = gg.p[0];
+    if (workspace_bytes && S > 1 && (!workspace || *workspace_bytes < pm_linear_bwd_weight_workspace_bytes(M, N, K))) return PM_EWORKSPACE;
+    s = LinSel{};
+    s.a_km = s.b_km = true;
+    s.gg.n = 1;
+    Gemm2Prob& g = s.gg.p[0];
     g.A = dY; g.lda = lddy; g.B = src; g.ldb = lds;
     g.M = N; g.N = K; g.K = M; g.act = 0; g.epi = G2_EPI_PLAIN;
     g.vecA = g.vecB = 1;
     g.gidx = idx; g.gzero = zero; g.gJ = J; g.gC = C;
-    float* bslabs = (float*)workspace + (size_t)S * N * K;
     if (S > 1) {
         int kchunk = (M + S - 1) / S;
         kchunk = ((kchunk + GB_K - 1) / GB_K) * GB_K;
         g.C = (float*)workspace; g.ldc = K; g.kchunk = kchunk; g.slab = (long)N * K; g.splits = S;
-        g.dbias = db ? bslabs : nullptr; g.bslab = N;
+        g.dbias = db ? (float*)workspace + (size_t)S * N * K : nullptr; g.bslab = N;     // the db slabs follow the dW slabs
     } else {
         g.C = dW; g.ldc = lddw; g.splits = 1; g.kchunk = ((M + 31) / 32) * 32; g.slab = 0;
         g.dbias = db; g.bslab = 0;
     }
-    const int rc = gemm2_launch(gg, true, true, stream);
+    return PM_OK;
+}
+
+extern "C" int pm_sparse_conv_bwd_weight_f32(const float* dY, long lddy, const float* src, long lds, const int32_t* idx, long rows,
+                                             int J, int C, float* dW, long lddw, float* db, int N, const float* zero,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+    LinSel s;
+    {
+        const int rc = sparse_bwd_weight_select(dY, lddy, src, lds, idx, rows, J, C, dW, lddw, db, N, zero, workspace, &workspace_bytes, s);
+        if (rc != PM_OK) return rc;
+    }
+    const int S = s.gg.p[0].splits, K = J * C;
+    const float* bslabs = (const float*)workspace + (size_t)S * N * K;
+    const int rc = gemm2_launch(s.gg, s.a_km, s.b_km, stream);
     if (rc != PM_OK) return rc;
     if (S > 1) {
         const long ne = (long)N * K + (db ? N : 0);
         hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((ne + 63) / 64)), dim3(64 * SR_G), 0, pm_stream(stream),
-                           (const float*)workspace, S, (long)N * K, dW, lddw, N, K, (const float*)bslabs, db);
+                           (const float*)workspace, S, (long)N * K, dW, lddw, N, K, bslabs, db);
         PM_CHECK_LAUNCH();
     }
     return PM_OK;
+}
+
+extern "C" int pm_sparse_conv_bwd_weight_variant_f32(const float* dY, long lddy, const float* src, long lds, const int32_t* idx,
+                                                     long rows, int J, int C, const float* dW, long lddw, const float* db, int N,
+                                                     const float* zero, const void* workspace, pm_linear_variant* out) {
+    LinSel s;
+    const int rc = sparse_bwd_weight_select(dY, lddy, src, lds, idx, rows, J, C, (float*)dW, lddw, (float*)db, N, zero, (void*)workspace,
+                                            nullptr, s);
+    return rc != PM_OK ? rc : linear_variant_out(s, out);
 }

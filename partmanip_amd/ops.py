@@ -372,6 +372,35 @@ def linear_variant(kind, problems, splits=1, workspace=0):
             "kchunk": list(out.kchunk[:n])}
 
 
+_SPARSE_VARIANT_FIELDS = {
+    "fwd": ("src", "lds", "idx", "rows", "J", "C", "W", "ldw", "b", "Y", "ldy", "N", "act", "zero"),
+    "bwd_data": ("dY", "lddy", "idxT", "rows", "J", "Cout", "Wt", "ldwt", "H", "ldh", "dX", "lddx", "Cin", "act", "zero"),
+    "bwd_scatter": ("dY", "lddy", "W", "ldw", "idx", "rows", "J", "C", "Cout", "H", "dX", "act"),
+    "bwd_weight": ("dY", "lddy", "src", "lds", "idx", "rows", "J", "C", "dW", "lddw", "db", "N", "zero", "workspace"),
+}
+
+
+def sparse_conv_variant(kind, problem):
+    """Which kernel a sparse-convolution call would run on (pm_sparse_conv_*_variant_f32: host only, no launch, no device needed).
+    kind: "fwd", "bwd_data", "bwd_scatter" (pm_sparse_conv_bwd_data_scatter_f32) or "bwd_weight".  `problem` is a dict of the launch's
+    arguments by their header names, without the stream and workspace_bytes (a missing field is 0 / NULL); a pointer field is an
+    address (only its alignment matters, 0 = NULL) or a tensor.  Returns the same dict as linear_variant."""
+    from ._lib import LinearVariant, LINEAR_PATHS
+    fields = _SPARSE_VARIANT_FIELDS[kind]
+    unknown = set(problem) - set(fields)
+    if unknown:
+        raise ValueError(f"sparse_conv_variant({kind!r}): unknown fields {sorted(unknown)}")
+    vals = [problem.get(k) for k in fields]
+    out = LinearVariant()
+    name = {"fwd": "pm_sparse_conv_fwd_variant_f32", "bwd_data": "pm_sparse_conv_bwd_data_variant_f32",
+            "bwd_scatter": "pm_sparse_conv_bwd_data_scatter_variant_f32", "bwd_weight": "pm_sparse_conv_bwd_weight_variant_f32"}[kind]
+    check(getattr(lib, name)(*[_ptr(v) if isinstance(v, torch.Tensor) else (v or 0) for v in vals], C.byref(out)), name)
+    n = out.n
+    return {"path": LINEAR_PATHS[out.path], "tm": out.tm, "tn": out.tn, "lay": out.lay, "stages": out.stages, "vec": out.vec,
+            "big": out.big, "grid": out.grid, "vecC": list(out.vecC[:n]), "splits": list(out.splits[:n]),
+            "kchunk": list(out.kchunk[:n])}
+
+
 def clip_adam_group(items):
     """items: [dict(p, g, m, v, n_clip, max_norm, lr, b1, b2, eps, state, skip_flag, gnorm, ws, extra, extra_stride, n_sum,
     n_extra)]: pm_clip_adam_step_f32 for several optimisers in two launches; `extra` = split-K slabs 1.. of g[:n_sum]."""

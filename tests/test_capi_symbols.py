@@ -32,7 +32,9 @@ def test_header_declares_the_survey_minimum_symbol_set():
                  "pm_linear_bwd_weight_f32", "pm_pointnet_enc_fwd_f32", "pm_pointnet_enc_bwd_f32",
                  "pm_ppo_actor_loss_fwd_bwd_f32", "pm_value_loss_fwd_bwd_f32", "pm_mse_tanh_loss_fwd_bwd_f32",
                  "pm_clip_adam_step_f32", "pm_fps_f32", "pm_ball_query_f32", "pm_group_points_f32",
-                 "pm_group_points_bwd_f32", "pm_version"):
+                 "pm_group_points_bwd_f32", "pm_version",
+                 "pm_sparse_conv_fwd_variant_f32", "pm_sparse_conv_bwd_data_variant_f32",
+                 "pm_sparse_conv_bwd_data_scatter_variant_f32", "pm_sparse_conv_bwd_weight_variant_f32"):
         assert need in fns, need
 
 

@@ -1077,9 +1077,15 @@ def test_maxpool_rows_value_and_lowest_arg(G, ns, C):
     np.testing.assert_array_equal(arg.cpu().numpy(), xr.argmax(1).astype(np.int32))
 
 
+# What ops.sparse_conv_variant reports for these shapes (all LDS-DMA, 16-byte stores; tests/sparse_conv_variant_cases.py has a case for
+# every variant the selector can name):
+#   forward and data gradient: the small 64 x 64 tile for the first eight -- 50 001 rows x 32 or 64 columns are 391 tiles of
+#     128 x 128, not the 512 that count as big;
+#   weight gradient: 64 x 64 for N = 64 and 128, the 32 x 128 tile (lay 1) for N <= 32, in 3 to 32 slabs, never big.
 @pytest.mark.parametrize("rows,J,C,N", [(1000, 27, 32, 32), (333, 8, 32, 64), (4097, 27, 64, 64), (700, 32, 4, 32), (129, 27, 32, 128),
                                         (50001, 27, 64, 32), (3000, 32, 32, 16), (2049, 8, 64, 32),
-                                        # >= 512 big tiles and <= 32 output columns: the forward's 128 x 32 tile (4 x 1 waves)
+                                        # >= 512 big tiles and <= 32 columns: the 128 x 32 tile (lay 2, 4 x 1 waves), in the forward
+                                        # and in the data gradient alike (C = 4 or 32 columns there)
                                         (70001, 32, 4, 32), (66000, 3, 32, 32), (65600, 27, 32, 32)])
 def test_sparse_conv_entry_points_against_torch(rows, J, C, N):
     """The three gathered-GEMM entry points (the (rows x J*C) operand exists only inside the LDS-DMA loader) against a plain
@@ -1121,6 +1127,7 @@ def test_sparse_conv_entry_points_against_torch(rows, J, C, N):
     assert float(dx[5].abs().max()) == 0.0
 
 
+# (all three: the small 64 x 64 LDS-DMA tile by ops.sparse_conv_variant -- Cout = N is a multiple of 32 and no grid reaches 512 big tiles)
 @pytest.mark.parametrize("rows,J,C,N", [(700, 28, 16, 32), (129, 8, 32, 64), (2050, 27, 32, 32)])
 def test_sparse_conv_bwd_data_scatter_against_torch(rows, J, C, N):
     """Data gradient by scatter (non-overlapping patches: every destination row has at most one (r, j)): against a torch

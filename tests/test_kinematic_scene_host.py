@@ -188,7 +188,7 @@ def test_header_ctypes_abi_and_wrapper_argument_order():
     import ctypes
     from partmanip_amd import _lib, ops
     src = header_text()
-    assert int(re.search(r"#define PM_ABI_VERSION (\d+)", src).group(1)) == 162 == _lib.ABI_VERSION == _lib.lib.pm_version()
+    assert int(re.search(r"#define PM_ABI_VERSION (\d+)", src).group(1)) == 163 == _lib.ABI_VERSION == _lib.lib.pm_version()
     m = re.search(r"int pm_articulation_objects_step_f32\(([^;]*?)\)\s*;", re.sub(r"/\*.*?\*/", "", src, flags=re.S), flags=re.S)
     names = [a.replace("*", " ").split()[-1] for a in m.group(1).split(",")]
     assert names == ["body_off", "dof_off", "K", "total_bodies", "total_dofs", "max_nb", "max_nd", "parent", "jtype", "dof", "origin_q",
