@@ -217,6 +217,14 @@ int pm_pointnet_enc_fwd_screen_f32(const float* x, long ldx, int B, int P, int C
                                    const float* b1, const float* b2, const float* b3, const float* packed,
                                    const void* packed_screen, int max_mean, float* feat, long ldf, int32_t* argmax,
                                    float* h2_save, unsigned long long* counters, void* stream);
+/* The same kernel with the order of its independent per-tile work chosen by the caller: schedule 0 = all eight waves in lock-step,
+ * 1 = waves 4-7 staggered against their SIMD partners (csrc/pointnet_enc_screen.h, SCHED).  Every output is bit-identical under
+ * both; pm_pointnet_enc_fwd_screen_f32 runs the measured default.  Any other schedule is refused (-1) before a launch.
+ * PM_ABI_VERSION stays 163 with this addition (no existing signature changed): a loader that wants it looks the symbol up. */
+int pm_pointnet_enc_fwd_screen_sched_f32(const float* x, long ldx, int B, int P, int C, int sub_mean, const float* W1,
+                                         const float* b1, const float* b2, const float* b3, const float* packed,
+                                         const void* packed_screen, int max_mean, float* feat, long ldf, int32_t* argmax,
+                                         float* h2_save, unsigned long long* counters, int schedule, void* stream);
 /* OPT-IN split-bf16 forward: same contract as pm_pointnet_enc_fwd_f32, but the two big per-point GEMMs run as
  * a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on bf16 MFMAs with fp32 accumulation (~1e-5 relative instead of ~1e-7;
  * 5.3x less matrix-pipe time).  P must be a multiple of 128.  `packed` = pm_pointnet_packed_bf3_bytes() bytes

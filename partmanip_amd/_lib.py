@@ -51,6 +51,7 @@ SIGNATURES = {
     "pm_pointnet_packed_screen_bytes": (Z, []),
     "pm_pointnet_pack_weights_screen": (I, [P, P, P, P]),
     "pm_pointnet_enc_fwd_screen_f32": (I, [P, L, I, I, I, I, P, P, P, P, P, P, I, P, L, P, P, P, P]),
+    "pm_pointnet_enc_fwd_screen_sched_f32": (I, [P, L, I, I, I, I, P, P, P, P, P, P, I, P, L, P, P, P, I, P]),
     "pm_pointnet_packed_bf3_bytes": (Z, []),
     "pm_pointnet_pack_weights_bf3": (I, [P, P, P, P]),
     "pm_pointnet_enc_fwd_bf3": (I, [P, L, I, I, I, I, P, P, P, P, P, I, P, L, P, P, P]),

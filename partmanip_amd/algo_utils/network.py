@@ -347,6 +347,10 @@ class PointNet(_HipNet):
         screen = _os.environ.get("PARTMANIP_PN_SCREEN")
         self.screen = bool(net_cfg.get('screen', PN_SCREEN_DEFAULT)) if screen is None else screen == "1"
         self.screen_counters = None
+        # PARTMANIP_PN_SCREEN_STAGGER=0|1: the screened kernel's schedule (0 = lock-step, 1 = waves 4-7 staggered; bit-identical
+        # results) for A/B in one build; unset = the library's default
+        stagger = _os.environ.get("PARTMANIP_PN_SCREEN_STAGGER")
+        self.screen_schedule = None if stagger is None else int(stagger)
         object.__setattr__(self, "_act", code)
         object.__setattr__(self, "_packed_s", None)
         object.__setattr__(self, "_head", _LinearChain([self.final_mlp[0], self.final_mlp[2], self.final_mlp[4]], code))
@@ -407,7 +411,8 @@ class PointNet(_HipNet):
             ops.pointnet_pack_screen(self.mlp[4].weight.data, self.mlp[4].bias.data, self._packed_s)
             ops.pointnet_enc_fwd_screen(x, self.point_num, self.in_channels, self.substract_mean, self.mlp[0].weight.data,
                                         self.mlp[0].bias.data, self.mlp[2].bias.data, self.mlp[4].bias.data, packed,
-                                        self._packed_s, self.max_mean_concat, feat, argmax, h2, self.screen_counters)
+                                        self._packed_s, self.max_mean_concat, feat, argmax, h2, self.screen_counters,
+                                        self.screen_schedule)
         else:
             ops.pointnet_enc_fwd(x, self.point_num, self.in_channels, self.substract_mean, self.mlp[0].weight.data,
                                  self.mlp[0].bias.data, self.mlp[2].bias.data, self.mlp[4].bias.data, packed,

@@ -32,7 +32,7 @@
 //
 // Work-group: 8 waves own one cloud; wave w owns channels [64 w, 64 w + 64) in layer 3 and lane l of it keeps the running
 // (vmax, imax) of channel 64 w + l.  LDS: fp32 H tile 66.5 KB (H1, then H2) + bf16 hi / lo planes of H2 67.6 KB + survivor
-// lists 8 KB + 4 KB = 146.5 KB: one work-group per CU, two waves per SIMD.
+// list 4 KB + 4 KB = 142.5 KB: one work-group per CU, two waves per SIMD.
 #pragma once
 
 typedef __bf16 ps_bf16x8 __attribute__((ext_vector_type(8)));
@@ -47,6 +47,17 @@ typedef __bf16 ps_bf16x8 __attribute__((ext_vector_type(8)));
 #define PS_OFF_W3 (4 * PS_P3 + 8192)
 #define PS_OFF_EPS (PS_OFF_W3 + PN_C3 * PN_C2 * 4)
 #define PS_PACKED_BYTES (PS_OFF_EPS + PN_C3 * 4)
+#ifndef PS_ABLATE
+#define PS_ABLATE 0          // profiling only (wrong results, same launch; tools/build_ab.py): 1 = no layer 1, 2 = no layer-2 MFMAs, 4 = no tanh / split
+                             // arithmetic in the layer-2 epilogue, 8 = no plane stores after tile 0, 16 = no screen MFMAs, 32 = no select / scan (and so
+                             // no finish), 64 = no survivor finish, 128 = no h2_save copy.  Every stand-in changes what the screen sees: read the
+                             // survivor / fallback counters next to each timing.  Measured (profiles/round8_pointnet_screen_overlap.md): 2, 4, 32, 64
+                             // and 128 keep the survivor count (3.8 - 4.1 per cloud and channel) and price their part; 1, 8 and 16 quadruple it and
+                             // price nothing.
+#endif
+#ifndef PS_SCHED_DEFAULT
+#define PS_SCHED_DEFAULT 0   // schedule of pm_pointnet_enc_fwd_screen_f32: 0 = lock-step, 1 = staggered (profiles/round8_pointnet_screen_overlap.md)
+#endif
 
 extern "C" size_t pm_pointnet_packed_screen_bytes(void) { return PS_PACKED_BYTES; }
 
@@ -137,7 +148,34 @@ __device__ __forceinline__ void ps_stream(const unsigned short* __restrict__ Ah,
 
 // counters (optional, tests and timing only): [0] survivors evaluated, [1] (wave, tile) pairs sent to the dense
 // fallback, [2] (tile, channel) pairs with at least one survivor
-template <int CT>
+//
+// SCHED (the order of independent work, never its arithmetic: every output is bit for bit the same under both).  A SIMD holds
+// waves w and w + 4 of the one work-group.  Under SCHED 0 all eight waves run screen -> select / finish -> h2_save copy between
+// the barrier after the layer-2 epilogue and the barrier at the top of the next tile, so SIMD partners reach their MFMA stream
+// together and their VALU / LDS / VMEM stretches together.  Under SCHED 1 waves 4-7 run the copy FIRST: it issues under the
+// partner's MFMA stream, and the partner's finish and copy issue under theirs.  Measured on MI355X this is no gain (the copy
+// is 0.09 ms of a 3.5 ms launch: too short an offset; VALU / MFMA co-execution cycles rose by a quarter, the launch got
+// 0.5 - 2 % longer, the all-fallback batch 2.5 %), so PS_SCHED_DEFAULT is 0 and SCHED 1 stays selectable for the next attempt
+// at a longer offset.  The copy reads H (the fp32 H2 tile), which is
+// complete at the barrier after the epilogue and is next written by layer 1 after the barrier at the top of the next tile;
+// the screen reads only the planes and the finish only H, skey and registers, so the three may run in any order between
+// those two barriers.  The branch is wave-uniform and holds no barrier: every wave executes four __syncthreads() per tile
+// on every path (survivor or fallback, last tile or not, P == 64), plus the one before the kernel's epilogue.
+template <int SCHED>
+__device__ __forceinline__ bool ps_late_wave(int wave) { return SCHED == 1 && __builtin_amdgcn_readfirstlane(wave) >= 4; }
+
+// training forward: the H2 tile (intact in LDS between the two barriers named above) also goes to HBM, as in pn_fwd_kernel
+template <int NT>
+__device__ __forceinline__ void ps_copy_h2(const float* __restrict__ H, float* __restrict__ dst, int tid) {
+#pragma unroll 2
+    for (int i = 0; i < PN_TM * PN_C2 / 4 / NT; ++i) {
+        const int q = tid + NT * i, row = q >> 6, c4 = q & 63;
+        const f32x4 v = *(const f32x4*)(H + row * PN_LD2 + 4 * c4);
+        *(f32x4*)(dst + row * PN_C2 + 4 * c4) = v;
+    }
+}
+
+template <int CT, int SCHED>
 __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
     const float* __restrict__ x, long ldx, int P, int C, int sub_mean, const float* __restrict__ W1,
     const float* __restrict__ b1, const float* __restrict__ b2, const float* __restrict__ b3,
@@ -150,7 +188,6 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
     __shared__ double red[16];
     __shared__ double cs[PN_C2];                                                      // column sums of h2 over the cloud
     __shared__ int skey[PS_NW][PS_CAP];                                               // survivors: (row << 6) | channel in wave
-    __shared__ float sval[PS_NW][PS_CAP];                                             // their exact layer-3 values
     unsigned short* Hh = Hp;
     unsigned short* Hl = Hp + PN_TM * PS_LDP;
 
@@ -177,39 +214,74 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
         asm volatile("" : "+v"(lane));
         const int li = lane & 31, lh = lane >> 5;
         __syncthreads();                     // Xs staged; the previous tile's reads of H and the planes are done
-        layer1_tile<CT, PN_TM, NT, true>(Xs, W1, b1, C, H);
+        if (!(PS_ABLATE & 1)) layer1_tile<CT, PN_TM, NT, true>(Xs, W1, b1, C, H);   // ablated: H1 = what the last tile left in H
         __syncthreads();
         {
             f32x16 acc2[2][1];
             zero_acc<2, 1>(acc2);
-            layer2_mfma<2, 1>(H, P2v, wave, lane, acc2);
+            if (PS_ABLATE & 2) {             // stand-in that still differs from point to point: 32 words of H1
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        acc2[mb][0][r] = H[(mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * PN_LD1 + ((wave * 32 + li) & 127)];
+            } else {
+                layer2_mfma<2, 1>(H, P2v, wave, lane, acc2);
+            }
             __syncthreads();                 // every wave has finished reading H1 (and Xs)
             // layer-2 epilogue: layer2_store's arithmetic, plus the bf16 planes and this tile's column sum
             const int col = wave * 32 + li;
             const float b2c = b2[col];
             float ts = 0.f;                  // fp32 within the tile, rows in increasing order
+            const bool planes = !(PS_ABLATE & 8) || tile == 0;      // ablated: the screen keeps reading tile 0's planes
+            // Lanes l and l ^ 1 hold columns col and col ^ 1 of the same rows: they swap one value of every row pair (r, r + 1), so
+            // the even lane holds both columns of row r and the odd lane both of row r + 1, and each stores its hi pair and its lo
+            // pair as one 32-bit word (v_cvt_pk_bf16_f32 rounds the two halves as it rounds one: the plane bytes are ps_split's).
+            const bool odd = (lane & 1) != 0;
+            unsigned* Hh2 = (unsigned*)(Hh + (odd ? PS_LDP : 0) + (col & ~1));      // 4-byte aligned: PS_LDP and col & ~1 are even
+            unsigned* Hl2 = (unsigned*)(Hl + (odd ? PS_LDP : 0) + (col & ~1));
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
-                    const f32x2 v2 = pm_tanh2(acc2[mb][0][r] + b2c, acc2[mb][0][r + 1] + b2c);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int row = mb * 32 + ((r + j) & 3) + 8 * ((r + j) >> 2) + 4 * lh;
-                        const float v = j ? v2.y : v2.x;
-                        unsigned short hi, lo;
-                        ps_split(v, hi, lo);
-                        H[row * PN_LD2 + col] = v;
-                        Hh[row * PS_LDP + col] = hi;
-                        Hl[row * PS_LDP + col] = lo;
-                        ts += v;
+                    const float z0 = acc2[mb][0][r] + b2c, z1 = acc2[mb][0][r + 1] + b2c;
+                    f32x2 v2;
+                    if (PS_ABLATE & 4) {
+                        v2.x = z0;
+                        v2.y = z1;
+                    } else {
+                        v2 = pm_tanh2(z0, z1);
+                    }
+                    const int row0 = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;     // r is even: r + 1 is row0 + 1
+                    H[row0 * PN_LD2 + col] = v2.x;
+                    H[(row0 + 1) * PN_LD2 + col] = v2.y;
+                    ts += v2.x;
+                    ts += v2.y;
+                    const float own = odd ? v2.y : v2.x, send = odd ? v2.x : v2.y;
+                    const float recv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(send), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]: lane ^ 1
+                    const float a = odd ? recv : own, c = odd ? own : recv;         // columns col & ~1 and col | 1 of row0 + odd
+                    unsigned h2w, l2w;
+                    if (PS_ABLATE & 4) {
+                        h2w = (__float_as_uint(a) >> 16) | (__float_as_uint(c) & 0xffff0000u);
+                        l2w = 0;
+                    } else {
+                        h2w = ps_cvt_pk(a, c);
+                        l2w = ps_cvt_pk(a - __uint_as_float(h2w << 16), c - __uint_as_float(h2w & 0xffff0000u));
+                    }
+                    if (planes) {
+                        Hh2[row0 * (PS_LDP / 2)] = h2w;                             // word index of halfword row0 * PS_LDP
+                        Hl2[row0 * (PS_LDP / 2)] = l2w;
                     }
                 }
             ts += __shfl_xor(ts, 32, 64);    // the other 32 rows; both halves hold the same sum
             csum += (double)ts;              // fp64 across tiles
             if (tile + 1 < ntiles) stage_points<PN_TM, NT>(xb, tile + 1, C, sub_mean, cen, Xs);
         }
-        __syncthreads();
+        __syncthreads();                     // H2 and the planes are complete; nothing below writes them before the loop-top barrier
+
+        const bool copy = h2_save && !(PS_ABLATE & 128), late = ps_late_wave<SCHED>(wave);
+        float* h2dst = copy ? h2_save + ((long)b * P + (long)tile * PN_TM) * PN_C2 : nullptr;
+        if (copy && late) ps_copy_h2<NT>(H, h2dst, tid);     // waves 4-7, SCHED 1: under the SIMD partner's screen MFMAs
 
         // ---- screen: z~ for 64 points x this wave's 64 channels ---------------------------------------------
         f32x16 acc[2][2];
@@ -219,10 +291,30 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[0][nb][r] = acc[1][nb][r] = b3c;
         }
-        ps_stream(Hh + li * PS_LDP + lh * 8, Hl + li * PS_LDP + lh * 8, S3h + (size_t)(wave * 2 * 16) * 64 + lane,
-                  S3l + (size_t)(wave * 2 * 16) * 64 + lane, acc);
+        if (PS_ABLATE & 16) {                // stand-in that still differs from point to point: b3 + 64 words of H2
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        acc[mb][nb][r] += H[(mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * PN_LD2 + ((wave * 64 + nb * 32 + li) & 255)];
+        } else {
+            ps_stream(Hh + li * PS_LDP + lh * 8, Hl + li * PS_LDP + lh * 8, S3h + (size_t)(wave * 2 * 16) * 64 + lane,
+                      S3l + (size_t)(wave * 2 * 16) * 64 + lane, acc);
+        }
 
         unsigned msk[2];
+        float tmax[2];                       // PS_ABLATE & 64 only
+#if (PS_ABLATE & 32) && defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {     // timing probe: the screen's results stay live without the compare / scan pass
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb) asm volatile("" ::"v"(acc[mb][nb]));
+            msk[nb] = 0;
+            tmax[nb] = 0.f;
+        }
+#else
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
             float m = -INFINITY;
@@ -244,7 +336,9 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
                     k |= (s ? 1u : 0u) << (mb * 16 + r);
                 }
             msk[nb] = k;
+            tmax[nb] = m;
         }
+#endif
         const int n = __popc(msk[0]) + __popc(msk[1]);
         int incl = n;
 #pragma unroll
@@ -254,7 +348,11 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
         }
         const int total = __builtin_amdgcn_readlane(incl, 63);
 
-        if (total <= PS_CAP) {
+        if (PS_ABLATE & 64) {
+            // no finish: the running maximum follows the tile maxima of z~ instead, so that the second test keeps pruning
+            vmax = fmaxf(vmax, lh ? tmax[1] : tmax[0]);
+            if (counters && lane == 0) atomicAdd(counters + 0, (unsigned long long)total);
+        } else if (total <= PS_CAP) {
             // ---- survivors -> list -> exact fp32 values -> running maximum ------------------------------------
             int off = incl - n;
 #pragma unroll
@@ -289,20 +387,22 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
                 s += __shfl_xor(s, 2, 64);
                 s += __shfl_xor(s, 1, 64);
                 s += b3[wave * 64 + cl];
-                if (j == 0 && e < total) sval[wave][e] = s;
-            }
-            __builtin_amdgcn_wave_barrier();
-            for (int e = 0; e < total; ++e) {                 // wave-uniform: every lane picks its own channel's survivors
-                const int key = skey[wave][e];
-                const float v = sval[wave][e];
-                if ((key & 63) == lane) {
-                    const int p = tile * PN_TM + (key >> 6);
-                    if (!(fabsf(v) < INFINITY)) pois += v;
-                    if (v > vmax || (v == vmax && p < imax)) {
-                        vmax = v;
-                        imax = p;
+                // All eight lanes of a group hold the same s (the butterfly's adds commute).  The pass's eight (value, key) pairs go
+                // to their channels' owner lanes through scalar registers, in list order as before (pois sums in that order).
+#pragma unroll
+                for (int gg = 0; gg < 8; ++gg)
+                    if (e0 + gg < total) {                    // wave-uniform
+                        const int kk = __builtin_amdgcn_readlane(key, gg * 8);
+                        const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), gg * 8));
+                        if ((kk & 63) == lane) {
+                            const int p = tile * PN_TM + (kk >> 6);
+                            if (!(fabsf(v) < INFINITY)) pois += v;
+                            if (v > vmax || (v == vmax && p < imax)) {
+                                vmax = v;
+                                imax = p;
+                            }
+                        }
                     }
-                }
             }
             if (counters) {
                 const unsigned long long h0 = __ballot(msk[0] != 0), h1 = __ballot(msk[1] != 0);
@@ -351,16 +451,7 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
             }
             if (counters && lane == 0) atomicAdd(counters + 1, 1ull);
         }
-        // training forward: the H2 tile (still intact in LDS) also goes to HBM, as in pn_fwd_kernel
-        if (h2_save) {
-            float* dst = h2_save + ((long)b * P + (long)tile * PN_TM) * PN_C2;
-#pragma unroll 2
-            for (int i = 0; i < PN_TM * PN_C2 / 4 / NT; ++i) {
-                const int q = tid + NT * i, row = q >> 6, c4 = q & 63;
-                const f32x4 v = *(const f32x4*)(H + row * PN_LD2 + 4 * c4);
-                *(f32x4*)(dst + row * PN_C2 + 4 * c4) = v;
-            }
-        }
+        if (copy && !late) ps_copy_h2<NT>(H, h2dst, tid);    // SCHED 1, waves 0-3: under the SIMD partner's screen MFMAs
     }
     // ---- epilogue: thread tid owns channel tid --------------------------------------------------------------
     if ((lane0 >> 5) == 0) cs[wave * 32 + lane0] = csum;
@@ -391,24 +482,40 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
     }
 }
 
-extern "C" int pm_pointnet_enc_fwd_screen_f32(const float* x, long ldx, int B, int P, int C, int sub_mean, const float* W1,
-                                              const float* b1, const float* b2, const float* b3, const float* packed,
-                                              const void* packed_screen, int max_mean, float* feat, long ldf,
-                                              int32_t* argmax, float* h2_save, unsigned long long* counters, void* stream) {
+extern "C" int pm_pointnet_enc_fwd_screen_sched_f32(const float* x, long ldx, int B, int P, int C, int sub_mean, const float* W1,
+                                                    const float* b1, const float* b2, const float* b3, const float* packed,
+                                                    const void* packed_screen, int max_mean, float* feat, long ldf,
+                                                    int32_t* argmax, float* h2_save, unsigned long long* counters, int schedule,
+                                                    void* stream) {
     PM_REQUIRE(x && W1 && b1 && b2 && b3 && packed && packed_screen && feat && argmax);
+    PM_REQUIRE(schedule == 0 || schedule == 1);
     if (h2_save && ((uintptr_t)h2_save & 15) != 0) return PM_EALIGN;
     PM_REQUIRE(B > 0 && P > 0 && P % PN_TM == 0 && C >= 1 && C <= PN_MAXC && ldx >= (long)P * C);
     PM_REQUIRE(ldf >= PN_C3 * (max_mean ? 2 : 1));
     PM_REQUIRE(!sub_mean || C >= 3);
     if (((uintptr_t)packed & 15) != 0 || ((uintptr_t)packed_screen & 15) != 0 || ((uintptr_t)counters & 7) != 0) return PM_EALIGN;
-#define PS_LAUNCH(CT)                                                                                                 \
-    hipLaunchKernelGGL((pn_fwd_screen_kernel<CT>), dim3(B), dim3(PS_NW * 64), 0, pm_stream(stream), x, ldx, P, C, sub_mean, \
+#define PS_LAUNCH(CT, S)                                                                                              \
+    hipLaunchKernelGGL((pn_fwd_screen_kernel<CT, S>), dim3(B), dim3(PS_NW * 64), 0, pm_stream(stream), x, ldx, P, C, sub_mean, \
                        W1, b1, b2, b3, packed, (const unsigned char*)packed_screen, max_mean, feat, ldf, argmax, h2_save,   \
                        counters)
-    if (C == 3) PS_LAUNCH(3);
-    else if (C == 4) PS_LAUNCH(4);
-    else PS_LAUNCH(0);
+    if (schedule == 0) {
+        if (C == 3) PS_LAUNCH(3, 0);
+        else if (C == 4) PS_LAUNCH(4, 0);
+        else PS_LAUNCH(0, 0);
+    } else {
+        if (C == 3) PS_LAUNCH(3, 1);
+        else if (C == 4) PS_LAUNCH(4, 1);
+        else PS_LAUNCH(0, 1);
+    }
 #undef PS_LAUNCH
     PM_CHECK_LAUNCH();
     return PM_OK;
+}
+
+extern "C" int pm_pointnet_enc_fwd_screen_f32(const float* x, long ldx, int B, int P, int C, int sub_mean, const float* W1,
+                                              const float* b1, const float* b2, const float* b3, const float* packed,
+                                              const void* packed_screen, int max_mean, float* feat, long ldf,
+                                              int32_t* argmax, float* h2_save, unsigned long long* counters, void* stream) {
+    return pm_pointnet_enc_fwd_screen_sched_f32(x, ldx, B, P, C, sub_mean, W1, b1, b2, b3, packed, packed_screen, max_mean, feat,
+                                                ldf, argmax, h2_save, counters, PS_SCHED_DEFAULT, stream);
 }

@@ -465,13 +465,22 @@ def pointnet_pack_screen(w3, b3, packed):
 
 
 def pointnet_enc_fwd_screen(x, P, Cc, sub_mean, w1, b1, b2, b3, packed, packed_screen, max_mean, feat, argmax, h2_save=None,
-                            counters=None):
+                            counters=None, schedule=None):
     """The screened tanh forward (csrc/pointnet_enc_screen.h).  counters: optional 3 x int64 device tensor the kernel adds
-    [survivors, dense-fallback (wave, tile) pairs, (tile, channel) pairs with a survivor] to."""
+    [survivors, dense-fallback (wave, tile) pairs, (tile, channel) pairs with a survivor] to.  schedule: None = the library's
+    default, 0 = lock-step, 1 = waves 4-7 staggered (same results bit for bit; anything else is refused)."""
     _req(x, w1, b1, b2, b3, packed, packed_screen, feat, argmax, h2_save, counters)
     if counters is not None and (counters.dtype != torch.int64 or counters.numel() < 3 or not counters.is_contiguous()):
         raise ValueError("counters: expected a contiguous int64 tensor of 3 elements")
     B = x.shape[0]
+    if schedule is not None:
+        with TIMER.bracket("pointnet_enc_fwd"):
+            check(lib.pm_pointnet_enc_fwd_screen_sched_f32(_ptr(x), _rows(x, "x"), B, P, Cc, int(sub_mean), _ptr(w1), _ptr(b1),
+                                                           _ptr(b2), _ptr(b3), _ptr(packed), _ptr(packed_screen), int(max_mean),
+                                                           _ptr(feat), _rows(feat, "feat"), _ptr(argmax), _ptr(h2_save),
+                                                           _ptr(counters), int(schedule), _stream()),
+                  "pm_pointnet_enc_fwd_screen_sched_f32")
+        return
     with TIMER.bracket("pointnet_enc_fwd"):
         check(lib.pm_pointnet_enc_fwd_screen_f32(_ptr(x), _rows(x, "x"), B, P, Cc, int(sub_mean), _ptr(w1), _ptr(b1), _ptr(b2),
                                                  _ptr(b3), _ptr(packed), _ptr(packed_screen), int(max_mean), _ptr(feat),
