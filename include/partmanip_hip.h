@@ -646,6 +646,54 @@ int pm_mesh_frame_render_f32(const float* verts, const int32_t* vert_part, int N
                              int bg_b, float* depth, long depth_stride, int32_t* seg, long seg_stride, uint8_t* rgb,
                              long rgb_stride, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ the two cameras over a scene whose environments differ
+ * pm_mesh_depth_render_groups_f32 / pm_mesh_frame_render_groups_f32: the arguments of the two entries above plus a partition of the
+ * rows of `faces` into a shared range and G groups, and one group per environment (open_drawer: env % num_objs is its cabinet).
+ *   F_shared                 rows [0, F_shared) of faces are drawn by every environment
+ *   group_off (G + 1) int32  rows relative to F_shared, non-decreasing, group_off[0] = 0, group_off[G] = F - F_shared
+ *   env_group (B) int32      g = env_group[b] in [0, G): environment b also draws rows [F_shared + group_off[g],
+ *                            F_shared + group_off[g + 1]); g = -1: the shared rows only
+ *   max_group_faces          an upper bound of the rows of a group, max_g (group_off[g + 1] - group_off[g]); it sizes the grid
+ * Definition: the image of environment b is the definition of the ungrouped entry applied to that subset of faces -- the same fp32
+ * association, hit rule, near / far; the frame's winner is the nearest triangle, a tie goes to the smaller row of faces (the key
+ * keeps the row in faces, so depth, seg and rgb are those of the ungrouped entry called with the subset in row order, and the
+ * resolve launch is unchanged).  vert_part keeps its meaning: a vertex names its pose slot, a static property of the vertex, equal
+ * in every environment that draws it; what differs between environments is which rows are drawn and the poses in the slots.
+ * Launch shape: one lane per (environment, view, face ordinal t < F_shared + max_group_faces); t < F_shared is row t, else row
+ * F_shared + group_off[g] + (t - F_shared) while that lies in the group.  An environment pays the set-up of its own triangles only.
+ * Memory safety: g outside [-1, G) counts as -1; a group's rows are clamped to [F_shared, F); at most max_group_faces rows of a
+ * group are drawn (a bound that is too small drops the group's last rows, it reads nothing out of range); nothing is read through
+ * a bad index.  No float atomics, no workspace beyond the frame camera's keys, stream-ordered, never synchronises.
+ * Before any launch -- PM_EINVAL: every condition of the ungrouped entry (its grid condition read with F_shared + max_group_faces in
+ * place of F), F_shared outside [0, F], G < 0, max_group_faces < 0, a NULL group_off or env_group with G > 0; PM_EWORKSPACE and
+ * PM_EALIGN as above.  PM_ABI_VERSION stays 163 with these additions (no existing signature changed). */
+int pm_mesh_depth_render_groups_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F, int F_shared,
+                                    const int32_t* group_off, int G, const int32_t* env_group, int max_group_faces,
+                                    const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V, float fx,
+                                    float fy, float cx, float cy, int H, int W, float near, float far, float* out, long out_stride,
+                                    void* stream);
+int pm_mesh_frame_render_groups_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F, int F_shared,
+                                    const int32_t* group_off, int G, const int32_t* env_group, int max_group_faces,
+                                    const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V, float fx,
+                                    float fy, float cx, float cy, int H, int W, float near, float far, const int32_t* part_label,
+                                    int miss_label, const float* palette, float ambient, float one_minus_ambient, int bg_r, int bg_g,
+                                    int bg_b, float* depth, long depth_stride, int32_t* seg, long seg_stride, uint8_t* rgb,
+                                    long rgb_stride, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ body poses of a whole scene (the cameras' pose input)
+ * rigid_body (nrows, 13) flat rows (position, quaternion (i, j, k, r), velocities); rows (B, M) int32: slot m of environment b is
+ * row rows[b, m]; part_C (MC, 3, 3) or NULL with MC = 0: the mesh-frame matrices of the first MC slots.
+ *   pose_T[b, m] = the row's position
+ *   pose_R[b, m] = quat_to_mat(q) for m >= MC, and for m < MC
+ *   pose_R[b, m][i][j] = (Q[i][0] C_m[0][j] + Q[i][1] C_m[1][j]) + Q[i][2] C_m[2][j]
+ * with quat_to_mat and the product exactly as the task kernels compute them (pm_grasp_cube_post_f32), so a slot both produce carries
+ * the same bits.  A row index outside [0, nrows) gives a NaN pose and its address is never formed (the cameras skip a triangle
+ * with a non-finite corner).  One launch, no workspace, no atomics, stream-ordered, never synchronises.
+ * PM_EINVAL: a NULL rigid_body / rows / pose_R / pose_T, nrows, B or M < 1, MC outside [0, M], MC > 0 with a NULL part_C.
+ * PM_ABI_VERSION stays 163 with this addition. */
+int pm_body_pose_gather_f32(const float* rigid_body, long nrows, const int32_t* rows, int B, int M, const float* part_C, int MC,
+                            float* pose_R, float* pose_T, void* stream);
+
 /* ------------------------------------------------------------------ grasp_cube task step (simulator side of the learner)
  * The tensor program of the reference's task layer (tasks/grasp_cube.py, tasks/load_robot.py, tasks/hand_base.py:363-392, 431-441)
  * as one launch after physics and one before it.  Neither synchronises, allocates or uses float atomics; both are stream-ordered.

@@ -115,6 +115,10 @@ SIGNATURES = {
     "pm_mesh_frame_workspace_bytes": (Z, [I, I, I, I]),
     "pm_mesh_frame_render_f32": (I, [P, P, I, P, I, P, P, I, I, P, I, F, F, F, F, I, I, F, F, P, I, P, F, F, I, I, I, P, L, P, L, P, L, P, Z,
                                      P]),
+    "pm_mesh_depth_render_groups_f32": (I, [P, P, I, P, I, I, P, I, P, I, P, P, I, I, P, I, F, F, F, F, I, I, F, F, P, L, P]),
+    "pm_mesh_frame_render_groups_f32": (I, [P, P, I, P, I, I, P, I, P, I, P, P, I, I, P, I, F, F, F, F, I, I, F, F, P, I, P, F, F, I, I, I,
+                                            P, L, P, L, P, L, P, Z, P]),
+    "pm_body_pose_gather_f32": (I, [P, L, P, I, I, P, I, P, P, P]),
     "pm_grasp_cube_post_f32": (I, [P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, F, P, P, P, I, P, L, P, L, P, P, P, P, L, P, P, P]),
     "pm_franka_control_f32": (I, [P, L, I, P, P, I, I, I, I, I, P, P, P, F, I, P, P, P, I, I, I, P, P, P, P, P, P, I, P]),
     "pm_franka_control_mobile_f32": (I, [P, L, I, P, P, I, I, I, I, I, P, P, P, F, I, I, P, P, P, P, I, I, I, P, P, P, P, P, P, I, P]),

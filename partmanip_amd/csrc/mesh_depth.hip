@@ -38,8 +38,22 @@
 // per tile.  It was not built and not measured: here the relaxed read filters most updates (a pixel's depth settles after its
 // first few triangles; 17 % of the pixels are hit at all in the timed scene), and the figures below are what it would have to beat.
 //
+// Grouped entry (pm_mesh_depth_render_groups_f32; include/partmanip_hip.h has the definition).  The rows of `faces` split into a
+// shared range [0, F_shared) and G groups behind it, and environment b draws the shared rows and the rows of group env_group[b]:
+// open_drawer's environments each hold their own cabinet.  Same fill, same md_raster, same commit; what differs is the row a lane
+// takes (mesh_raster.h, md_group_face): a lane owns (environment, view, face ordinal t < F_shared + max_group_faces), t maps to a row
+// of the shared range or of the environment's group, and a block whose first ordinal lies past its environment's count returns
+// before md_raster's barrier (the count depends on the block's environment only, so the branch is uniform over the block).  The image
+// of an environment is therefore the definition applied to its own rows, bit for bit, and it pays the set-up of its own triangles;
+// the alternative with the ungrouped entry -- every object of the library in one scene, NaN poses for the absent ones -- pays the
+// set-up of the whole library in every environment (tools/time_drawer_scene.py, profiles/drawer_scene_timing.json).  A group id
+// outside [0, G) is no group, a group's rows are clamped to [F_shared, F) and to max_group_faces: nothing is read through a bad index.
+//
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): raster 54 VGPRs, 64 SGPRs, no scratch, occupancy 8 waves / SIMD,
-// LDS (dynamic) 4 (W + H) bytes = 3.2 KB at 512 x 288; fill 28 VGPRs, 51 SGPRs, no scratch.
+// LDS (dynamic) 4 (W + H) bytes = 3.2 KB at 512 x 288; fill 28 VGPRs, 51 SGPRs, no scratch.  Re-run when md_raster began to take the
+// face row from its caller: the ungrouped raster kernel keeps 54 VGPRs / 64 SGPRs / no scratch / occupancy 8 / the same LDS (its
+// device assembly differs from the previous one in the order of five scalar instructions and in one compare that became unsigned),
+// fill unchanged; the grouped raster kernel: 54 VGPRs, 64 SGPRs, no scratch, occupancy 8, the same LDS.
 // Measured A/B on one MI355X (tools/time_mesh_depth.py: 12 ellipsoids, 133 200 triangles, 1024 environments, random poses; the
 // shipped rig 3 x 288 x 512 / the image rig 1 x 72 x 128, ms per call), MD_WAVE_BOX = 16 / 64 / 256: 56.65 / 18.97 / 18.99 and
 // 10.63 / 2.85 / 2.85.  A box holds 27 / 18 pixels on average (a pixel-sized triangle widened by one pixel), so at 16 nearly every triangle
@@ -56,6 +70,14 @@ __global__ __launch_bounds__(MD_THREADS) void mesh_depth_fill_kernel(float* __re
     }
 }
 
+// The depth minimum of one hit.  dst is the pixel's word of the image, holding the bits of a positive float.
+struct md_depth_commit {
+    __device__ __forceinline__ void operator()(unsigned* dst, float z, int) const {
+        const unsigned zb = __float_as_uint(z);
+        if (zb < __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(dst, zb);
+    }
+};
+
 __global__ __launch_bounds__(MD_THREADS) void mesh_depth_raster_kernel(
     const float* __restrict__ verts, const int32_t* __restrict__ vert_part, int NV, const int32_t* __restrict__ faces, int F,
     const float* __restrict__ pose_R, const float* __restrict__ pose_T, int M, const float* __restrict__ cam_pose, int V, int chunks,
@@ -65,25 +87,48 @@ __global__ __launch_bounds__(MD_THREADS) void mesh_depth_raster_kernel(
     int v, chunk;
     md_block(blockIdx.x, chunks, V, b, v, chunk);
     unsigned* img = (unsigned*)(out + b * out_stride + (long)v * H * W);
-    // The depth minimum of one hit.  dst is the pixel's word of the image, holding the bits of a positive float.
-    md_raster(verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, b, v, chunk, fx, fy, cx, cy, H, W, near, far, md_tab, img,
-              [](unsigned* dst, float z, int) {
-                  const unsigned zb = __float_as_uint(z);
-                  if (zb < __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(dst, zb);
-              });
+    md_raster(verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, b, v, chunk * MD_THREADS + (int)threadIdx.x, fx, fy, cx, cy, H,
+              W, near, far, md_tab, img, md_depth_commit());
 }
 
-extern "C" int pm_mesh_depth_render_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F,
-                                        const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V,
-                                        float fx, float fy, float cx, float cy, int H, int W, float near, float far, float* out,
-                                        long out_stride, void* stream) {
+// The grouped entry's raster: a lane owns (environment, view, face ordinal t), chunks = ceil((F_shared + max_group_faces) / 256).  A
+// block whose first ordinal lies past its environment's count leaves before md_raster's barrier; the test is uniform over the block.
+__global__ __launch_bounds__(MD_THREADS) void mesh_depth_raster_groups_kernel(
+    const float* __restrict__ verts, const int32_t* __restrict__ vert_part, int NV, const int32_t* __restrict__ faces, int F,
+    int F_shared, const int32_t* __restrict__ group_off, int G, const int32_t* __restrict__ env_group, int max_group_faces,
+    const float* __restrict__ pose_R, const float* __restrict__ pose_T, int M, const float* __restrict__ cam_pose, int V, int chunks,
+    float fx, float fy, float cx, float cy, int H, int W, float near, float far, float* out, long out_stride) {
+    extern __shared__ float md_tab[];
+    long b;
+    int v, chunk, count;
+    md_block(blockIdx.x, chunks, V, b, v, chunk);
+    const int f = md_group_face(chunk * MD_THREADS + (int)threadIdx.x, b, F, F_shared, group_off, G, env_group, max_group_faces, count);
+    if (chunk * MD_THREADS >= count) return;
+    unsigned* img = (unsigned*)(out + b * out_stride + (long)v * H * W);
+    md_raster(verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, b, v, f, fx, fy, cx, cy, H, W, near, far, md_tab, img,
+              md_depth_commit());
+}
+
+// Both entries: the checks, the fill and one raster launch.  grouped: the ordinals of an environment are F_shared + max_group_faces
+// (the latter cut to F - F_shared, which no group can exceed); else they are the F rows.
+static int md_render(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F, bool grouped, int F_shared,
+                     const int32_t* group_off, int G, const int32_t* env_group, int max_group_faces, const float* pose_R,
+                     const float* pose_T, int B, int M, const float* cam_pose, int V, float fx, float fy, float cx, float cy, int H, int W,
+                     float near, float far, float* out, long out_stride, void* stream) {
     PM_REQUIRE(verts && vert_part && faces && pose_R && pose_T && cam_pose && out);
     PM_REQUIRE(NV >= 1 && F >= 1 && B >= 1 && M >= 1 && V >= 1 && H >= 1 && W >= 1);
     PM_REQUIRE(near > 0.f && far > near);                    // a NaN fails either
     PM_REQUIRE((long)W + H <= MD_MAX_TAB);
     const long n = (long)V * H * W;
     PM_REQUIRE(out_stride >= n);
-    const int chunks = (F + MD_THREADS - 1) / MD_THREADS;
+    long ordinals = F;
+    if (grouped) {
+        PM_REQUIRE(F_shared >= 0 && F_shared <= F && G >= 0 && max_group_faces >= 0);
+        PM_REQUIRE(G == 0 || (group_off && env_group));
+        if (max_group_faces > F - F_shared) max_group_faces = F - F_shared;
+        ordinals = (long)F_shared + max_group_faces;
+    }
+    const int chunks = (int)((ordinals + MD_THREADS - 1) / MD_THREADS);
     const long blocks = (long)chunks * V * B;
     PM_REQUIRE(blocks < (1L << 31) && (long)H * W < (1L << 31));
     const long total = n * B;
@@ -91,9 +136,33 @@ extern "C" int pm_mesh_depth_render_f32(const float* verts, const int32_t* vert_
     hipLaunchKernelGGL(mesh_depth_fill_kernel, dim3((unsigned)(fill_blocks < (1L << 20) ? fill_blocks : (1L << 20))),
                        dim3(MD_THREADS), 0, pm_stream(stream), out, out_stride, n, total, far);
     PM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mesh_depth_raster_kernel, dim3((unsigned)blocks), dim3(MD_THREADS), (size_t)(W + H) * sizeof(float),
-                       pm_stream(stream), verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, V, chunks, fx, fy, cx, cy,
-                       H, W, near, far, out, out_stride);
-    PM_CHECK_LAUNCH();
+    if (!grouped) {
+        hipLaunchKernelGGL(mesh_depth_raster_kernel, dim3((unsigned)blocks), dim3(MD_THREADS), (size_t)(W + H) * sizeof(float),
+                           pm_stream(stream), verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, V, chunks, fx, fy, cx, cy,
+                           H, W, near, far, out, out_stride);
+        PM_CHECK_LAUNCH();
+    } else if (blocks > 0) {                                 // no shared row and no group row: the fill is the image
+        hipLaunchKernelGGL(mesh_depth_raster_groups_kernel, dim3((unsigned)blocks), dim3(MD_THREADS), (size_t)(W + H) * sizeof(float),
+                           pm_stream(stream), verts, vert_part, NV, faces, F, F_shared, group_off, G, env_group, max_group_faces, pose_R,
+                           pose_T, M, cam_pose, V, chunks, fx, fy, cx, cy, H, W, near, far, out, out_stride);
+        PM_CHECK_LAUNCH();
+    }
     return PM_OK;
+}
+
+extern "C" int pm_mesh_depth_render_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F,
+                                        const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V,
+                                        float fx, float fy, float cx, float cy, int H, int W, float near, float far, float* out,
+                                        long out_stride, void* stream) {
+    return md_render(verts, vert_part, NV, faces, F, false, 0, nullptr, 0, nullptr, 0, pose_R, pose_T, B, M, cam_pose, V, fx, fy, cx, cy,
+                     H, W, near, far, out, out_stride, stream);
+}
+
+extern "C" int pm_mesh_depth_render_groups_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F,
+                                               int F_shared, const int32_t* group_off, int G, const int32_t* env_group,
+                                               int max_group_faces, const float* pose_R, const float* pose_T, int B, int M,
+                                               const float* cam_pose, int V, float fx, float fy, float cx, float cy, int H, int W,
+                                               float near, float far, float* out, long out_stride, void* stream) {
+    return md_render(verts, vert_part, NV, faces, F, true, F_shared, group_off, G, env_group, max_group_faces, pose_R, pose_T, B, M,
+                     cam_pose, V, fx, fy, cx, cy, H, W, near, far, out, out_stride, stream);
 }

@@ -35,7 +35,10 @@
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): fill 6 VGPRs, 18 SGPRs; raster 54 VGPRs, 64 SGPRs, occupancy 8
 // waves / SIMD, LDS (dynamic) 4 (W + H) bytes -- the depth raster's figures; resolve 68 VGPRs, 84 SGPRs, occupancy 7.  No scratch in
-// any of the three.
+// any of the three.  Re-run when md_raster began to take the face row from its caller and the grouped entry was added
+// (pm_mesh_frame_render_groups_f32: mesh_depth.hip's grouped raster with this file's commit; the key keeps the row in `faces`, so the
+// tie-break and the resolve launch are the ungrouped entry's): fill, the ungrouped raster and resolve keep the figures above; the
+// grouped raster kernel: 54 VGPRs, 66 SGPRs, no scratch, occupancy 8, the same LDS.
 // Measured 2026-10-19 on one MI355X (tools/time_mesh_frame.py: the depth camera's scene, 133 200 triangles, 17 % of the pixels hit;
 // ms per call, the three taken in turn): depth kernel / this file writing seg only / writing all three = 0.212 / 0.207 / 0.212
 // (image rig 1 x 72 x 128, 64 environments), 2.83 / 2.79 / 2.86 (1024 environments), 1.21 / 1.18 / 1.37 (shipped rig 3 x 288 x 512,
@@ -53,6 +56,14 @@ __global__ __launch_bounds__(MD_THREADS) void mesh_frame_fill_kernel(unsigned lo
     for (long i = (long)blockIdx.x * MD_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * MD_THREADS) keys[i] = key;
 }
 
+// The winner of one hit: nearer first, then the smaller face index.
+struct mf_key_commit {
+    __device__ __forceinline__ void operator()(unsigned long long* dst, float z, int f) const {
+        const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)f;
+        if (key < __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(dst, key);
+    }
+};
+
 __global__ __launch_bounds__(MD_THREADS) void mesh_frame_raster_kernel(
     const float* __restrict__ verts, const int32_t* __restrict__ vert_part, int NV, const int32_t* __restrict__ faces, int F,
     const float* __restrict__ pose_R, const float* __restrict__ pose_T, int M, const float* __restrict__ cam_pose, int V, int chunks,
@@ -62,12 +73,26 @@ __global__ __launch_bounds__(MD_THREADS) void mesh_frame_raster_kernel(
     int v, chunk;
     md_block(blockIdx.x, chunks, V, b, v, chunk);
     unsigned long long* img = keys + (b * V + v) * ((long)H * W);
-    // The winner of one hit: nearer first, then the smaller face index.
-    md_raster(verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, b, v, chunk, fx, fy, cx, cy, H, W, near, far, md_tab, img,
-              [](unsigned long long* dst, float z, int f) {
-                  const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)f;
-                  if (key < __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(dst, key);
-              });
+    md_raster(verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, b, v, chunk * MD_THREADS + (int)threadIdx.x, fx, fy, cx, cy, H,
+              W, near, far, md_tab, img, mf_key_commit());
+}
+
+// The grouped entry's raster (mesh_depth.hip's grouped kernel with this file's commit): the key's low word is the row in faces, so
+// the tie-break and the resolve launch are the ungrouped entry's.
+__global__ __launch_bounds__(MD_THREADS) void mesh_frame_raster_groups_kernel(
+    const float* __restrict__ verts, const int32_t* __restrict__ vert_part, int NV, const int32_t* __restrict__ faces, int F,
+    int F_shared, const int32_t* __restrict__ group_off, int G, const int32_t* __restrict__ env_group, int max_group_faces,
+    const float* __restrict__ pose_R, const float* __restrict__ pose_T, int M, const float* __restrict__ cam_pose, int V, int chunks,
+    float fx, float fy, float cx, float cy, int H, int W, float near, float far, unsigned long long* keys) {
+    extern __shared__ float md_tab[];
+    long b;
+    int v, chunk, count;
+    md_block(blockIdx.x, chunks, V, b, v, chunk);
+    const int f = md_group_face(chunk * MD_THREADS + (int)threadIdx.x, b, F, F_shared, group_off, G, env_group, max_group_faces, count);
+    if (chunk * MD_THREADS >= count) return;
+    unsigned long long* img = keys + (b * V + v) * ((long)H * W);
+    md_raster(verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, b, v, f, fx, fy, cx, cy, H, W, near, far, md_tab, img,
+              mf_key_commit());
 }
 
 __global__ __launch_bounds__(MD_THREADS) void mesh_frame_resolve_kernel(
@@ -123,8 +148,9 @@ extern "C" size_t pm_mesh_frame_workspace_bytes(int B, int V, int H, int W) {
     return (size_t)8 * (size_t)B * (size_t)V * (size_t)H * (size_t)W;
 }
 
-extern "C" int pm_mesh_frame_render_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F,
-                                        const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V,
+// Both entries: the checks and the three launches.  grouped: see mesh_depth.hip's md_render.
+static int mf_render(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F, bool grouped, int F_shared,
+                                        const int32_t* group_off, int G, const int32_t* env_group, int max_group_faces, const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V,
                                         float fx, float fy, float cx, float cy, int H, int W, float near, float far,
                                         const int32_t* part_label, int miss_label, const float* palette, float ambient,
                                         float one_minus_ambient, int bg_r, int bg_g, int bg_b, float* depth, long depth_stride,
@@ -139,7 +165,14 @@ extern "C" int pm_mesh_frame_render_f32(const float* verts, const int32_t* vert_
     PM_REQUIRE(!rgb || palette);
     PM_REQUIRE(ambient >= 0.f && one_minus_ambient >= 0.f && ambient + one_minus_ambient <= 1.f);      // a NaN fails
     PM_REQUIRE(bg_r >= 0 && bg_r <= 255 && bg_g >= 0 && bg_g <= 255 && bg_b >= 0 && bg_b <= 255);
-    const int chunks = (F + MD_THREADS - 1) / MD_THREADS;
+    long ordinals = F;
+    if (grouped) {
+        PM_REQUIRE(F_shared >= 0 && F_shared <= F && G >= 0 && max_group_faces >= 0);
+        PM_REQUIRE(G == 0 || (group_off && env_group));
+        if (max_group_faces > F - F_shared) max_group_faces = F - F_shared;
+        ordinals = (long)F_shared + max_group_faces;
+    }
+    const int chunks = (int)((ordinals + MD_THREADS - 1) / MD_THREADS);
     const long blocks = (long)chunks * V * B;
     PM_REQUIRE(blocks < (1L << 31) && hw < (1L << 31));
     if (!workspace || workspace_bytes < pm_mesh_frame_workspace_bytes(B, V, H, W)) return PM_EWORKSPACE;
@@ -154,13 +187,45 @@ extern "C" int pm_mesh_frame_render_f32(const float* verts, const int32_t* vert_
     hipLaunchKernelGGL(mesh_frame_fill_kernel, pixel_grid, dim3(MD_THREADS), 0, pm_stream(stream), keys, total,
                        ((unsigned long long)far_bits << 32) | MF_MISS_FACE);
     PM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mesh_frame_raster_kernel, dim3((unsigned)blocks), dim3(MD_THREADS), (size_t)(W + H) * sizeof(float),
-                       pm_stream(stream), verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, V, chunks, fx, fy, cx, cy,
-                       H, W, near, far, keys);
-    PM_CHECK_LAUNCH();
+    if (!grouped) {
+        hipLaunchKernelGGL(mesh_frame_raster_kernel, dim3((unsigned)blocks), dim3(MD_THREADS), (size_t)(W + H) * sizeof(float),
+                           pm_stream(stream), verts, vert_part, NV, faces, F, pose_R, pose_T, M, cam_pose, V, chunks, fx, fy, cx, cy,
+                           H, W, near, far, keys);
+        PM_CHECK_LAUNCH();
+    } else if (blocks > 0) {                                 // no shared row and no group row: every pixel is a miss
+        hipLaunchKernelGGL(mesh_frame_raster_groups_kernel, dim3((unsigned)blocks), dim3(MD_THREADS), (size_t)(W + H) * sizeof(float),
+                           pm_stream(stream), verts, vert_part, NV, faces, F, F_shared, group_off, G, env_group, max_group_faces, pose_R,
+                           pose_T, M, cam_pose, V, chunks, fx, fy, cx, cy, H, W, near, far, keys);
+        PM_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(mesh_frame_resolve_kernel, pixel_grid, dim3(MD_THREADS), 0, pm_stream(stream), keys, verts, vert_part, NV,
                        faces, F, pose_R, pose_T, M, cam_pose, V, hw, total, far, part_label, miss_label, palette, ambient,
                        one_minus_ambient, bg_r, bg_g, bg_b, depth, depth_stride, seg, seg_stride, rgb, rgb_stride);
     PM_CHECK_LAUNCH();
     return PM_OK;
+}
+
+extern "C" int pm_mesh_frame_render_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F,
+                                        const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V,
+                                        float fx, float fy, float cx, float cy, int H, int W, float near, float far,
+                                        const int32_t* part_label, int miss_label, const float* palette, float ambient,
+                                        float one_minus_ambient, int bg_r, int bg_g, int bg_b, float* depth, long depth_stride,
+                                        int32_t* seg, long seg_stride, uint8_t* rgb, long rgb_stride, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    return mf_render(verts, vert_part, NV, faces, F, false, 0, nullptr, 0, nullptr, 0,
+                     pose_R, pose_T, B, M, cam_pose, V, fx, fy, cx, cy, H, W, near, far, part_label, miss_label, palette, ambient, one_minus_ambient,
+                     bg_r, bg_g, bg_b, depth, depth_stride, seg, seg_stride, rgb, rgb_stride, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pm_mesh_frame_render_groups_f32(const float* verts, const int32_t* vert_part, int NV, const int32_t* faces, int F,
+                                        int F_shared, const int32_t* group_off, int G, const int32_t* env_group, int max_group_faces,
+                                        const float* pose_R, const float* pose_T, int B, int M, const float* cam_pose, int V,
+                                        float fx, float fy, float cx, float cy, int H, int W, float near, float far,
+                                        const int32_t* part_label, int miss_label, const float* palette, float ambient,
+                                        float one_minus_ambient, int bg_r, int bg_g, int bg_b, float* depth, long depth_stride,
+                                        int32_t* seg, long seg_stride, uint8_t* rgb, long rgb_stride, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    return mf_render(verts, vert_part, NV, faces, F, true, F_shared, group_off, G, env_group, max_group_faces,
+                     pose_R, pose_T, B, M, cam_pose, V, fx, fy, cx, cy, H, W, near, far, part_label, miss_label, palette, ambient, one_minus_ambient,
+                     bg_r, bg_g, bg_b, depth, depth_stride, seg, seg_stride, rgb, rgb_stride, workspace, workspace_bytes, stream);
 }

@@ -3,7 +3,8 @@
 // path for boxes over MD_WAVE_BOX).  Every formula is the definition of include/partmanip_hip.h (pm_mesh_depth_render_f32); the two
 // kernels differ only in what a hit commits, which they hand to md_raster as `commit(dst, z, f)`: dst = the pixel's word of the
 // kernel's own image of the view (img + r W + c), z the hit's depth, f the triangle's row in `faces`.  mesh_depth.hip's header has the definition, the properties that follow
-// from it and the measurements that chose MD_WAVE_BOX.
+// from it and the measurements that chose MD_WAVE_BOX.  Which triangle a lane takes is its kernel's choice (md_raster's `f`): the
+// ungrouped kernels walk the rows of `faces` in order, the grouped ones take md_group_face's row of the environment's own subset.
 #pragma once
 #include "common.h"
 
@@ -80,15 +81,33 @@ __device__ __forceinline__ void md_block(long blk, int chunks, int V, long& b, i
     v = (int)(bv - b * V);
 }
 
-// The raster work of one block: environment b, view v, triangles [chunk MD_THREADS, (chunk + 1) MD_THREADS).  md_tab: W + H floats
-// of LDS; img: the (H, W) image of this environment and view, of whatever word the kernel keeps per pixel.  Every lane of the block
-// must call it (a barrier and wave-wide broadcasts inside).  commit(img + r W + c, z, f) is called for every (pixel, triangle) hit
-// with 0 <= r < H, 0 <= c < W and f the triangle's row in faces, 0 <= f < F.
+// The face row of ordinal t of environment b in the grouped entries (include/partmanip_hip.h, pm_mesh_depth_render_groups_f32): the
+// shared rows [0, F_shared) first, then the rows of the environment's group; -1 ("none") past them.  A group id outside [0, G) is no
+// group; the group's rows are clamped to [F_shared, F) and to max_group_faces rows, so the row returned lies in [0, F) whatever the
+// tables hold.  count: the environment's ordinals.  The host has checked 0 <= F_shared <= F and 0 <= max_group_faces <= F - F_shared.
+__device__ __forceinline__ int md_group_face(int t, long b, int F, int F_shared, const int32_t* __restrict__ group_off, int G,
+                                             const int32_t* __restrict__ env_group, int max_group_faces, int& count) {
+    int lo = 0, n = 0;
+    const int g = G > 0 ? env_group[b] : -1;
+    if (g >= 0 && g < G) {
+        const int room = F - F_shared;
+        lo = min(max(group_off[g], 0), room);
+        n = min(min(max(group_off[g + 1], lo), room) - lo, max_group_faces);
+    }
+    count = F_shared + n;
+    return t < F_shared ? t : (t < count ? F_shared + lo + (t - F_shared) : -1);
+}
+
+// The raster work of one block: environment b, view v, one triangle per lane: f, its row in faces, chosen by the caller (the
+// ungrouped kernels: chunk MD_THREADS + threadIdx.x; the grouped ones: md_group_face); a row outside [0, F) is "none".  md_tab: W + H
+// floats of LDS; img: the (H, W) image of this environment and view, of whatever word the kernel keeps per pixel.  Every lane of the
+// block must call it (a barrier and wave-wide broadcasts inside).  commit(img + r W + c, z, f) is called for every (pixel, triangle)
+// hit with 0 <= r < H, 0 <= c < W and f the triangle's row in faces, 0 <= f < F.
 template <class Word, class Commit>
 __device__ __forceinline__ void md_raster(const float* __restrict__ verts, const int32_t* __restrict__ vert_part, int NV,
                                           const int32_t* __restrict__ faces, int F, const float* __restrict__ pose_R,
                                           const float* __restrict__ pose_T, int M, const float* __restrict__ cam_pose, long b, int v,
-                                          int chunk, float fx, float fy, float cx, float cy, int H, int W, float near, float far,
+                                          int f, float fx, float fy, float cx, float cy, int H, int W, float near, float far,
                                           float* md_tab, Word* img, Commit commit) {
     for (int i = threadIdx.x; i < W + H; i += MD_THREADS)
         md_tab[i] = i < W ? __fdiv_rn(sub_rn((float)i, cx), fx) : __fdiv_rn(sub_rn((float)(i - W), cy), fy);
@@ -98,8 +117,7 @@ __device__ __forceinline__ void md_raster(const float* __restrict__ verts, const
     const float* Tb = pose_T + b * M * 3;
 
     md_tri t = {};
-    const int f = chunk * MD_THREADS + threadIdx.x;
-    if (f < F) {
+    if ((unsigned)f < (unsigned)F) {
         float ax, ay, az, bx, by, bz, qx, qy, qz;
         const bool ok0 = md_vertex(verts, vert_part, NV, M, Rb, Tb, cam, faces[3L * f], ax, ay, az);
         const bool ok1 = md_vertex(verts, vert_part, NV, M, Rb, Tb, cam, faces[3L * f + 1], bx, by, bz);
@@ -141,7 +159,7 @@ __device__ __forceinline__ void md_raster(const float* __restrict__ verts, const
         s.z0 = md_bcast(t.z0, l), s.z1 = md_bcast(t.z1, l), s.z2 = md_bcast(t.z2, l);
         s.x0 = __builtin_amdgcn_readlane(t.x0, l), s.y0 = __builtin_amdgcn_readlane(t.y0, l);
         s.bw = __builtin_amdgcn_readlane(t.bw, l), s.cnt = __builtin_amdgcn_readlane(t.cnt, l);
-        const int fl = f - lane + l;                         // lane l's triangle
+        const int fl = __builtin_amdgcn_readlane(f, l);      // lane l's triangle
         for (int i = lane; i < s.cnt; i += PM_WAVE) {
             const int rr = i / s.bw;
             const int r = s.y0 + rr, c = s.x0 + (i - rr * s.bw);

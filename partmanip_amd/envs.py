@@ -17,6 +17,7 @@ observation after they have stepped."""
 import numpy as np
 import torch
 
+from . import ops
 from .kinematics import KinematicSim, ObjectLibrary
 from .png import write_png
 from .tasks import Franka, GraspCubeTensors, MobileFranka, OpenDrawerTensors
@@ -64,10 +65,29 @@ def depth_img_observer(cam):
     return _Observer(cam.num_view * cam.im_h * cam.im_w, lambda R, T, out: cam.render(R, T, out=out))
 
 
+def depth_tsdf_observer(cam, volume):
+    """mesh2depth.DepthFromMesh and a depth2tsdf.TSDFVolume with the same cameras registered -> resolution^3 columns: the rendered
+    depth images integrated into the volume (the `depth_tsdf` mode of hand_base.py:325-327; integrate returns its own tensor, so
+    this one copies into the row)."""
+    n = int(volume._resolution) ** 3
+
+    def write(R, T, out):
+        out[:, :n].copy_(volume.integrate(cam.render(R, T)).reshape(out.shape[0], -1))
+    return _Observer(n, write)
+
+
+def depth_sparse_observer(cam, volume, K=1024):
+    """The same pair -> 4 * K columns: rows (x, y, z, tsdf) of K voxels near the surface (the `depth_sparse` mode of
+    hand_base.py:335-336, TSDFVolume.sparse_voxel)."""
+    def write(R, T, out):
+        out[:, :4 * K].copy_(volume.sparse_voxel(cam.render(R, T), K=K).reshape(out.shape[0], -1))
+    return _Observer(4 * K, write)
+
+
 def frame_recorder(cam, env=0, view=0):
     """mesh2depth.DepthFromMesh -> record(pose_R, pose_T, path): the colour image of environment `env` in view `view` written to
     `path` as a PNG (the image hand_base.py:355-357 saves).  Only that environment is rendered (b = 1, a slice of the poses, rgb
-    only).  The copy to the host SYNCHRONISES the stream; it happens only for a frame somebody asked for."""
+    only; a camera built with groups= is told that environment's object).  The copy to the host SYNCHRONISES the stream; it happens only for a frame somebody asked for."""
     env, view = int(env), int(view)
     if not 0 <= view < cam.num_view:
         raise ValueError(f"frame_recorder: view {view} outside [0, {cam.num_view})")
@@ -75,25 +95,35 @@ def frame_recorder(cam, env=0, view=0):
     def record(pose_R, pose_T, path):
         if not 0 <= env < pose_R.shape[0]:
             raise ValueError(f"frame_recorder: environment {env} outside [0, {pose_R.shape[0]})")
-        frame = cam.render_frame(pose_R[env:env + 1], pose_T[env:env + 1], depth=False, seg=False, rgb=True)
+        group = cam.group_of[env:env + 1] if getattr(cam, "groups", False) else None
+        frame = cam.render_frame(pose_R[env:env + 1], pose_T[env:env + 1], depth=False, seg=False, rgb=True, group_of=group)
         write_png(path, frame.rgb[0, view].cpu().numpy())
     return record
 
 
 class KinematicEnv:
     """task: GraspCubeTensors over sim = KinematicSim(free_body=True), or OpenDrawerTensors over KinematicSim(objects=...).
-    observers: {mode: pc_observer(...) / tsdf_observer(...) / depth_pc_observer(...) / depth_img_observer(...)}; with add_proprio_obs the proprio row is the
+    observers: {mode: pc_observer(...) / tsdf_observer(...) / depth_pc_observer(...) / depth_img_observer(...) / depth_tsdf_observer(...) /
+    depth_sparse_observer(...)}; with add_proprio_obs the proprio row is the
     tail of every such mode's row (for grasp_cube the first mode's tail is written by end_step(obs_out=) itself: no cat).
     num_obs reports the widths returned.  grasp_width: the grasp predicate's (grasp_cube); hold=False switches the rule off (the
     cube, or the drawer, then never moves), hold='always' sets the flag in every environment whatever the predicate says (the
     "held" of kinematics.py: a flag the caller sets).  random_reset: the cube's reset draws u with torch.rand (default: the task cfg's `random_reset`, False).
     recorder: frame_recorder(cam, ...) or None; with one, step(actions, save_image_path=p) writes the frame after the step to p (the
-    runners pass such a path when `save_video` is set); without one the path is ignored."""
+    runners pass such a path when `save_video` is set); without one the path is ignored.
+    scene_rows (N, M) int32 on the device (rows of sim.rigid_body, -1 for an empty slot) with scene_C (MC, 3, 3) or None: observers
+    and recorder are then handed the poses of these M bodies from one ops.body_pose_gather launch per step, in place of the task's
+    own parts (make_open_drawer_env(scene_meshes=) builds the table)."""
 
     def __init__(self, task, sim, observers=None, add_proprio_obs=False, grasp_width=GRASP_WIDTH, hold=True, random_reset=False,
-                 recorder=None):
+                 recorder=None, scene_rows=None, scene_C=None):
         self.task, self.sim = task, sim
         self.recorder, self._scene_pose = recorder, None
+        self.scene_rows, self.scene_C = scene_rows, scene_C
+        if scene_rows is not None:
+            f32 = dict(dtype=torch.float32, device=sim.device)
+            self._scene_R = [torch.empty(*scene_rows.shape, 3, 3, **f32) for _ in range(2)]     # two sets, used in turn like the rows
+            self._scene_T = [torch.empty(*scene_rows.shape, 3, **f32) for _ in range(2)]
         self.grasp = isinstance(task, GraspCubeTensors)
         if self.grasp != bool(getattr(sim, "free_body", False)) or (not self.grasp and sim.objects is None):
             raise ValueError("KinematicEnv: a GraspCubeTensors needs KinematicSim(free_body=True), an OpenDrawerTensors KinematicSim(objects=...)")
@@ -159,7 +189,7 @@ class KinematicEnv:
             torch.gt(task.extras["is_grasped"], 0, out=self._hold)
         self._scene_pose = None
         if self.observers:
-            R, T = self._scene_pose = task.compute_scene_pose()
+            R, T = self.compute_scene_pose()
             for mode, ob in self.observers.items():
                 ob.write(R, T, rows[mode])
                 if self.add_proprio_obs and not (self.grasp and mode == first):
@@ -197,13 +227,24 @@ class KinematicEnv:
             sim.step(task.pos_act, reset, hold=hold)
         obs = self._observe()
         if save_image_path is not None and self.recorder is not None:
-            R, T = self._scene_pose or task.compute_scene_pose()         # the observers' pose where there are observers
+            R, T = self.compute_scene_pose()                              # the observers' pose where there are observers
             self.recorder(R, T, save_image_path)
         return obs, task.rew_buf, task.reset_buf, dict(task.extras)
 
+    def compute_scene_pose(self):
+        """(rot (N, M, 3, 3), pos (N, M, 3)) of the last step, as the observers and the recorder get them: the task's own parts, or
+        with scene_rows the M bodies of the table (gathered once per step, on first use)."""
+        if self._scene_pose is None:
+            if self.scene_rows is None:
+                self._scene_pose = self.task.compute_scene_pose()
+            else:
+                self._scene_pose = ops.body_pose_gather(self.sim.rigid_body, self.scene_rows, self.scene_C,
+                                                        self._scene_R[self._slot], self._scene_T[self._slot])
+        return self._scene_pose
+
     def save_scene_pose(self, path=None):
         """hand_base.save_scene_pose: the posed parts of the last step on the host (a synchronisation; the runners call it in eval)."""
-        rot, pos = self.task.compute_scene_pose()
+        rot, pos = self.compute_scene_pose()
         return {"rot": rot.cpu().numpy(), "pos": pos.cpu().numpy()}
 
 
@@ -237,10 +278,29 @@ def make_grasp_cube_env(cfg_task, num_envs, device, urdf, dt, base_pose=None, do
                         random_reset=bool(cfg_task.get("random_reset", False)), recorder=recorder)
 
 
+def scene_row_table(part_slot, rb_row0, obj_rb_row0, obj_bodies, max_bodies=None):
+    """The (N, M) int32 row table of a scene whose environments differ, on the host: slot p < len(part_slot) of environment e is the
+    robot body rb_row0[e] + part_slot[p]; slot len(part_slot) + j is body j of the environment's object, obj_rb_row0[e] + j, and -1
+    from the object's body count on.  M = len(part_slot) + max_bodies (default: the largest body count among the environments)."""
+    part_slot, rb_row0, obj_rb_row0, obj_bodies = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (part_slot, rb_row0, obj_rb_row0,
+                                                                                                          obj_bodies))
+    most = int(obj_bodies.max()) if max_bodies is None else int(max_bodies)
+    if most < int(obj_bodies.max()):
+        raise ValueError(f"max_bodies {most} below an object's {int(obj_bodies.max())} bodies")
+    j = np.arange(most)[None]
+    cab = np.where(j < obj_bodies[:, None], obj_rb_row0[:, None] + j, -1)
+    return np.ascontiguousarray(np.concatenate([rb_row0[:, None] + part_slot[None], cab], axis=1), dtype=np.int32)
+
+
 def make_open_drawer_env(cfg_task, num_envs, device, urdf, assets, dt, observers=None, add_proprio_obs=False, hold=True,
-                         max_velocity=None, recorder=None):
+                         max_velocity=None, recorder=None, scene_meshes=None):
     """OpenDrawerTensors + KinematicSim(objects=...) wired as INTEGRATION.md's loop: assets = load_drawer_assets(folders, scale),
-    handed out as env % num_objs; the robot of `urdf` (the mobile Franka of the shipped config, or the fixed one)."""
+    handed out as env % num_objs; the robot of `urdf` (the mobile Franka of the shipped config, or the fixed one).
+    scene_meshes: None, or load_drawer_meshes(assets) -- the same list a DepthFromMesh(meshes=robot parts, groups=scene_meshes,
+    group_of=env.task.obj_id) was built from.  Observers and recorder then get the poses of the robot's posed parts (with their
+    mesh-frame matrices) followed by EVERY body of the environment's own cabinet, in the tree's body order, NaN past its body count:
+    scene_row_table over the sim's rows, env.scene_rows, one body_pose_gather launch per step.  Without it they get the task's 13
+    parts (the robot's, the target link, the handle), as before."""
     tree = load_urdf(urdf) if isinstance(urdf, str) else urdf
     envs = assets.for_envs(num_envs)
     kw = tree.robot_kwargs()
@@ -250,4 +310,17 @@ def make_open_drawer_env(cfg_task, num_envs, device, urdf, assets, dt, observers
                              **envs.task_kwargs())
     sim = KinematicSim(tree, num_envs, device, dt, max_velocity=max_velocity, objects=ObjectLibrary(assets.trees, device),
                        obj_type=envs.obj_id, target_dof=envs.target_dof, tips=(robot.ltip_rb_index, robot.rtip_rb_index))
-    return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, hold=hold, recorder=recorder)
+    rows = C = None
+    if scene_meshes is not None:
+        if len(scene_meshes) != assets.num_objs:
+            raise ValueError(f"scene_meshes: expected one list per object ({assets.num_objs}), got {len(scene_meshes)}")
+        for k, bodies in enumerate(scene_meshes):
+            if len(bodies) != int(assets.num_bodies[k]):
+                raise ValueError(f"scene_meshes[{k}]: expected one entry per body ({int(assets.num_bodies[k])}), got {len(bodies)}")
+        nr = task.part_slot.numel() - 2                       # the robot's posed parts; the last two are the target link and the handle
+        rows = scene_row_table(task.part_slot[:nr].cpu().numpy(), sim.rb_row0.cpu().numpy(), sim.obj_rb_row0.cpu().numpy(),
+                               envs.obj_bodies, max_bodies=int(assets.num_bodies.max()))
+        rows = torch.from_numpy(rows).to(device)
+        C = None if task.part_C is None else task.part_C[:nr].contiguous()
+    return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, hold=hold, recorder=recorder, scene_rows=rows,
+                        scene_C=C)

@@ -21,6 +21,16 @@ the same depth, a part label (the reference's IMAGE_SEGMENTATION, hand_base.py:2
 mask, load_robot.py:83) and a shaded colour (the image hand_base.py:355-357 saves).  All three are defined bit for bit; the nearest
 triangle wins a pixel, the smaller row of `faces` on a tie.  The shading -- a headlight along the optical axis over a fixed palette
 -- is this project's choice, not Isaac Gym's renderer.  Sensor noise and `is_camera_rand` are out of scope.
+
+A scene whose environments differ (open_drawer: every environment holds its own cabinet, env % num_objs):
+
+    cam = DepthFromMesh(N, device, ..., meshes=robot_parts, groups=load_drawer_meshes(assets), group_of=envs.obj_id)
+
+`meshes` are the parts every environment draws (slots 0 .. len(meshes) - 1); groups[k][j] is the mesh of body j of object k, or
+None, and takes slot len(meshes) + j in whatever environment holds object k.  render / render_frame then take (N, part_num, ...)
+poses with part_num = len(meshes) + the largest body count, and call the grouped entries (pm_mesh_depth_render_groups_f32,
+pm_mesh_frame_render_groups_f32): an environment pays the triangle set-up of its own object only, not of the whole library.
+Textures and materials are not read, and `is_camera_rand` stays out of scope.
 """
 import collections
 
@@ -43,10 +53,14 @@ class DepthFromMesh:
     near = 0.01 is this project's choice, not Isaac Gym's clip plane; both faces of a triangle are hit (two-sided).
     For render_frame: labels (M,) ints, the seg value of each part (None: the part index), miss_label the seg value where nothing
     is hit; palette (M, 3) colours in 0..255 (None: PALETTE, cycled); ambient in [0, 1], the share of a colour that a surface seen
-    edge-on keeps; background, the colour where nothing is hit."""
+    edge-on keeps; background, the colour where nothing is hit.
+    groups: None, or one list per object of (vertices, faces)-or-None per body (tasks.open_drawer.load_drawer_meshes); group_of
+    (num_envs,) ints in [-1, len(groups)): the object each environment holds, -1 for none (default: env % len(groups), the
+    reference's rule).  Slots, labels and palette then cover part_num = len(meshes) + the largest body count; attributes: num_shared
+    (the shared slots), face_shared, group_off (numpy), group_of (numpy), max_group_faces.  With groups, `meshes` may be empty."""
 
     def __init__(self, num_envs, device, cam_pose, cam_intr, im_h, im_w, asset_root='.', meshes=None, near=0.01, far=100.0,
-                 labels=None, miss_label=-1, palette=None, ambient=0.25, background=(255, 255, 255)):
+                 labels=None, miss_label=-1, palette=None, ambient=0.25, background=(255, 255, 255), groups=None, group_of=None):
         self.num_envs = num_envs
         self.device = device
         self.asset_root = asset_root
@@ -68,20 +82,46 @@ class DepthFromMesh:
         self.cam_pose = torch.from_numpy(np.ascontiguousarray(pose)).to(self.device)
         if meshes is None:
             meshes = [meshio.load_mesh(path) for path in meshio.scene_mesh_paths(asset_root)]
-        if len(meshes) == 0:
+        if len(meshes) == 0 and not groups:
             raise ValueError("meshes: at least one part is needed")
+        if group_of is not None and groups is None:
+            raise ValueError("group_of: needs groups=")
         verts, part, faces, base = [], [], [], 0
-        for i, (v, f) in enumerate(meshes):
-            v, f = np.asarray(v, dtype=np.float32), np.asarray(f, dtype=np.int64)
+
+        def add(mesh, slot, what):
+            nonlocal base
+            v, f = np.asarray(mesh[0], dtype=np.float32), np.asarray(mesh[1], dtype=np.int64)
             if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or len(v) == 0 or len(f) == 0:
-                raise ValueError(f"meshes[{i}]: expected vertices (n > 0, 3) and faces (f > 0, 3), got {v.shape} and {f.shape}")
+                raise ValueError(f"{what}: expected vertices (n > 0, 3) and faces (f > 0, 3), got {v.shape} and {f.shape}")
             if f.min() < 0 or f.max() >= len(v):
-                raise ValueError(f"meshes[{i}]: a face index lies outside [0, {len(v)})")
+                raise ValueError(f"{what}: a face index lies outside [0, {len(v)})")
             verts.append(v)
-            part.append(np.full(len(v), i, dtype=np.int32))
+            part.append(np.full(len(v), slot, dtype=np.int32))
             faces.append(f + base)
             base += len(v)
-        self.part_num = len(meshes)
+            return len(f)
+
+        for i, mesh in enumerate(meshes):
+            add(mesh, i, f"meshes[{i}]")
+        self.num_shared = self.part_num = len(meshes)
+        self.face_shared = sum(len(f) for f in faces)
+        self.groups = groups is not None
+        if self.groups:
+            groups = [list(g) for g in groups]
+            if not groups:
+                raise ValueError("groups: at least one object is needed")
+            off = [0]
+            for k, bodies in enumerate(groups):
+                off.append(off[-1] + sum(add(mesh, self.num_shared + j, f"groups[{k}][{j}]") for j, mesh in enumerate(bodies)
+                                         if mesh is not None))
+            self.part_num += max(len(bodies) for bodies in groups)
+            self.group_off = np.asarray(off, dtype=np.int32)
+            self.max_group_faces = int(np.diff(self.group_off).max())
+            if not verts:
+                raise ValueError("meshes and groups: no mesh at all")
+            self.group_of = self._host_group_of(np.arange(int(num_envs)) % len(groups) if group_of is None else group_of, int(num_envs))
+            self._group_off = torch.from_numpy(self.group_off).to(self.device)
+            self._group_of = torch.from_numpy(self.group_of).to(self.device)
         self.verts = torch.from_numpy(np.ascontiguousarray(np.concatenate(verts))).to(self.device)               # (NV, 3)
         self.vert_part = torch.from_numpy(np.concatenate(part)).to(self.device)                                  # (NV,) int32
         self.faces = torch.from_numpy(np.ascontiguousarray(np.concatenate(faces).astype(np.int32))).to(self.device)   # (F, 3) int32
@@ -106,29 +146,61 @@ class DepthFromMesh:
             raise ValueError(f"background: expected three values in 0..255, got {background}")
         self._keys = ops.Workspace(self.device)                                                 # render_frame's 64-bit keys, grown on demand
 
-    def render(self, pose_R, pose_T, out=None):
+    def _host_group_of(self, group_of, b):
+        g = np.asarray(group_of.cpu().numpy() if torch.is_tensor(group_of) else group_of)
+        G = len(self.group_off) - 1
+        if g.shape != (b,) or g.dtype.kind not in "iu" or g.min() < -1 or g.max() >= G:
+            raise ValueError(f"group_of: expected {b} integers in [-1, {G}), got {g.dtype} {g.shape}")
+        return np.ascontiguousarray(g, dtype=np.int32)
+
+    def _env_groups(self, b, group_of):
+        """The (F_shared, group_off, env_group, max_group_faces) of a call over b environments: the table of the constructor, or the
+        call's own group_of (b ints on the host, or an int32 tensor on the device, which is not read here)."""
+        if not self.groups:
+            if group_of is not None:
+                raise ValueError("group_of: this camera was built without groups=")
+            return None
+        if group_of is None:
+            if b != self.num_envs:
+                raise ValueError(f"poses: expected {self.num_envs} environments (the group table's), got {b}; pass group_of= for a slice")
+            eg = self._group_of
+        elif torch.is_tensor(group_of) and group_of.is_cuda:
+            eg = group_of
+        else:
+            eg = torch.from_numpy(self._host_group_of(group_of, b)).to(self.device)
+        return self.face_shared, self._group_off, eg, self.max_group_faces
+
+    def render(self, pose_R, pose_T, out=None, group_of=None):
         """pose_R [b, m, 3, 3], pose_T [b, m, 3] (any b) -> [b, V, im_h, im_w] float32: the z-depth (not the ray length) of the
         nearest surface through every pixel centre, `far` where nothing is hit.
         out: None, or a 2-D float32 view (b, >= V h w) with unit inner stride (e.g. the head of a depth_img observation buffer); the
-        result is then a view of its first V h w columns."""
+        result is then a view of its first V h w columns.  With groups=: b = num_envs, or group_of= (b,) names the object of each
+        row of this call (frame_recorder's one-environment slice)."""
         b, _ = ops.check_poses(pose_R, pose_T, self.part_num)
         n = self.num_view * self.im_h * self.im_w
         if out is not None:
             ops._out_rows(out, b, n)                                                           # a bad view is reported before the device
+        groups = self._env_groups(b, group_of)
         ops._req(pose_R, pose_T, out, self.verts)
         pose_R, pose_T = pose_R.contiguous(), pose_T.contiguous()
+        if groups is not None:
+            res = ops.mesh_depth_render_groups(self.verts, self.vert_part, self.faces, groups[0], groups[1], groups[2], pose_R, pose_T,
+                                               self.cam_pose, self.fx, self.fy, self.cx, self.cy, self.im_h, self.im_w, self.near,
+                                               self.far, out, max_group_faces=groups[3])
+            return res[:, :n].unflatten(1, (self.num_view, self.im_h, self.im_w))
         res = ops.mesh_depth_render(self.verts, self.vert_part, self.faces, pose_R, pose_T, self.cam_pose, self.fx, self.fy, self.cx,
                                     self.cy, self.im_h, self.im_w, self.near, self.far, out)
         return res[:, :n].unflatten(1, (self.num_view, self.im_h, self.im_w))
 
-    def render_frame(self, pose_R, pose_T, depth=True, seg=True, rgb=True, out_depth=None):
+    def render_frame(self, pose_R, pose_T, depth=True, seg=True, rgb=True, out_depth=None, group_of=None):
         """pose_R [b, m, 3, 3], pose_T [b, m, 3] (any b) -> Frame(depth, seg, rgb) from one rasterisation, each None when switched off:
         depth [b, V, im_h, im_w] float32, the bits render() gives; seg [b, V, im_h, im_w] int32, labels[part] of the nearest
         triangle (the smaller row of `faces` on a tie), miss_label where nothing is hit; rgb [b, V, im_h, im_w, 3] uint8, the part's
         palette colour times ambient + (1 - ambient) |n.z| with n the triangle's unit normal in camera space, `background`
         where nothing is hit.  out_depth: as render()'s out.  The keys' workspace (8 b V im_h im_w bytes) belongs to this object and
-        is reused while b fits."""
+        is reused while b fits.  group_of: as render()'s."""
         b, _ = ops.check_poses(pose_R, pose_T, self.part_num)
+        groups = self._env_groups(b, group_of)
         if not (depth or seg or rgb):
             raise ValueError("render_frame: depth, seg and rgb are all switched off")
         if out_depth is not None and not depth:
@@ -144,6 +216,6 @@ class DepthFromMesh:
                                         miss_label=self.miss_label, palette=self.palette if rgb else None, ambient=self.ambient,
                                         one_minus_ambient=self.one_minus_ambient, background=self.background,
                                         depth=(True if out_depth is None else out_depth) if depth else False, seg=bool(seg),
-                                        rgb=bool(rgb))
+                                        rgb=bool(rgb), groups=groups)
         return Frame(None if d is None else d[:, :n].unflatten(1, (V, h, w)), None if s is None else s.unflatten(1, (V, h, w)),
                      None if c is None else c.unflatten(1, (V, h, w, 3)))

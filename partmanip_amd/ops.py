@@ -6,6 +6,8 @@ raw device pointers to libpartmanip_hip.so.  Ops refuse CPU tensors -- there is 
 import ctypes as C
 import os
 
+import numpy as np
+
 import torch
 
 from ._lib import lib, check
@@ -1478,9 +1480,63 @@ def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy,
     return out
 
 
+def face_groups(group_off, env_group, F, F_shared, B, device, max_group_faces=None):
+    """The group arguments of mesh_depth_render_groups / mesh_frame_render_groups -> (group_off (G + 1) int32 on `device`, env_group
+    (B) int32 on `device`, G, max_group_faces).  Host arrays (numpy, lists, CPU tensors) are validated here -- group_off starts at 0,
+    never decreases and ends at F - F_shared; env_group holds B values in [-1, G) -- and copied to the device, and max_group_faces
+    is computed from them.  Device tensors are only checked for type and length (reading them would synchronise; the kernel clamps
+    whatever they hold) and need max_group_faces from the caller."""
+    F, F_shared, B = int(F), int(F_shared), int(B)
+    if not 0 <= F_shared <= F:
+        raise ValueError(f"F_shared: expected a value in [0, {F}], got {F_shared}")
+    on_device = [torch.is_tensor(a) and a.is_cuda for a in (group_off, env_group)]
+    if on_device[0] != on_device[1]:
+        raise ValueError("group_off and env_group: expected both on the host or both on the device")
+    if on_device[0]:
+        if max_group_faces is None:
+            raise ValueError("max_group_faces: needed with device tables (the host arrays give it for free)")
+        _i32c(group_off, "group_off"), _i32c(env_group, "env_group")
+        if group_off.dim() != 1 or group_off.numel() < 1 or tuple(env_group.shape) != (B,):
+            raise ValueError(f"group_off / env_group: expected (G + 1,) and ({B},), got {tuple(group_off.shape)} and {tuple(env_group.shape)}")
+        if int(max_group_faces) < 0:
+            raise ValueError(f"max_group_faces: expected a non-negative count, got {max_group_faces}")
+        return group_off, env_group, group_off.numel() - 1, int(max_group_faces)
+    off, eg = (np.asarray(a.numpy() if torch.is_tensor(a) else a) for a in (group_off, env_group))
+    if off.dtype.kind not in "iu" or eg.dtype.kind not in "iu" or off.ndim != 1 or off.size < 1 or eg.shape != (B,):
+        raise ValueError(f"group_off / env_group: expected integers (G + 1,) and ({B},), got {off.dtype} {off.shape} and {eg.dtype} {eg.shape}")
+    off, eg = off.astype(np.int64), eg.astype(np.int64)
+    G = off.size - 1
+    if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != F - F_shared:
+        raise ValueError(f"group_off: expected a non-decreasing table from 0 to F - F_shared = {F - F_shared}, got {off.tolist()}")
+    if eg.min() < -1 or eg.max() >= G:
+        raise ValueError(f"env_group: values must lie in [-1, {G}), got [{eg.min()}, {eg.max()}]")
+    most = int(np.diff(off).max()) if G else 0
+    if max_group_faces is not None and int(max_group_faces) < most:
+        raise ValueError(f"max_group_faces: {max_group_faces} is below the largest group's {most} rows")
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)       # noqa: E731
+    return i32(off), i32(eg), G, most if max_group_faces is None else int(max_group_faces)
+
+
+def mesh_depth_render_groups(verts, vert_part, faces, F_shared, group_off, env_group, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h,
+                             im_w, near=0.01, far=100.0, out=None, max_group_faces=None):
+    """mesh_depth_render over a scene whose environments differ (pm_mesh_depth_render_groups_f32): environment b draws rows
+    [0, F_shared) of faces and the rows of group env_group[b] (-1: none), group g being rows F_shared + [group_off[g], group_off[g + 1]).
+    group_off / env_group / max_group_faces as face_groups takes them; everything else, and the result, as mesh_depth_render."""
+    NV, B, M, V, im_h, im_w = _mesh_camera_args(verts, vert_part, faces, pose_R, pose_T, cam_pose, im_h, im_w, near, far)
+    group_off, env_group, G, most = face_groups(group_off, env_group, faces.shape[0], F_shared, B, pose_R.device, max_group_faces)
+    _one_device("mesh_depth_render_groups", verts, vert_part, faces, group_off, env_group, pose_R, pose_T, cam_pose, out)
+    out, ldo = _out_rows(out, B, V * im_h * im_w, pose_R.device)
+    with TIMER.bracket("mesh_depth_render_groups"):
+        check(lib.pm_mesh_depth_render_groups_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], int(F_shared),
+                                                  _ptr(group_off), G, _ptr(env_group), most, _ptr(pose_R), _ptr(pose_T), B, M,
+                                                  _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w, float(near),
+                                                  float(far), _ptr(out), ldo, _stream()), "pm_mesh_depth_render_groups_f32")
+    return out
+
+
 def mesh_frame_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h, im_w, near, far, workspace,
                       part_label=None, miss_label=-1, palette=None, ambient=0.25, one_minus_ambient=None, background=(255, 255, 255),
-                      depth=True, seg=True, rgb=True):
+                      depth=True, seg=True, rgb=True, groups=None):
     """Depth, part-label and shaded colour images of the posed part meshes from one rasterisation (pm_mesh_frame_render_f32); the
     geometry, pose and camera arguments are mesh_depth_render's.  part_label (M) int32 or None (the part index itself), miss_label
     for pixels nothing hits; palette (M, 3) float32 in [0, 255], ambient and one_minus_ambient (default 1 - ambient) the headlight's
@@ -1488,7 +1544,8 @@ def mesh_frame_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy,
     int32 / (B, 3 V h w) uint8) or a 2-D view of that type with at least that many columns and unit inner stride; columns past
     them are left alone.  workspace: a device tensor of at least pm_mesh_frame_workspace_bytes(B, V, h, w) bytes, 8-byte aligned
     (the library checks both).  Returns (depth, seg, rgb) with None for the ones switched off.  The winner of a pixel is the nearest
-    triangle, the smaller row of `faces` on a tie; all three images are defined bit for bit (include/partmanip_hip.h)."""
+    triangle, the smaller row of `faces` on a tie; all three images are defined bit for bit (include/partmanip_hip.h).
+    groups: None, or mesh_frame_render_groups' (F_shared, group_off, env_group, max_group_faces)."""
     outs = [o if torch.is_tensor(o) else None for o in (depth, seg, rgb)]
     _one_device("mesh_frame_render", verts, vert_part, faces, pose_R, pose_T, cam_pose, workspace, part_label, palette, *outs)
     NV, B, M, V, im_h, im_w = _mesh_camera_args(verts, vert_part, faces, pose_R, pose_T, cam_pose, im_h, im_w, near, far)
@@ -1517,6 +1574,20 @@ def mesh_frame_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy,
     if rgb is not False:
         rgb, ldc = _out_rows(None if rgb is True else rgb, B, 3 * n, dev, torch.uint8, "rgb")
     d_, s_, c_ = (None if o is False else o for o in (depth, seg, rgb))
+    if groups is not None:
+        F_shared, group_off, env_group, most = groups
+        group_off, env_group, G, most = face_groups(group_off, env_group, faces.shape[0], F_shared, B, dev, most)
+        _one_device("mesh_frame_render_groups", verts, group_off, env_group)
+        with TIMER.bracket("mesh_frame_render_groups"):
+            check(lib.pm_mesh_frame_render_groups_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], int(F_shared),
+                                                      _ptr(group_off), G, _ptr(env_group), most, _ptr(pose_R), _ptr(pose_T), B, M,
+                                                      _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w,
+                                                      float(near), float(far), _ptr(part_label), int(miss_label), _ptr(palette),
+                                                      float(ambient), one_minus_ambient, bg[0], bg[1], bg[2], _ptr(d_), ldd, _ptr(s_),
+                                                      lds, _ptr(c_), ldc, _ptr(workspace),
+                                                      workspace.numel() * workspace.element_size(), _stream()),
+                  "pm_mesh_frame_render_groups_f32")
+        return d_, s_, c_
     with TIMER.bracket("mesh_frame_render"):
         check(lib.pm_mesh_frame_render_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], _ptr(pose_R), _ptr(pose_T),
                                            B, M, _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w,
@@ -1525,6 +1596,47 @@ def mesh_frame_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy,
                                            _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
               "pm_mesh_frame_render_f32")
     return d_, s_, c_
+
+
+def mesh_frame_render_groups(verts, vert_part, faces, F_shared, group_off, env_group, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h,
+                             im_w, near, far, workspace, max_group_faces=None, **kw):
+    """mesh_frame_render over a scene whose environments differ (pm_mesh_frame_render_groups_f32): the face subset of an environment
+    as in mesh_depth_render_groups, the winner the nearest triangle of the subset (the smaller row of `faces` on a tie); the
+    keywords and the result are mesh_frame_render's."""
+    return mesh_frame_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h, im_w, near, far, workspace,
+                             groups=(F_shared, group_off, env_group, max_group_faces), **kw)
+
+
+def body_pose_gather(rigid_body, rows, part_C=None, pose_R=None, pose_T=None):
+    """Body poses of a whole scene in one launch (pm_body_pose_gather_f32): rigid_body (..., 13) float32 contiguous, read as flat rows;
+    rows (B, M) int32, slot m of environment b is flat row rows[b, m] (outside [0, rows): a NaN pose); part_C (MC <= M, 3, 3) or None:
+    the mesh-frame matrices of the first MC slots.  pose_R (B, M, 3, 3) / pose_T (B, M, 3): None (fresh) or contiguous float32
+    tensors to write.  Returns (pose_R, pose_T): the position, and quat_to_mat(q) (times C_m for m < MC) exactly as the task kernels
+    compute them."""
+    _one_device("body_pose_gather", rigid_body, rows, part_C, pose_R, pose_T)
+    _f32c(rigid_body, "rigid_body")
+    if rigid_body.dim() < 2 or rigid_body.shape[-1] != 13 or rigid_body.numel() == 0:
+        raise ValueError(f"rigid_body: expected (..., 13) with at least one row, got {tuple(rigid_body.shape)}")
+    _i32c(rows, "rows")
+    if rows.dim() != 2 or rows.numel() == 0:
+        raise ValueError(f"rows: expected (B > 0, M > 0), got {tuple(rows.shape)}")
+    B, M = rows.shape
+    MC = 0
+    if part_C is not None:
+        _f32c(part_C, "part_C")
+        if part_C.dim() != 3 or tuple(part_C.shape[1:]) != (3, 3) or part_C.shape[0] > M:
+            raise ValueError(f"part_C: expected (MC <= {M}, 3, 3), got {tuple(part_C.shape)}")
+        MC = part_C.shape[0]
+    f = dict(dtype=torch.float32, device=rigid_body.device)
+    pose_R = torch.empty(B, M, 3, 3, **f) if pose_R is None else pose_R
+    pose_T = torch.empty(B, M, 3, **f) if pose_T is None else pose_T
+    _f32c(pose_R, "pose_R"), _f32c(pose_T, "pose_T")
+    if tuple(pose_R.shape) != (B, M, 3, 3) or tuple(pose_T.shape) != (B, M, 3):
+        raise ValueError(f"pose_R / pose_T: expected ({B}, {M}, 3, 3) and ({B}, {M}, 3), got {tuple(pose_R.shape)} and {tuple(pose_T.shape)}")
+    with TIMER.bracket("body_pose_gather"):
+        check(lib.pm_body_pose_gather_f32(_ptr(rigid_body), rigid_body.numel() // 13, _ptr(rows), B, M, _ptr(part_C if MC else None), MC,
+                                          _ptr(pose_R), _ptr(pose_T), _stream()), "pm_body_pose_gather_f32")
+    return pose_R, pose_T
 
 
 def _vec(t_, name, n, dtype=torch.float32):

@@ -170,6 +170,14 @@ def load_drawer_assets(folders, scale=0.5):
                         cols["dir"], cols["lower"], cols["upper"])
 
 
+def load_drawer_meshes(assets):
+    """DrawerAssets -> one list per object of (vertices, faces)-or-None per body, in the tree's body order: the visual meshes of each
+    folder's mobility_new.urdf at the assets' scale (urdf.load_urdf_visuals).  It is the `groups=` of mesh2depth.DepthFromMesh and
+    the `scene_meshes=` of envs.make_open_drawer_env."""
+    from ..urdf import load_urdf_visuals
+    return [load_urdf_visuals(os.path.join(folder, "mobility_new.urdf"), scale=assets.scale) for folder in assets.folders]
+
+
 def _host_ints(x, name, shape):
     a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
     if a.dtype.kind not in "iu":

@@ -10,7 +10,9 @@ closed):
   * `rpy` is fixed-axis roll-pitch-yaw, R = Rz(yaw) Ry(pitch) Rx(roll), computed in float64 and kept as a unit quaternion (x, y, z, w).
 DOFs are numbered in body order.  `<mimic>` is ignored, as the reference's simulator does (both fingers are DOFs); a `continuous`
 joint is a revolute one without limits.  Any other joint type, a second root, a cycle or an unknown link raises a ValueError that
-names the joint.  At most 64 bodies and 64 DOFs (the ancestor masks are 64-bit and the kernel stages one robot per lane)."""
+names the joint.  At most 64 bodies and 64 DOFs (the ancestor masks are 64-bit and the kernel stages one robot per lane).
+
+    meshes = load_urdf_visuals("mobility_new.urdf", scale=0.5)    # per body, in that order: (vertices, faces) in the body's frame, or None"""
 import os
 import xml.etree.ElementTree as ET
 
@@ -174,3 +176,65 @@ def load_urdf(path_or_string, scale=1.0):
         raise ValueError(f"joint {child_of[lost].get('name')!r} is part of a cycle: link {lost!r} is not reachable from the root "
                          f"{roots[0]!r}")
     return KinematicTree(names, joint_names, parent, jtype, origin_t, origin_rpy, axis, limits, has_mesh)
+
+
+def _rpy_matrix(rpy):
+    """Rz(yaw) Ry(pitch) Rx(roll) in float64: the rotation rpy_to_quat encodes."""
+    r, p, y = (float(v) for v in rpy)
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    return np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
+                     [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
+                     [-sp, cp * sr, cp * cr]], dtype=np.float64)
+
+
+def load_urdf_visuals(path, scale=1.0):
+    """The visual meshes of a URDF file, one entry per body in load_urdf's body order: (vertices (n, 3) float32, faces (f, 3) int64)
+    in the body's frame, or None for a body without a mesh.  A body's mesh is every <visual> of its link that has a geometry/mesh,
+    concatenated in file order; where no visual has one, the <collision> meshes instead.  A mesh is read by meshio.load_mesh from
+    its file name taken relative to the URDF's folder (a leading `package://` is dropped), multiplied by the mesh tag's `scale`
+    (default 1 1 1), moved by the visual's <origin xyz rpy> (rpy as in rpy_to_quat: Rz Ry Rx), then multiplied by `scale` -- the
+    simulator's actor scale, as in load_urdf; all in float64, rounded to float32 once.  Textures and materials are not read.
+    ValueError, naming the file and the link: a missing mesh file, a mesh that cannot be read, a face index out of range."""
+    from . import meshio
+    scale = float(scale)
+    if not scale > 0 or not np.isfinite(scale):
+        raise ValueError(f"scale: expected a positive finite number, got {scale}")
+    path = os.fspath(path)
+    tree = load_urdf(path)
+    folder = os.path.dirname(os.path.abspath(path))
+    with open(path, encoding="utf-8") as f:
+        links = {ln.get("name"): ln for ln in ET.fromstring(f.read()).findall("link")}
+    out = []
+    for name in tree.names:
+        shapes = []
+        for tag in ("visual", "collision"):
+            shapes = [e for e in links[name].findall(tag) if e.find("geometry/mesh") is not None]
+            if shapes:
+                break
+        verts, faces, base = [], [], 0
+        for e in shapes:
+            mesh = e.find("geometry/mesh")
+            fn = mesh.get("filename") or ""
+            if fn.startswith("package://"):
+                fn = fn[len("package://"):]
+            file = os.path.join(folder, fn)
+            if not fn or not os.path.isfile(file):
+                raise ValueError(f"{file}: missing mesh file of link {name!r}")
+            try:
+                v, fa = meshio.load_mesh(file)
+            except ValueError as err:
+                raise ValueError(f"{file}: the mesh of link {name!r} cannot be read ({err})") from None
+            fa = np.asarray(fa, dtype=np.int64).reshape(-1, 3)
+            if fa.size and (fa.min() < 0 or fa.max() >= len(v)):
+                raise ValueError(f"{file}: a face index of the mesh of link {name!r} lies outside [0, {len(v)})")
+            ms = _floats(mesh.get("scale", "1 1 1"), 3, f"link {name!r} mesh scale")
+            o = e.find("origin")
+            t = _floats(o.get("xyz", "0 0 0"), 3, f"link {name!r} origin xyz") if o is not None else np.zeros(3)
+            rpy = _floats(o.get("rpy", "0 0 0"), 3, f"link {name!r} origin rpy") if o is not None else np.zeros(3)
+            x = np.asarray(v, dtype=np.float64).reshape(-1, 3) * ms
+            verts.append(((x @ _rpy_matrix(rpy).T + t) * scale).astype(np.float32))
+            faces.append(fa + base)
+            base += len(v)
+        nf = sum(len(fa) for fa in faces)
+        out.append((np.concatenate(verts), np.concatenate(faces)) if nf else None)
+    return out
