@@ -553,6 +553,37 @@ int pm_mesh_tsdf_query_f32(const float* fields, const int64_t* part_off, const i
                            int res, float vox_size, float ox, float oy, float oz, float sdf_trunc, const float* base,
                            int base_per_env, float* out, long out_stride, int brick_skip, void* stream);
 
+/* ------------------------------------------------------------------ mesh-TSDF observation of a scene whose environments differ
+ * pm_mesh_tsdf_query_groups_f32: the arguments of the entry above with the part tables read as a GRID LIBRARY of NG rows (fields,
+ * part_off, part_shape, part_bbox_min, part_voxel_size: one row per grid) plus
+ *   grid_slot (NG) int32     the pose slot in [0, M) that row's grid is placed by: its pose in environment b is pose[b, grid_slot[row]]
+ *   NG_shared                rows [0, NG_shared) are sampled by every environment
+ *   group_off (G + 1) int32  rows relative to NG_shared, non-decreasing, group_off[0] = 0, group_off[G] = NG - NG_shared
+ *   env_group (B) int32      g = env_group[b] in [0, G): environment b also owns the rows of group g; g = -1: the shared rows only
+ *   max_group_grids          an upper bound of the rows of a group, max_g (group_off[g + 1] - group_off[g])
+ *   t0, t1                   an ordinal range in place of p0, p1
+ * Definition: environment b owns the ordinals t < NG_shared (row t) and t = NG_shared + i for i < group_off[g + 1] - group_off[g]
+ * (row NG_shared + group_off[g] + i).  Take its own rows, in ordinal order, as the parts of pm_mesh_tsdf_query_f32, each with the
+ * pose of the slot its row names, and p0, p1 = its own ordinals inside [t0, t1): the volume of environment b is exactly that result
+ * -- the same fp32 association, the same validity rule against the row's own shape, the same min with the base, the same division
+ * and clamp -- bit for bit, with brick_skip on and off.  No own ordinal inside [t0, t1): clamp(base / sdf_trunc, -1, 1).
+ * Environment b comes out all-NaN iff a pose of a slot named by one of its OWN rows has a non-finite entry, whatever t0 and t1 are;
+ * slots no own row names are never examined (the NaN poses a scene's row table leaves past a cabinet's body count do nothing).
+ * Launch shape: that of the entry above (one wave per 4^3 brick, four bricks per work-group, grid row = environment); lane l tests
+ * ordinal pb + l; group, row and slot of an iteration are wave-uniform, so table and pose reads stay scalar loads.
+ * Memory safety: g outside [-1, G) counts as -1; group_off is cut to [0, NG - NG_shared], so rows stay in [NG_shared, NG); at most
+ * max_group_grids rows of a group are sampled (a bound that is too small drops the group's last rows); a grid_slot outside [0, M)
+ * makes its row unsampled and no pose is read through it; gathers stay behind the validity test.
+ * PM_EINVAL (before any launch): every condition of the entry above (p0, p1 read as t0, t1), NG <= 0, NG_shared outside [0, NG],
+ * G < 0, max_group_grids < 0, t0 < 0, t0 >= t1, t1 > NG_shared + max_group_grids, a NULL grid_slot, a NULL group_off or env_group
+ * with G > 0.  PM_ABI_VERSION stays 163 with this addition (no existing signature changed). */
+int pm_mesh_tsdf_query_groups_f32(const float* fields, const int64_t* part_off, const int32_t* part_shape, const float* part_bbox_min,
+                                  const float* part_voxel_size, const int32_t* grid_slot, int NG, int NG_shared,
+                                  const int32_t* group_off, int G, const int32_t* env_group, int max_group_grids, const float* pose_R,
+                                  const float* pose_T, int B, int M, int t0, int t1, int res, float vox_size, float ox, float oy,
+                                  float oz, float sdf_trunc, const float* base, int base_per_env, float* out, long out_stride,
+                                  int brick_skip, void* stream);
+
 /* ------------------------------------------------------------------ mesh bake (producer of the mesh-TSDF part grids)
  * utils/mesh2sdf.py:201-237 `TSDFfromMesh.mesh2sdf` without kaolin / ManifoldPlus: the signed-distance grid of one triangle mesh.
  * tri: (F, 3, 3) float32 corner positions (faces with two equal corners already dropped by the caller; a remaining zero-area

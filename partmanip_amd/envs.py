@@ -37,8 +37,11 @@ class _Observer:
 
 def pc_observer(pc, sel=None):
     """mesh2pc.PCfromMesh -> 3 * num_points columns.  sel (K) int32 on the device: the subset of the scene's points, drawn once here
-    from torch's CPU generator where None (the reference draws one per call; a fixed one keeps the step free of host work)."""
-    if sel is None:
+    from torch's CPU generator where None (the reference draws one per call; a fixed one keeps the step free of host work).  A cloud
+    built with groups= gives its own default, pc.group_sel(): (N, K) rows, every environment's from its own cabinet's cloud."""
+    if sel is None and getattr(pc, "groups", False):
+        sel = pc.group_sel()
+    elif sel is None:
         sel = torch.randperm(pc.pts.shape[0])[:pc.num_points].to(torch.int32).to(pc.device)
     obs = _Observer(3 * sel.shape[-1], lambda R, T, out: pc.query_pc(R, T, out=out, sel=sel))
     obs.sel = sel

@@ -12,6 +12,15 @@ and with `out=` writes them straight into the left part of an (N, 3 * num_points
 
 One copy of the canonical points lives on the device (`part_pc (m, p, 3)`, its flat view `pts (m p, 3)`, `part_of (m p)`); the
 reference's per-environment repeat is the property `all_pc`, materialised on demand.
+
+A scene whose environments differ (open_drawer: every environment holds its own cabinet, env % num_objs):
+
+    pc = PCfromMesh(N, device, meshes=robot_parts, groups=load_drawer_meshes(assets), group_of=envs.obj_id)
+
+The point library `pts` is then the shared parts' points followed by `num_points` points of every body of every object; a point of
+body j names slot len(meshes) + j (`part_of`), and an environment's own cloud is the shared rows plus the rows of its object.  The
+kernel is the same one: it already takes a selection per environment, so `group_sel()` only has to draw every environment's rows
+from its own cloud.
 """
 import numpy as np
 import torch
@@ -36,9 +45,17 @@ class PCfromMesh:
     """Constructor of the reference plus keyword extensions in the manner of TSDFfromMesh: `asset_root` (prefix of the reference's
     relative paths assets/franka_description/meshes/visual/* and assets/objs/cube/cube.obj), `meshes` (a list of (vertices, faces)
     used instead of the files), `part_pcs` (a ready (m, p, 3) array used instead of sampling) and `seed` (part i is sampled with
-    torch.Generator().manual_seed(seed + i), so the two fingers, one file loaded twice, get different points as in the reference)."""
+    torch.Generator().manual_seed(seed + i), so the two fingers, one file loaded twice, get different points as in the reference).
+    groups: None, or one list per object with one entry per body: (vertices, faces), a ready (num_points, 3) array, or None for a
+    body without a mesh (tasks.open_drawer.load_drawer_meshes); body j of object k is sampled with
+    torch.Generator().manual_seed(seed + GROUP_SEED_STRIDE * (k + 1) + j).  group_of (num_envs,) ints in [-1, len(groups)): the object
+    each environment holds, -1 for none (default: env % len(groups), the reference's rule).  part_num is then num_shared + the
+    largest body count; attributes: num_shared, pts_shared (the shared rows of pts), group_off (numpy, rows of pts relative to
+    pts_shared), group_of (numpy), max_group_points.  With groups, `meshes` may be empty."""
 
-    def __init__(self, num_envs, device, num_points=1024, asset_root='.', meshes=None, part_pcs=None, seed=0):
+    GROUP_SEED_STRIDE = 4096
+
+    def __init__(self, num_envs, device, num_points=1024, asset_root='.', meshes=None, part_pcs=None, seed=0, groups=None, group_of=None):
         self.num_envs = num_envs
         self.device = device
         self.num_points = int(num_points)
@@ -53,16 +70,120 @@ class PCfromMesh:
         else:
             if meshes is None:
                 meshes = [meshio.load_mesh(path) for path in meshio.scene_mesh_paths(asset_root)]
-            if len(meshes) == 0:
+            if len(meshes) == 0 and not groups:
                 raise ValueError("meshes: at least one part is needed")
-            pcs = np.stack([self.load_pc_from_mesh(v, f, i) for i, (v, f) in enumerate(meshes)])
+            pcs = np.stack([self.load_pc_from_mesh(v, f, i) for i, (v, f) in enumerate(meshes)]) if len(meshes) else \
+                np.zeros((0, self.num_points, 3), dtype=np.float32)
+        if group_of is not None and groups is None:
+            raise ValueError("group_of: needs groups=")
         self.part_num, self.points_per_part = int(pcs.shape[0]), int(pcs.shape[1])
+        self.groups = groups is not None
+        self.last_sel = None
+        if self.groups:
+            self._init_groups(pcs, groups, group_of)
+            return
         self.part_pc = torch.from_numpy(pcs).to(self.device)                                   # (m, p, 3)
         self.pts = self.part_pc.view(-1, 3)                                                    # (m p, 3), the same memory
         self.part_of = torch.arange(self.part_num, dtype=torch.int32).repeat_interleave(self.points_per_part).to(self.device)
-        self.last_sel = None
         self._full = None                                                                      # scratch of select='fps'
         self._fps_ws = None
+
+    def _init_groups(self, pcs, groups, group_of):
+        """The point library of a scene whose environments differ: the shared parts' points, then every object's bodies."""
+        groups = [list(g) for g in groups]
+        if not groups:
+            raise ValueError("groups: at least one object is needed")
+        S = self.num_shared = self.part_num
+        self._full = self._fps_ws = None
+        self.part_pc = torch.from_numpy(pcs).to(self.device)                                   # (S, p, 3): the shared parts only
+        clouds, part, off = [pcs.reshape(-1, 3)], [np.repeat(np.arange(S, dtype=np.int32), self.points_per_part)], [0]
+        for k, bodies in enumerate(groups):
+            for j, body in enumerate(bodies):
+                if body is None:
+                    continue
+                if isinstance(body, (tuple, list)):
+                    pts = self.load_pc_from_mesh(body[0], body[1], self.GROUP_SEED_STRIDE * (k + 1) + j)
+                else:
+                    pts = np.ascontiguousarray(body.cpu().numpy() if torch.is_tensor(body) else body, dtype=np.float32)
+                    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
+                        raise ValueError(f"groups[{k}][{j}]: expected (vertices, faces), a (p, 3) array of points or None, got {pts.shape}")
+                clouds.append(pts)
+                part.append(np.full(len(pts), S + j, dtype=np.int32))
+            off.append(sum(len(c) for c in clouds[1:]))
+        self.part_num = S + max(len(bodies) for bodies in groups)
+        self.pts_shared = S * self.points_per_part
+        self.group_off = np.asarray(off, dtype=np.int64)
+        self.max_group_points = int(np.diff(self.group_off).max())
+        if self.pts_shared + self.max_group_points == 0:
+            raise ValueError("meshes and groups: no mesh at all")
+        G = len(groups)
+        self.group_of = self._host_group_of(np.arange(int(self.num_envs)) % G if group_of is None else group_of, int(self.num_envs))
+        self._group_of = torch.from_numpy(self.group_of).to(self.device)
+        self.pts = torch.from_numpy(np.ascontiguousarray(np.concatenate(clouds), dtype=np.float32)).to(self.device)   # (Q, 3)
+        self.part_of = torch.from_numpy(np.concatenate(part)).to(self.device)                  # (Q,) int32: the slot
+        self._all_table = None
+
+    def _host_group_of(self, group_of, b):
+        g = np.asarray(group_of.cpu().numpy() if torch.is_tensor(group_of) else group_of)
+        G = len(self.group_off) - 1
+        if g.shape != (b,) or g.dtype.kind not in "iu" or g.min() < -1 or g.max() >= G:
+            raise ValueError(f"group_of: expected {b} integers in [-1, {G}), got {g.dtype} {g.shape}")
+        return np.ascontiguousarray(g, dtype=np.int32)
+
+    def _env_groups(self, b, group_of):
+        """(host ints or None, device int64 (b,)) of a call over b environments: the constructor's table, or the call's own group_of
+        (b ints on the host, or an integer tensor on the device, which is not read here)."""
+        if group_of is None:
+            if b != self.num_envs:
+                raise ValueError(f"poses: expected {self.num_envs} environments (the group table's), got {b}; pass group_of= for a slice")
+            return self.group_of, self._group_of.long()
+        if torch.is_tensor(group_of) and group_of.is_cuda:
+            if tuple(group_of.shape) != (b,):
+                raise ValueError(f"group_of: expected ({b},), got {tuple(group_of.shape)}")
+            g = group_of.long()                                                                # an id outside [-1, G) counts as -1, as in the kernels
+            return None, torch.where((g >= 0) & (g < len(self.group_off) - 1), g, torch.full_like(g, -1))
+        host = self._host_group_of(group_of, b)
+        return host, torch.from_numpy(host).to(self.device).long()
+
+    def own_rows(self, g):
+        """The rows of `pts` that make the cloud of an environment holding object g (-1: none): the shared rows, then the object's."""
+        rows = np.arange(self.pts_shared)
+        if g >= 0:
+            rows = np.concatenate([rows, self.pts_shared + np.arange(self.group_off[g], self.group_off[g + 1])])
+        return rows
+
+    def group_sel(self, generator=None, group_of=None):
+        """(b, K) int32 rows of `pts` on the device, K = num_points: for every object in turn, and then once for 'no object' (-1), the
+        first K entries of torch.randperm over that cloud (own_rows) drawn from `generator` (None: the CPU global generator), then
+        row group_of[e] of that table for every environment e, gathered on the device.  An environment's points so come from the
+        shared parts and its own object only; environments holding the same object share their selection, as the reference's
+        environments all do.  The 'no object' row is drawn only when the shared cloud has K points; it is -1 (NaN points)
+        otherwise, and asking for it from the host is an error."""
+        if not self.groups:
+            raise ValueError("group_sel: this cloud was built without groups=")
+        host, dev = self._env_groups(self.num_envs if group_of is None else len(group_of), group_of)
+        K, G = self.num_points, len(self.group_off) - 1
+        table = np.full((G + 1, K), -1, dtype=np.int32)
+        for g in list(range(G)) + [-1]:
+            rows = self.own_rows(g)
+            if len(rows) < K:
+                if g >= 0 or (host is not None and (host < 0).any()):
+                    raise ValueError(f"num_points {K} exceeds the {len(rows)} points of the cloud of " +
+                                     (f"object {g}" if g >= 0 else "an environment without an object"))
+                continue
+            table[g] = rows[torch.randperm(len(rows), generator=generator)[:K].numpy()]
+        return torch.from_numpy(table).to(self.device)[dev]                                    # index -1 is the last row
+
+    def _all_sel(self, dev):
+        """(b, pts_shared + max_group_points) int32: every row of every environment's own cloud, -1 (a NaN point) past its count."""
+        if self._all_table is None:
+            G = len(self.group_off) - 1
+            table = np.full((G + 1, self.pts_shared + self.max_group_points), -1, dtype=np.int32)
+            for g in list(range(G)) + [-1]:
+                rows = self.own_rows(g)
+                table[g, :len(rows)] = rows
+            self._all_table = torch.from_numpy(table).to(self.device)
+        return self._all_table[dev]
 
     def load_pc_from_mesh(self, vertices, faces, index=0):
         """`num_points` surface points of one part (mesh2pc.py:32-41) as float32 (p, 3), seeded with seed + index."""
@@ -75,16 +196,23 @@ class PCfromMesh:
         (600 MB at 4096 environments); nothing here reads it."""
         return self.part_pc.unsqueeze(0).repeat(self.num_envs, 1, 1, 1).reshape(-1, self.points_per_part, 3)
 
-    def query_pc(self, pose_R, pose_T, out=None, sel=None, select='random'):
+    def query_pc(self, pose_R, pose_T, out=None, sel=None, select='random', group_of=None):
         """pose_R [b, m, 3, 3], pose_T [b, m, 3] (any b) -> [b, K, 3].
         select='random' (the reference): the first num_points entries of torch.randperm(m p) from the CPU global generator, one
         subset for all environments (mesh2pc.py:63-64).  select='all': every point, K = m p.  select='fps': the posed cloud of all
         points is thinned to num_points per environment by farthest-point sampling (ops.fps, start index 0), so large parts are
         covered as densely as small ones.  sel: an int32 device tensor (K,) or (b, K) used instead (no host generator, no copy).
         out: None, or a 2-D float32 view (b, >= 3K) with unit inner stride (e.g. obs[:, :3K] of an observation buffer); the result
-        is then a view of its first 3K columns.  `last_sel` holds the selection that was used (None for 'all')."""
+        is then a view of its first 3K columns.  `last_sel` holds the selection that was used (None for 'all').
+        With groups=: 'random' draws group_sel() per call; 'all' gives K = pts_shared + max_group_points with NaN rows past an
+        environment's own points; 'fps' is refused; sel keeps its meaning (rows of pts).  b = num_envs, or group_of= (b,) names the
+        object of each row of this call."""
         Q = self.pts.shape[0]
         b, _ = ops.check_poses(pose_R, pose_T, self.part_num)
+        if self.groups:
+            return self._query_pc_groups(pose_R, pose_T, b, out, sel, select, group_of)
+        if group_of is not None:
+            raise ValueError("group_of: this cloud was built without groups=")
         if sel is not None:
             if sel.dtype != torch.int32 or sel.dim() not in (1, 2) or (sel.dim() == 2 and sel.shape[0] != b) or sel.shape[-1] == 0:
                 raise ValueError(f"sel: expected an int32 tensor (K,) or ({b}, K), got {sel.dtype} {tuple(sel.shape)}")
@@ -108,6 +236,29 @@ class PCfromMesh:
                 self._fps_ws = ops.Workspace(pose_R.device)
             ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, None, self._full)
             sel = ops.fps(self._full.view(b, Q, 3), self.num_points, self._fps_ws)
+        res = ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, sel, out)
+        self.last_sel = sel
+        return res[:, :3 * K].unflatten(1, (K, 3))
+
+    def _query_pc_groups(self, pose_R, pose_T, b, out, sel, select, group_of):
+        if sel is not None:
+            if sel.dtype != torch.int32 or sel.dim() not in (1, 2) or (sel.dim() == 2 and sel.shape[0] != b) or sel.shape[-1] == 0:
+                raise ValueError(f"sel: expected an int32 tensor (K,) or ({b}, K), got {sel.dtype} {tuple(sel.shape)}")
+            K = sel.shape[-1]
+        elif select not in SELECT_MODES:
+            raise ValueError(f"select: expected one of {SELECT_MODES}, got {select!r}")
+        elif select == 'fps':
+            raise ValueError("select='fps': not available with groups= (the farthest-point kernel thins one cloud of a common size; "
+                             "the environments' own clouds differ in size)")
+        else:
+            K = self.pts_shared + self.max_group_points if select == 'all' else self.num_points
+        if out is not None:
+            ops._out_rows(out, b, 3 * K)                                                       # a bad view is reported before the device and any launch
+        env = None if sel is not None else self._env_groups(b, group_of)                       # ... and so is a slice without its group_of
+        ops._req(pose_R, pose_T, sel, out, self.pts)
+        pose_R, pose_T = pose_R.contiguous(), pose_T.contiguous()
+        if sel is None:
+            sel = self.group_sel(group_of=group_of) if select == 'random' else self._all_sel(env[1])
         res = ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, sel, out)
         self.last_sel = sel
         return res[:, :3 * K].unflatten(1, (K, 3))

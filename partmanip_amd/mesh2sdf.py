@@ -23,7 +23,18 @@ the reference's fp32 expressions (`bake_grid_layout`); the magnitude is the exac
 generalised winding number (|w| >= 0.5 is inside), which equals kaolin's ray parity on a closed mesh and needs no manifold
 pre-pass on an open one.  Without `bake=True` an absent grid raises as before.  Marching cubes, ManifoldPlus itself
 and the debug dumps stay outside this build's scope: they raise NotImplementedError.
+
+A scene whose environments differ (open_drawer: every environment holds its own cabinet, env % num_objs):
+
+    groups = bake_groups(device, load_drawer_meshes(assets), trunc, voxel_size)
+    tsdf = TSDFfromMesh(N, size, res, device, sdf_dicts=robot_grids, groups=groups, group_of=envs.obj_id)
+
+The shared grids keep slots 0 .. S - 1; groups[k][j] is the grid dict of body j of object k, or None, and is placed by slot S + j in
+whatever environment holds object k.  query_tsdf then takes (N, part_num, ...) poses with part_num = S + the largest body count --
+the table make_open_drawer_env(scene_meshes=) hands its observers -- and is one launch of pm_mesh_tsdf_query_groups_f32: an
+environment samples its own cabinet's grids only, and the NaN poses past its body count are never looked at.
 """
+import hashlib
 import os
 
 import numpy as np
@@ -61,6 +72,60 @@ def bake_mesh(device, trunc, voxel_size, mesh_path=None, vertices=None, faces=No
     return {'sdf': sdf.cpu().numpy(), 'bbox_min': bbox_min.numpy(), 'voxel_size': voxel_size}
 
 
+def _fitting_voxel_size(vertices, trunc, voxel_size):
+    """The smallest voxel size, found by growing `voxel_size` in steps of 1 %, whose bake grid has fewer than 2^31 cells."""
+    vs = float(voxel_size)
+    while int(np.prod(np.asarray(bake_grid_layout(vertices, trunc, vs)[0], dtype=np.float64))) >= 2 ** 31:
+        vs *= 1.01
+    return vs
+
+
+def bake_groups(device, meshes, trunc, voxel_size, cache_dir=None):
+    """tasks.open_drawer.load_drawer_meshes(assets) -- one list per object of (vertices, faces)-or-None per body -- baked into the
+    `groups` of TSDFfromMesh: one grid dict per body (bake_mesh), None where the body has no mesh.  cache_dir: None, or a folder
+    where every baked dict is kept as <digest>.npy (np.save of the dict, as load_sdf keeps the robot's), the digest being the SHA-256
+    of the mesh's float32 vertices, int64 faces, trunc and voxel_size; a file that is there is loaded instead of baking.
+    A body whose grid would hold 2^31 cells or more is refused with the voxel size that would fit, before anything is baked."""
+    meshes = [list(bodies) for bodies in meshes]
+    for k, bodies in enumerate(meshes):
+        for j, mesh in enumerate(bodies):
+            if mesh is None:
+                continue
+            v = np.ascontiguousarray(mesh[0], dtype=np.float32).reshape(-1, 3)
+            shape = bake_grid_layout(v, trunc, voxel_size)[0]
+            if int(np.prod(np.asarray(shape, dtype=np.float64))) >= 2 ** 31:
+                raise ValueError(f"groups[{k}][{j}]: the grid of body {j} of object {k} would be {shape} = {np.prod(np.asarray(shape, dtype=np.float64)):.3g} "
+                                 f"cells at voxel_size {voxel_size} (the limit is 2^31); a voxel_size of "
+                                 f"{_fitting_voxel_size(v, trunc, voxel_size):.4g} or more fits")
+    if cache_dir is not None:
+        os.makedirs(cache_dir, exist_ok=True)
+    groups = []
+    for bodies in meshes:
+        out = []
+        for mesh in bodies:
+            if mesh is None:
+                out.append(None)
+                continue
+            v = np.ascontiguousarray(mesh[0], dtype=np.float32).reshape(-1, 3)
+            f = np.ascontiguousarray(mesh[1], dtype=np.int64).reshape(-1, 3)
+            path = None
+            if cache_dir is not None:
+                h = hashlib.sha256()
+                for piece in (np.asarray(v.shape, dtype=np.int64), v, np.asarray(f.shape, dtype=np.int64), f,
+                              np.asarray([trunc, voxel_size], dtype=np.float64)):
+                    h.update(piece.tobytes())
+                path = os.path.join(cache_dir, h.hexdigest() + ".npy")
+            if path is not None and os.path.exists(path):
+                out.append(np.load(path, allow_pickle=True).item())
+                continue
+            d = bake_mesh(device, trunc, voxel_size, vertices=v, faces=f)
+            if path is not None:
+                np.save(path, d)
+            out.append(d)
+        groups.append(out)
+    return groups
+
+
 class TSDFfromMesh:
     """Constructor of the reference plus three keyword extensions: `bake` (bake absent grids from their meshes on the GPU, module
     docstring; default False = an absent grid is an error), `sdf_dicts` (a list of {'sdf': (X,Y,Z) float32, 'bbox_min':
@@ -68,10 +133,13 @@ class TSDFfromMesh:
     paths assets/franka_description/sdf/visual/*.npy and assets/objs/cube/sdf.npy).  `vox_origin` may be None, a tensor or the
     yaml's list (the reference raises TypeError on a list, tasks/hand_base.py passes one).
     `parallel=False` is served by the same kernel: the reference's own naive path (query_tsdf_naive ->
-    triplet_interpolation_query) indexes a 3-D field with a flat index and cannot run; the parallel path is the specification."""
+    triplet_interpolation_query) indexes a 3-D field with a flat index and cannot run; the parallel path is the specification.
+    groups: None, or one list per object of grid dict-or-None per body (bake_groups); group_of (num_envs,) ints in [-1, len(groups)):
+    the object each environment holds, -1 for none (default: env % len(groups), the reference's rule).  part_num is then num_shared
+    + the largest body count; attributes: num_shared, grid_slot, group_off (numpy), group_of (numpy), max_group_grids."""
 
     def __init__(self, num_envs, size, resolution, device, parallel=True, debug=False, vox_origin=None, sdf_dicts=None,
-                 asset_root='.', bake=False):
+                 asset_root='.', bake=False, groups=None, group_of=None):
         if debug:
             raise NotImplementedError("debug dumps (surface points / marching cubes) are outside this build's scope (DESIGN.md)")
         self.num_envs = num_envs
@@ -112,7 +180,38 @@ class TSDFfromMesh:
         else:
             self.load_franka(os.path.join(asset_root, "assets", "franka_description"))
             self.load_sdf(os.path.join(asset_root, OBJ_SDF_PATH), os.path.join(asset_root, meshio.OBJ_MESH_PATH))
+        if group_of is not None and groups is None:
+            raise ValueError("group_of: needs groups=")
+        self.groups = groups is not None
+        self._group_dicts = []
+        if self.groups:
+            groups = [list(g) for g in groups]
+            if not groups:
+                raise ValueError("groups: at least one object is needed")
+            S = len(self.sdf_dict_list)
+            slot, off = list(range(S)), [0]
+            for k, bodies in enumerate(groups):
+                for j, d in enumerate(bodies):
+                    if d is None:
+                        continue
+                    if not isinstance(d, dict) or not {'sdf', 'bbox_min', 'voxel_size'} <= set(d):
+                        raise ValueError(f"groups[{k}][{j}]: expected a dict with 'sdf', 'bbox_min' and 'voxel_size', or None")
+                    self._group_dicts.append(d)
+                    slot.append(S + j)
+                off.append(len(self._group_dicts))
+            if not slot:
+                raise ValueError("sdf_dicts and groups: no grid at all")
+            self.grid_slot = np.asarray(slot, dtype=np.int32)
+            self.group_off = np.asarray(off, dtype=np.int32)
+            self.max_group_grids = int(np.diff(self.group_off).max())
+            self.group_of = self._host_group_of(np.arange(int(num_envs)) % len(groups) if group_of is None else group_of, int(num_envs))
         self.merge_sdf_field()
+        if self.groups:
+            self.num_shared = len(self.sdf_dict_list)
+            self.part_num = self.num_shared + max(len(bodies) for bodies in groups)
+            self._grid_slot = torch.from_numpy(self.grid_slot).to(self.device)
+            self._group_off = torch.from_numpy(self.group_off).to(self.device)
+            self._group_of = torch.from_numpy(self.group_of).to(self.device)
 
     # ------------------------------------------------------------------------------------------------ loading
     def load_franka(self, hand_base_path):
@@ -161,8 +260,9 @@ class TSDFfromMesh:
     def merge_sdf_field(self):
         """One flat buffer of the concatenated (un-padded) grids + per-part tables, on `device`:
         sdf_field (sum X*Y*Z), sdf_field_off (m) int64, sdf_field_res (m, 3) int32, sdf_bbox_min (m, 3), sdf_voxel_size (m)."""
-        self.part_num = len(self.sdf_dict_list)
-        grids = [np.ascontiguousarray(d['sdf'], dtype=np.float32) for d in self.sdf_dict_list]
+        dicts = self.sdf_dict_list + self._group_dicts       # the shared grids, then every object's (the rows of the grid library)
+        self.part_num = len(dicts)
+        grids = [np.ascontiguousarray(d['sdf'], dtype=np.float32) for d in dicts]
         for g in grids:
             if g.ndim != 3 or g.size >= 2 ** 31:
                 raise ValueError(f"a part's 'sdf' must be a 3-D grid of fewer than 2^31 cells, got shape {g.shape}")
@@ -171,9 +271,9 @@ class TSDFfromMesh:
         self.sdf_field = torch.from_numpy(np.concatenate([g.reshape(-1) for g in grids])).to(self.device)
         self.sdf_field_off = torch.from_numpy(off).to(self.device)
         self.sdf_field_res = torch.tensor([list(g.shape) for g in grids], dtype=torch.int32).to(self.device)
-        self.sdf_bbox_min = torch.tensor(np.stack([np.asarray(d['bbox_min'], dtype=np.float32).reshape(3) for d in self.sdf_dict_list]),
+        self.sdf_bbox_min = torch.tensor(np.stack([np.asarray(d['bbox_min'], dtype=np.float32).reshape(3) for d in dicts]),
                                          dtype=torch.float32).to(self.device)
-        self.sdf_voxel_size = torch.tensor([float(d['voxel_size']) for d in self.sdf_dict_list], dtype=torch.float32).to(self.device)
+        self.sdf_voxel_size = torch.tensor([float(d['voxel_size']) for d in dicts], dtype=torch.float32).to(self.device)
 
     # ------------------------------------------------------------------------------------------------ queries
     def initialize_sdf(self, nerf_pred_tsdf):
@@ -181,30 +281,73 @@ class TSDFfromMesh:
         self.init_tsdf = torch.as_tensor(nerf_pred_tsdf, dtype=torch.float32).to(self.device) * self.sdf_trunc
         self._init_base = self.init_tsdf.reshape(self.num_envs, self.point_num).contiguous()
 
-    def _query(self, pose_R, pose_T, p0, p1, base, out, brick_skip=True):
+    def _host_group_of(self, group_of, b):
+        g = np.asarray(group_of.cpu().numpy() if torch.is_tensor(group_of) else group_of)
+        G = len(self.group_off) - 1
+        if g.shape != (b,) or g.dtype.kind not in "iu" or g.min() < -1 or g.max() >= G:
+            raise ValueError(f"group_of: expected {b} integers in [-1, {G}), got {g.dtype} {g.shape}")
+        return np.ascontiguousarray(g, dtype=np.int32)
+
+    def _env_groups(self, b, group_of):
+        """The env_group table of a call over b environments: the constructor's, or the call's own group_of (b ints on the host, or
+        an int32 tensor on the device, which is not read here).  None without groups."""
+        if not self.groups:
+            if group_of is not None:
+                raise ValueError("group_of: this object was built without groups=")
+            return None
+        if group_of is None:
+            if b != self.num_envs:
+                raise ValueError(f"poses: expected {self.num_envs} environments (the group table's), got {b}; pass group_of= for a slice")
+            return self._group_of
+        if torch.is_tensor(group_of) and group_of.is_cuda:
+            return group_of
+        return torch.from_numpy(self._host_group_of(group_of, b)).to(self.device)
+
+    def _query(self, pose_R, pose_T, p0, p1, base, out, brick_skip=True, group_of=None):
+        """Parts [p0, p1) against `base`; with groups, the ordinals [p0, p1) of every environment's own rows."""
+        eg = self._env_groups(ops.check_poses(pose_R, pose_T, self.part_num)[0] if self.groups else 0, group_of)
         pose_R = pose_R.to(torch.float32).reshape(-1, self.part_num, 3, 3).contiguous()
         pose_T = pose_T.to(torch.float32).reshape(-1, self.part_num, 3).contiguous()
         n = self.point_num
         if base.dim() == 2 and base.shape[0] != pose_R.shape[0]:
             raise ValueError(f"initialize_sdf was given {base.shape[0]} environments, the poses have {pose_R.shape[0]}")
-        res = ops.mesh_tsdf_query(self.sdf_field, self.sdf_field_off, self.sdf_field_res, self.sdf_bbox_min, self.sdf_voxel_size,
-                                  pose_R, pose_T, self.resolution, self.vox_size, self._origin3, self.sdf_trunc, base,
-                                  p0, p1, out, brick_skip)
+        if eg is not None:
+            res = ops.mesh_tsdf_query_groups(self.sdf_field, self.sdf_field_off, self.sdf_field_res, self.sdf_bbox_min,
+                                             self.sdf_voxel_size, self._grid_slot, self.num_shared, self._group_off, eg, pose_R, pose_T,
+                                             self.resolution, self.vox_size, self._origin3, self.sdf_trunc, base, p0, p1, out, brick_skip,
+                                             max_group_grids=self.max_group_grids)
+        else:
+            res = ops.mesh_tsdf_query(self.sdf_field, self.sdf_field_off, self.sdf_field_res, self.sdf_bbox_min, self.sdf_voxel_size,
+                                      pose_R, pose_T, self.resolution, self.vox_size, self._origin3, self.sdf_trunc, base,
+                                      p0, p1, out, brick_skip)
         r = self.resolution
         return res[:, :n].unflatten(1, (r, r, r))
 
-    def query_tsdf(self, pose_R, pose_T, out=None, brick_skip=True):
+    def query_tsdf(self, pose_R, pose_T, out=None, brick_skip=True, group_of=None):
         """pose_R [b, m, 3, 3], pose_T [b, m, 3] -> [b, res, res, res].  out: None, or a 2-D float32 view (b, >= res^3) with
         unit inner stride (e.g. obs[:, :res^3] of an observation buffer); the result is then a view of its first res^3 columns.
-        brick_skip=False turns the brick-level part rejection off (same bits, slower; for tests)."""
-        return self._query(pose_R, pose_T, 0, self.part_num, self._init_base, out, brick_skip)
+        brick_skip=False turns the brick-level part rejection off (same bits, slower; for tests).  With groups=: one launch of the
+        grouped entry; b = num_envs, or group_of= (b,) names the object of each row of this call."""
+        if self.groups:
+            return self._query(pose_R, pose_T, 0, self.num_shared + self.max_group_grids, self._init_base, out, brick_skip, group_of)
+        return self._query(pose_R, pose_T, 0, self.part_num, self._init_base, out, brick_skip, group_of)
 
     query_tsdf_parallel = query_tsdf
     query_tsdf_naive = query_tsdf          # the reference's naive path cannot run (class docstring); same kernel
 
-    def query_tsdf_seperately(self, pose_R, pose_T, out_scene=None, out_obj=None):
+    def query_tsdf_seperately(self, pose_R, pose_T, out_scene=None, out_obj=None, group_of=None):
         """(scene, obj): the parts before the last against the base field, and the last part (the object) alone against the
-        ground plane (mesh2sdf.py:95-117); min(scene, obj) == query_tsdf bit for bit.  Two launches over part ranges."""
+        ground plane (mesh2sdf.py:95-117); min(scene, obj) == query_tsdf bit for bit.  Two launches over part ranges.
+        With groups=: (the shared rows against the base field, the environment's own rows against the ground plane).  The equality
+        holds while the base field is the ground plane, as in the reference (after initialize_sdf the object's volume still carries
+        the ground)."""
+        if self.groups:
+            S, most = self.num_shared, self.max_group_grids
+            if S == 0 or most == 0:
+                raise ValueError("query_tsdf_seperately: needs at least one shared grid and one grid in a group")
+            scene = self._query(pose_R, pose_T, 0, S, self._init_base, out_scene, group_of=group_of)
+            obj = self._query(pose_R, pose_T, S, S + most, self._ground, out_obj, group_of=group_of)
+            return scene, obj
         scene = self._query(pose_R, pose_T, 0, self.part_num - 1, self._init_base, out_scene)
         obj = self._query(pose_R, pose_T, self.part_num - 1, self.part_num, self._ground, out_obj)
         return scene, obj

@@ -1409,6 +1409,60 @@ def mesh_tsdf_query(fields, part_off, part_shape, part_bbox_min, part_voxel_size
     return out
 
 
+def mesh_tsdf_query_groups(fields, part_off, part_shape, part_bbox_min, part_voxel_size, grid_slot, NG_shared, group_off, env_group,
+                           pose_R, pose_T, res, vox_size, origin, sdf_trunc, base, t0=0, t1=None, out=None, brick_skip=True,
+                           max_group_grids=None):
+    """mesh_tsdf_query over a scene whose environments differ (pm_mesh_tsdf_query_groups_f32): the part tables are a library of NG
+    grids; environment b samples rows [0, NG_shared) and the rows of group env_group[b] (-1: none), group g being rows NG_shared +
+    [group_off[g], group_off[g + 1]); row r is placed by pose slot grid_slot[r] of pose_R (B, M, 3, 3), pose_T (B, M, 3).  [t0, t1):
+    the ordinals of an environment's own rows that are sampled (default: all, t1 = NG_shared + max_group_grids).  grid_slot: (NG) host
+    integers (checked against [0, M) and copied) or an int32 device tensor (type and length only; the kernel leaves a row with a
+    slot outside [0, M) unsampled).  group_off / env_group / max_group_grids as face_groups takes them; everything else, and the
+    result, as mesh_tsdf_query."""
+    for t_, name in ((fields, "fields"), (part_bbox_min, "part_bbox_min"), (part_voxel_size, "part_voxel_size"),
+                     (pose_R, "pose_R"), (pose_T, "pose_T"), (base, "base")):
+        _f32c(t_, name)
+    if part_off.dtype != torch.int64 or not part_off.is_contiguous() or part_off.numel() == 0:
+        raise ValueError("part_off: expected a contiguous int64 tensor of at least one row")
+    _i32c(part_shape, "part_shape")
+    NG = part_off.numel()
+    B, M = check_poses(pose_R, pose_T)
+    if tuple(part_shape.shape) != (NG, 3) or tuple(part_bbox_min.shape) != (NG, 3) or part_voxel_size.numel() != NG:
+        raise ValueError("grid tables: expected part_shape (NG,3), part_bbox_min (NG,3), part_voxel_size (NG)")
+    if torch.is_tensor(grid_slot) and grid_slot.is_cuda:
+        _i32c(grid_slot, "grid_slot")
+        if tuple(grid_slot.shape) != (NG,):
+            raise ValueError(f"grid_slot: expected ({NG},), got {tuple(grid_slot.shape)}")
+    else:
+        gs = np.asarray(grid_slot.numpy() if torch.is_tensor(grid_slot) else grid_slot)
+        if gs.dtype.kind not in "iu" or gs.shape != (NG,) or gs.min() < 0 or gs.max() >= M:
+            raise ValueError(f"grid_slot: expected {NG} integers in [0, {M}), got {gs.dtype} {gs.shape}")
+        grid_slot = torch.from_numpy(np.ascontiguousarray(gs, dtype=np.int32)).to(pose_R.device)
+    group_off, env_group, G, most = face_groups(group_off, env_group, NG, NG_shared, B, pose_R.device, max_group_grids,
+                                                names=("NG", "NG_shared", "max_group_grids"))
+    _one_device("mesh_tsdf_query_groups", fields, part_off, part_shape, part_bbox_min, part_voxel_size, grid_slot, group_off, env_group,
+                pose_R, pose_T, base, out)
+    t0, t1 = int(t0), int(NG_shared) + most if t1 is None else int(t1)
+    if not 0 <= t0 < t1 <= int(NG_shared) + most:
+        raise ValueError(f"t0, t1: expected 0 <= t0 < t1 <= NG_shared + max_group_grids = {int(NG_shared) + most}, got {t0}, {t1}")
+    n = int(res) ** 3
+    if tuple(base.shape) == (n,):
+        per_env = 0
+    elif tuple(base.shape) == (B, n):
+        per_env = 1
+    else:
+        raise ValueError(f"base: expected ({n},) or ({B}, {n}), got {tuple(base.shape)}")
+    out, ldo = _out_rows(out, B, n, pose_R.device)
+    ox, oy, oz = (float(v) for v in origin)
+    with TIMER.bracket("mesh_tsdf_query_groups"):
+        check(lib.pm_mesh_tsdf_query_groups_f32(_ptr(fields), _ptr(part_off), _ptr(part_shape), _ptr(part_bbox_min),
+                                                _ptr(part_voxel_size), _ptr(grid_slot), NG, int(NG_shared), _ptr(group_off), G,
+                                                _ptr(env_group), most, _ptr(pose_R), _ptr(pose_T), B, M, t0, t1, int(res),
+                                                float(vox_size), ox, oy, oz, float(sdf_trunc), _ptr(base), per_env, _ptr(out), ldo,
+                                                1 if brick_skip else 0, _stream()), "pm_mesh_tsdf_query_groups_f32")
+    return out
+
+
 def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None):
     """The posed mesh point cloud (pm_mesh_pc_query_f32): pts (Q, 3) canonical surface points, part_of (Q) int32, pose_R (B, M, 3, 3),
     pose_T (B, M, 3); sel: None (every point, K = Q), (K) int32 shared by all environments or (B, K) int32 with unit inner stride.
@@ -1480,26 +1534,28 @@ def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy,
     return out
 
 
-def face_groups(group_off, env_group, F, F_shared, B, device, max_group_faces=None):
+def face_groups(group_off, env_group, F, F_shared, B, device, max_group_faces=None, names=("F", "F_shared", "max_group_faces")):
     """The group arguments of mesh_depth_render_groups / mesh_frame_render_groups -> (group_off (G + 1) int32 on `device`, env_group
     (B) int32 on `device`, G, max_group_faces).  Host arrays (numpy, lists, CPU tensors) are validated here -- group_off starts at 0,
     never decreases and ends at F - F_shared; env_group holds B values in [-1, G) -- and copied to the device, and max_group_faces
     is computed from them.  Device tensors are only checked for type and length (reading them would synchronise; the kernel clamps
-    whatever they hold) and need max_group_faces from the caller."""
+    whatever they hold) and need max_group_faces from the caller.  names: what the messages call F, F_shared and max_group_faces
+    (mesh_tsdf_query_groups partitions the rows of a grid library the same way)."""
+    nF, nS, nM = names
     F, F_shared, B = int(F), int(F_shared), int(B)
     if not 0 <= F_shared <= F:
-        raise ValueError(f"F_shared: expected a value in [0, {F}], got {F_shared}")
+        raise ValueError(f"{nS}: expected a value in [0, {F}], got {F_shared}")
     on_device = [torch.is_tensor(a) and a.is_cuda for a in (group_off, env_group)]
     if on_device[0] != on_device[1]:
         raise ValueError("group_off and env_group: expected both on the host or both on the device")
     if on_device[0]:
         if max_group_faces is None:
-            raise ValueError("max_group_faces: needed with device tables (the host arrays give it for free)")
+            raise ValueError(f"{nM}: needed with device tables (the host arrays give it for free)")
         _i32c(group_off, "group_off"), _i32c(env_group, "env_group")
         if group_off.dim() != 1 or group_off.numel() < 1 or tuple(env_group.shape) != (B,):
             raise ValueError(f"group_off / env_group: expected (G + 1,) and ({B},), got {tuple(group_off.shape)} and {tuple(env_group.shape)}")
         if int(max_group_faces) < 0:
-            raise ValueError(f"max_group_faces: expected a non-negative count, got {max_group_faces}")
+            raise ValueError(f"{nM}: expected a non-negative count, got {max_group_faces}")
         return group_off, env_group, group_off.numel() - 1, int(max_group_faces)
     off, eg = (np.asarray(a.numpy() if torch.is_tensor(a) else a) for a in (group_off, env_group))
     if off.dtype.kind not in "iu" or eg.dtype.kind not in "iu" or off.ndim != 1 or off.size < 1 or eg.shape != (B,):
@@ -1507,12 +1563,12 @@ def face_groups(group_off, env_group, F, F_shared, B, device, max_group_faces=No
     off, eg = off.astype(np.int64), eg.astype(np.int64)
     G = off.size - 1
     if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != F - F_shared:
-        raise ValueError(f"group_off: expected a non-decreasing table from 0 to F - F_shared = {F - F_shared}, got {off.tolist()}")
+        raise ValueError(f"group_off: expected a non-decreasing table from 0 to {nF} - {nS} = {F - F_shared}, got {off.tolist()}")
     if eg.min() < -1 or eg.max() >= G:
         raise ValueError(f"env_group: values must lie in [-1, {G}), got [{eg.min()}, {eg.max()}]")
     most = int(np.diff(off).max()) if G else 0
     if max_group_faces is not None and int(max_group_faces) < most:
-        raise ValueError(f"max_group_faces: {max_group_faces} is below the largest group's {most} rows")
+        raise ValueError(f"{nM}: {max_group_faces} is below the largest group's {most} rows")
     i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)       # noqa: E731
     return i32(off), i32(eg), G, most if max_group_faces is None else int(max_group_faces)
 
