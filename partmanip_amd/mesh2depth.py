@@ -37,7 +37,7 @@ import collections
 import numpy as np
 import torch
 
-from . import meshio, ops
+from . import meshio, ops, scene_groups
 
 # The default colours of the parts, cycled: twelve well-separated hues at moderate saturation (0..255).
 PALETTE = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240), (240, 50, 230),
@@ -88,7 +88,7 @@ class DepthFromMesh:
             raise ValueError("group_of: needs groups=")
         verts, part, faces, base = [], [], [], 0
 
-        def add(mesh, slot, what):
+        def add(mesh, slot, what, k=None, j=None):
             nonlocal base
             v, f = np.asarray(mesh[0], dtype=np.float32), np.asarray(mesh[1], dtype=np.int64)
             if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or len(v) == 0 or len(f) == 0:
@@ -106,22 +106,13 @@ class DepthFromMesh:
         self.num_shared = self.part_num = len(meshes)
         self.face_shared = sum(len(f) for f in faces)
         self.groups = groups is not None
+        self._scene = None
         if self.groups:
-            groups = [list(g) for g in groups]
-            if not groups:
-                raise ValueError("groups: at least one object is needed")
-            off = [0]
-            for k, bodies in enumerate(groups):
-                off.append(off[-1] + sum(add(mesh, self.num_shared + j, f"groups[{k}][{j}]") for j, mesh in enumerate(bodies)
-                                         if mesh is not None))
-            self.part_num += max(len(bodies) for bodies in groups)
-            self.group_off = np.asarray(off, dtype=np.int32)
-            self.max_group_faces = int(np.diff(self.group_off).max())
+            sg = self._scene = scene_groups.SceneGroups(num_envs, self.device, self.num_shared, groups, add, group_of)
+            self.part_num, self.group_off, self.group_of, self.max_group_faces = sg.part_num, sg.group_off, sg.group_of, sg.most
+            self._group_of = sg.group_of_dev
             if not verts:
                 raise ValueError("meshes and groups: no mesh at all")
-            self.group_of = self._host_group_of(np.arange(int(num_envs)) % len(groups) if group_of is None else group_of, int(num_envs))
-            self._group_off = torch.from_numpy(self.group_off).to(self.device)
-            self._group_of = torch.from_numpy(self.group_of).to(self.device)
         self.verts = torch.from_numpy(np.ascontiguousarray(np.concatenate(verts))).to(self.device)               # (NV, 3)
         self.vert_part = torch.from_numpy(np.concatenate(part)).to(self.device)                                  # (NV,) int32
         self.faces = torch.from_numpy(np.ascontiguousarray(np.concatenate(faces).astype(np.int32))).to(self.device)   # (F, 3) int32
@@ -146,29 +137,13 @@ class DepthFromMesh:
             raise ValueError(f"background: expected three values in 0..255, got {background}")
         self._keys = ops.Workspace(self.device)                                                 # render_frame's 64-bit keys, grown on demand
 
-    def _host_group_of(self, group_of, b):
-        g = np.asarray(group_of.cpu().numpy() if torch.is_tensor(group_of) else group_of)
-        G = len(self.group_off) - 1
-        if g.shape != (b,) or g.dtype.kind not in "iu" or g.min() < -1 or g.max() >= G:
-            raise ValueError(f"group_of: expected {b} integers in [-1, {G}), got {g.dtype} {g.shape}")
-        return np.ascontiguousarray(g, dtype=np.int32)
-
-    def _env_groups(self, b, group_of):
-        """The (F_shared, group_off, env_group, max_group_faces) of a call over b environments: the table of the constructor, or the
-        call's own group_of (b ints on the host, or an int32 tensor on the device, which is not read here)."""
-        if not self.groups:
+    def _call_groups(self, b, group_of):
+        """The (F_shared, group_off, env_group, max_group_faces) of a call over b environments; None without groups."""
+        if self._scene is None:
             if group_of is not None:
                 raise ValueError("group_of: this camera was built without groups=")
             return None
-        if group_of is None:
-            if b != self.num_envs:
-                raise ValueError(f"poses: expected {self.num_envs} environments (the group table's), got {b}; pass group_of= for a slice")
-            eg = self._group_of
-        elif torch.is_tensor(group_of) and group_of.is_cuda:
-            eg = group_of
-        else:
-            eg = torch.from_numpy(self._host_group_of(group_of, b)).to(self.device)
-        return self.face_shared, self._group_off, eg, self.max_group_faces
+        return self.face_shared, self._scene.group_off_dev, self._scene.for_call(b, group_of), self.max_group_faces
 
     def render(self, pose_R, pose_T, out=None, group_of=None):
         """pose_R [b, m, 3, 3], pose_T [b, m, 3] (any b) -> [b, V, im_h, im_w] float32: the z-depth (not the ray length) of the
@@ -180,16 +155,11 @@ class DepthFromMesh:
         n = self.num_view * self.im_h * self.im_w
         if out is not None:
             ops._out_rows(out, b, n)                                                           # a bad view is reported before the device
-        groups = self._env_groups(b, group_of)
+        groups = self._call_groups(b, group_of)
         ops._req(pose_R, pose_T, out, self.verts)
         pose_R, pose_T = pose_R.contiguous(), pose_T.contiguous()
-        if groups is not None:
-            res = ops.mesh_depth_render_groups(self.verts, self.vert_part, self.faces, groups[0], groups[1], groups[2], pose_R, pose_T,
-                                               self.cam_pose, self.fx, self.fy, self.cx, self.cy, self.im_h, self.im_w, self.near,
-                                               self.far, out, max_group_faces=groups[3])
-            return res[:, :n].unflatten(1, (self.num_view, self.im_h, self.im_w))
         res = ops.mesh_depth_render(self.verts, self.vert_part, self.faces, pose_R, pose_T, self.cam_pose, self.fx, self.fy, self.cx,
-                                    self.cy, self.im_h, self.im_w, self.near, self.far, out)
+                                    self.cy, self.im_h, self.im_w, self.near, self.far, out, groups=groups)
         return res[:, :n].unflatten(1, (self.num_view, self.im_h, self.im_w))
 
     def render_frame(self, pose_R, pose_T, depth=True, seg=True, rgb=True, out_depth=None, group_of=None):
@@ -200,7 +170,7 @@ class DepthFromMesh:
         where nothing is hit.  out_depth: as render()'s out.  The keys' workspace (8 b V im_h im_w bytes) belongs to this object and
         is reused while b fits.  group_of: as render()'s."""
         b, _ = ops.check_poses(pose_R, pose_T, self.part_num)
-        groups = self._env_groups(b, group_of)
+        groups = self._call_groups(b, group_of)
         if not (depth or seg or rgb):
             raise ValueError("render_frame: depth, seg and rgb are all switched off")
         if out_depth is not None and not depth:

@@ -25,7 +25,7 @@ from its own cloud.
 import numpy as np
 import torch
 
-from . import meshio, ops
+from . import meshio, ops, scene_groups
 
 SELECT_MODES = ("random", "all", "fps")
 
@@ -90,59 +90,46 @@ class PCfromMesh:
 
     def _init_groups(self, pcs, groups, group_of):
         """The point library of a scene whose environments differ: the shared parts' points, then every object's bodies."""
-        groups = [list(g) for g in groups]
-        if not groups:
-            raise ValueError("groups: at least one object is needed")
-        S = self.num_shared = self.part_num
+        S = self.part_num
         self._full = self._fps_ws = None
         self.part_pc = torch.from_numpy(pcs).to(self.device)                                   # (S, p, 3): the shared parts only
-        clouds, part, off = [pcs.reshape(-1, 3)], [np.repeat(np.arange(S, dtype=np.int32), self.points_per_part)], [0]
-        for k, bodies in enumerate(groups):
-            for j, body in enumerate(bodies):
-                if body is None:
-                    continue
-                if isinstance(body, (tuple, list)):
-                    pts = self.load_pc_from_mesh(body[0], body[1], self.GROUP_SEED_STRIDE * (k + 1) + j)
-                else:
-                    pts = np.ascontiguousarray(body.cpu().numpy() if torch.is_tensor(body) else body, dtype=np.float32)
-                    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
-                        raise ValueError(f"groups[{k}][{j}]: expected (vertices, faces), a (p, 3) array of points or None, got {pts.shape}")
-                clouds.append(pts)
-                part.append(np.full(len(pts), S + j, dtype=np.int32))
-            off.append(sum(len(c) for c in clouds[1:]))
-        self.part_num = S + max(len(bodies) for bodies in groups)
+        clouds, part = [pcs.reshape(-1, 3)], [np.repeat(np.arange(S, dtype=np.int32), self.points_per_part)]
+
+        def add(body, slot, what, k, j):
+            if isinstance(body, (tuple, list)):
+                pts = self.load_pc_from_mesh(body[0], body[1], self.GROUP_SEED_STRIDE * (k + 1) + j)
+            else:
+                pts = np.ascontiguousarray(body.cpu().numpy() if torch.is_tensor(body) else body, dtype=np.float32)
+                if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
+                    raise ValueError(f"{what}: expected (vertices, faces), a (p, 3) array of points or None, got {pts.shape}")
+            clouds.append(pts)
+            part.append(np.full(len(pts), slot, dtype=np.int32))
+            return len(pts)
+
+        sg = self._scene = scene_groups.SceneGroups(self.num_envs, self.device, S, groups, add, group_of)
+        self.num_shared, self.part_num, self.group_of, self.max_group_points = S, sg.part_num, sg.group_of, sg.most
+        self.group_off = sg.group_off.astype(np.int64)                                         # rows of pts, as before: int64
         self.pts_shared = S * self.points_per_part
-        self.group_off = np.asarray(off, dtype=np.int64)
-        self.max_group_points = int(np.diff(self.group_off).max())
         if self.pts_shared + self.max_group_points == 0:
             raise ValueError("meshes and groups: no mesh at all")
-        G = len(groups)
-        self.group_of = self._host_group_of(np.arange(int(self.num_envs)) % G if group_of is None else group_of, int(self.num_envs))
-        self._group_of = torch.from_numpy(self.group_of).to(self.device)
+        self._group_of_long = sg.group_of_dev.long()                                           # the index type of group_sel's gather
         self.pts = torch.from_numpy(np.ascontiguousarray(np.concatenate(clouds), dtype=np.float32)).to(self.device)   # (Q, 3)
         self.part_of = torch.from_numpy(np.concatenate(part)).to(self.device)                  # (Q,) int32: the slot
         self._all_table = None
 
-    def _host_group_of(self, group_of, b):
-        g = np.asarray(group_of.cpu().numpy() if torch.is_tensor(group_of) else group_of)
-        G = len(self.group_off) - 1
-        if g.shape != (b,) or g.dtype.kind not in "iu" or g.min() < -1 or g.max() >= G:
-            raise ValueError(f"group_of: expected {b} integers in [-1, {G}), got {g.dtype} {g.shape}")
-        return np.ascontiguousarray(g, dtype=np.int32)
-
-    def _env_groups(self, b, group_of):
-        """(host ints or None, device int64 (b,)) of a call over b environments: the constructor's table, or the call's own group_of
-        (b ints on the host, or an integer tensor on the device, which is not read here)."""
+    def _call_groups(self, b, group_of):
+        """(host ints or None, device int64 (b,)) of a call over b environments, by SceneGroups' rules, as the index group_sel gathers
+        with: the constructor's table, a host list validated once and copied, or a device tensor (not read here) checked for its
+        length and clamped."""
         if group_of is None:
-            if b != self.num_envs:
-                raise ValueError(f"poses: expected {self.num_envs} environments (the group table's), got {b}; pass group_of= for a slice")
-            return self.group_of, self._group_of.long()
+            self._scene.for_call(b, None)                                                      # the slice rule
+            return self.group_of, self._group_of_long
         if torch.is_tensor(group_of) and group_of.is_cuda:
             if tuple(group_of.shape) != (b,):
                 raise ValueError(f"group_of: expected ({b},), got {tuple(group_of.shape)}")
             g = group_of.long()                                                                # an id outside [-1, G) counts as -1, as in the kernels
             return None, torch.where((g >= 0) & (g < len(self.group_off) - 1), g, torch.full_like(g, -1))
-        host = self._host_group_of(group_of, b)
+        host = self._scene.host_group_of(group_of, b)
         return host, torch.from_numpy(host).to(self.device).long()
 
     def own_rows(self, g):
@@ -161,7 +148,7 @@ class PCfromMesh:
         otherwise, and asking for it from the host is an error."""
         if not self.groups:
             raise ValueError("group_sel: this cloud was built without groups=")
-        host, dev = self._env_groups(self.num_envs if group_of is None else len(group_of), group_of)
+        host, dev = self._call_groups(self.num_envs if group_of is None else len(group_of), group_of)
         K, G = self.num_points, len(self.group_off) - 1
         table = np.full((G + 1, K), -1, dtype=np.int32)
         for g in list(range(G)) + [-1]:
@@ -209,9 +196,7 @@ class PCfromMesh:
         object of each row of this call."""
         Q = self.pts.shape[0]
         b, _ = ops.check_poses(pose_R, pose_T, self.part_num)
-        if self.groups:
-            return self._query_pc_groups(pose_R, pose_T, b, out, sel, select, group_of)
-        if group_of is not None:
+        if group_of is not None and not self.groups:
             raise ValueError("group_of: this cloud was built without groups=")
         if sel is not None:
             if sel.dtype != torch.int32 or sel.dim() not in (1, 2) or (sel.dim() == 2 and sel.shape[0] != b) or sel.shape[-1] == 0:
@@ -219,13 +204,21 @@ class PCfromMesh:
             K = sel.shape[-1]
         elif select not in SELECT_MODES:
             raise ValueError(f"select: expected one of {SELECT_MODES}, got {select!r}")
+        elif self.groups and select == 'fps':
+            raise ValueError("select='fps': not available with groups= (the farthest-point kernel thins one cloud of a common size; "
+                             "the environments' own clouds differ in size)")
+        elif self.groups:
+            K = self.pts_shared + self.max_group_points if select == 'all' else self.num_points
         else:
             K = Q if select == 'all' else min(self.num_points, Q)
         if out is not None:
             ops._out_rows(out, b, 3 * K)                                                       # a bad view is reported before the device and any launch
+        env = self._call_groups(b, group_of) if self.groups and sel is None else None          # ... and so is a slice without its group_of
         ops._req(pose_R, pose_T, sel, out, self.pts)
         pose_R, pose_T = pose_R.contiguous(), pose_T.contiguous()
-        if sel is None and select == 'random':
+        if sel is None and self.groups:
+            sel = self.group_sel(group_of=group_of) if select == 'random' else self._all_sel(env[1])
+        elif sel is None and select == 'random':
             randperm = torch.randperm(Q)
             sel = randperm[:self.num_points].to(torch.int32).to(self.device)
         elif sel is None and select == 'fps':
@@ -236,29 +229,6 @@ class PCfromMesh:
                 self._fps_ws = ops.Workspace(pose_R.device)
             ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, None, self._full)
             sel = ops.fps(self._full.view(b, Q, 3), self.num_points, self._fps_ws)
-        res = ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, sel, out)
-        self.last_sel = sel
-        return res[:, :3 * K].unflatten(1, (K, 3))
-
-    def _query_pc_groups(self, pose_R, pose_T, b, out, sel, select, group_of):
-        if sel is not None:
-            if sel.dtype != torch.int32 or sel.dim() not in (1, 2) or (sel.dim() == 2 and sel.shape[0] != b) or sel.shape[-1] == 0:
-                raise ValueError(f"sel: expected an int32 tensor (K,) or ({b}, K), got {sel.dtype} {tuple(sel.shape)}")
-            K = sel.shape[-1]
-        elif select not in SELECT_MODES:
-            raise ValueError(f"select: expected one of {SELECT_MODES}, got {select!r}")
-        elif select == 'fps':
-            raise ValueError("select='fps': not available with groups= (the farthest-point kernel thins one cloud of a common size; "
-                             "the environments' own clouds differ in size)")
-        else:
-            K = self.pts_shared + self.max_group_points if select == 'all' else self.num_points
-        if out is not None:
-            ops._out_rows(out, b, 3 * K)                                                       # a bad view is reported before the device and any launch
-        env = None if sel is not None else self._env_groups(b, group_of)                       # ... and so is a slice without its group_of
-        ops._req(pose_R, pose_T, sel, out, self.pts)
-        pose_R, pose_T = pose_R.contiguous(), pose_T.contiguous()
-        if sel is None:
-            sel = self.group_sel(group_of=group_of) if select == 'random' else self._all_sel(env[1])
         res = ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, sel, out)
         self.last_sel = sel
         return res[:, :3 * K].unflatten(1, (K, 3))

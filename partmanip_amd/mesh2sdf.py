@@ -40,7 +40,7 @@ import os
 import numpy as np
 import torch
 
-from . import meshio, ops
+from . import meshio, ops, scene_groups
 
 OBJ_SDF_PATH = os.path.join("assets", "objs", "cube", "sdf.npy")                     # mesh2sdf.py:48
 
@@ -184,34 +184,27 @@ class TSDFfromMesh:
             raise ValueError("group_of: needs groups=")
         self.groups = groups is not None
         self._group_dicts = []
+        self._scene = None
         if self.groups:
-            groups = [list(g) for g in groups]
-            if not groups:
-                raise ValueError("groups: at least one object is needed")
-            S = len(self.sdf_dict_list)
-            slot, off = list(range(S)), [0]
-            for k, bodies in enumerate(groups):
-                for j, d in enumerate(bodies):
-                    if d is None:
-                        continue
-                    if not isinstance(d, dict) or not {'sdf', 'bbox_min', 'voxel_size'} <= set(d):
-                        raise ValueError(f"groups[{k}][{j}]: expected a dict with 'sdf', 'bbox_min' and 'voxel_size', or None")
-                    self._group_dicts.append(d)
-                    slot.append(S + j)
-                off.append(len(self._group_dicts))
+            slot = list(range(len(self.sdf_dict_list)))
+
+            def add(d, s, what, k, j):
+                if not isinstance(d, dict) or not {'sdf', 'bbox_min', 'voxel_size'} <= set(d):
+                    raise ValueError(f"{what}: expected a dict with 'sdf', 'bbox_min' and 'voxel_size', or None")
+                self._group_dicts.append(d)
+                slot.append(s)
+                return 1
+
+            sg = self._scene = scene_groups.SceneGroups(num_envs, self.device, len(slot), groups, add, group_of)
             if not slot:
                 raise ValueError("sdf_dicts and groups: no grid at all")
             self.grid_slot = np.asarray(slot, dtype=np.int32)
-            self.group_off = np.asarray(off, dtype=np.int32)
-            self.max_group_grids = int(np.diff(self.group_off).max())
-            self.group_of = self._host_group_of(np.arange(int(num_envs)) % len(groups) if group_of is None else group_of, int(num_envs))
+            self._grid_slot = torch.from_numpy(self.grid_slot).to(self.device)
+            self.num_shared, self.group_off, self.group_of, self.max_group_grids = sg.num_shared, sg.group_off, sg.group_of, sg.most
+            self._group_of = sg.group_of_dev
         self.merge_sdf_field()
         if self.groups:
-            self.num_shared = len(self.sdf_dict_list)
-            self.part_num = self.num_shared + max(len(bodies) for bodies in groups)
-            self._grid_slot = torch.from_numpy(self.grid_slot).to(self.device)
-            self._group_off = torch.from_numpy(self.group_off).to(self.device)
-            self._group_of = torch.from_numpy(self.group_of).to(self.device)
+            self.part_num = sg.part_num                                              # pose slots, not merge_sdf_field's library rows
 
     # ------------------------------------------------------------------------------------------------ loading
     def load_franka(self, hand_base_path):
@@ -281,31 +274,20 @@ class TSDFfromMesh:
         self.init_tsdf = torch.as_tensor(nerf_pred_tsdf, dtype=torch.float32).to(self.device) * self.sdf_trunc
         self._init_base = self.init_tsdf.reshape(self.num_envs, self.point_num).contiguous()
 
-    def _host_group_of(self, group_of, b):
-        g = np.asarray(group_of.cpu().numpy() if torch.is_tensor(group_of) else group_of)
-        G = len(self.group_off) - 1
-        if g.shape != (b,) or g.dtype.kind not in "iu" or g.min() < -1 or g.max() >= G:
-            raise ValueError(f"group_of: expected {b} integers in [-1, {G}), got {g.dtype} {g.shape}")
-        return np.ascontiguousarray(g, dtype=np.int32)
-
-    def _env_groups(self, b, group_of):
-        """The env_group table of a call over b environments: the constructor's, or the call's own group_of (b ints on the host, or
-        an int32 tensor on the device, which is not read here).  None without groups."""
-        if not self.groups:
-            if group_of is not None:
-                raise ValueError("group_of: this object was built without groups=")
-            return None
-        if group_of is None:
-            if b != self.num_envs:
-                raise ValueError(f"poses: expected {self.num_envs} environments (the group table's), got {b}; pass group_of= for a slice")
-            return self._group_of
-        if torch.is_tensor(group_of) and group_of.is_cuda:
-            return group_of
-        return torch.from_numpy(self._host_group_of(group_of, b)).to(self.device)
+    def _row_range(self):
+        """(s, e) of a query: it covers rows [0, e), of which [0, s) are the scene's and [s, e) the object's -- the parts, or with
+        groups the ordinals of an environment's own rows (the shared ones, then its group's)."""
+        if self.groups:
+            return self.num_shared, self.num_shared + self.max_group_grids
+        return self.part_num - 1, self.part_num
 
     def _query(self, pose_R, pose_T, p0, p1, base, out, brick_skip=True, group_of=None):
-        """Parts [p0, p1) against `base`; with groups, the ordinals [p0, p1) of every environment's own rows."""
-        eg = self._env_groups(ops.check_poses(pose_R, pose_T, self.part_num)[0] if self.groups else 0, group_of)
+        """Rows [p0, p1) of _row_range against `base`."""
+        eg = None
+        if self.groups:
+            eg = self._scene.for_call(ops.check_poses(pose_R, pose_T, self.part_num)[0], group_of)
+        elif group_of is not None:
+            raise ValueError("group_of: this object was built without groups=")
         pose_R = pose_R.to(torch.float32).reshape(-1, self.part_num, 3, 3).contiguous()
         pose_T = pose_T.to(torch.float32).reshape(-1, self.part_num, 3).contiguous()
         n = self.point_num
@@ -313,9 +295,9 @@ class TSDFfromMesh:
             raise ValueError(f"initialize_sdf was given {base.shape[0]} environments, the poses have {pose_R.shape[0]}")
         if eg is not None:
             res = ops.mesh_tsdf_query_groups(self.sdf_field, self.sdf_field_off, self.sdf_field_res, self.sdf_bbox_min,
-                                             self.sdf_voxel_size, self._grid_slot, self.num_shared, self._group_off, eg, pose_R, pose_T,
-                                             self.resolution, self.vox_size, self._origin3, self.sdf_trunc, base, p0, p1, out, brick_skip,
-                                             max_group_grids=self.max_group_grids)
+                                             self.sdf_voxel_size, self._grid_slot, self.num_shared, self._scene.group_off_dev, eg, pose_R,
+                                             pose_T, self.resolution, self.vox_size, self._origin3, self.sdf_trunc, base, p0, p1, out,
+                                             brick_skip, max_group_grids=self.max_group_grids)
         else:
             res = ops.mesh_tsdf_query(self.sdf_field, self.sdf_field_off, self.sdf_field_res, self.sdf_bbox_min, self.sdf_voxel_size,
                                       pose_R, pose_T, self.resolution, self.vox_size, self._origin3, self.sdf_trunc, base,
@@ -328,9 +310,7 @@ class TSDFfromMesh:
         unit inner stride (e.g. obs[:, :res^3] of an observation buffer); the result is then a view of its first res^3 columns.
         brick_skip=False turns the brick-level part rejection off (same bits, slower; for tests).  With groups=: one launch of the
         grouped entry; b = num_envs, or group_of= (b,) names the object of each row of this call."""
-        if self.groups:
-            return self._query(pose_R, pose_T, 0, self.num_shared + self.max_group_grids, self._init_base, out, brick_skip, group_of)
-        return self._query(pose_R, pose_T, 0, self.part_num, self._init_base, out, brick_skip, group_of)
+        return self._query(pose_R, pose_T, 0, self._row_range()[1], self._init_base, out, brick_skip, group_of)
 
     query_tsdf_parallel = query_tsdf
     query_tsdf_naive = query_tsdf          # the reference's naive path cannot run (class docstring); same kernel
@@ -341,13 +321,10 @@ class TSDFfromMesh:
         With groups=: (the shared rows against the base field, the environment's own rows against the ground plane).  The equality
         holds while the base field is the ground plane, as in the reference (after initialize_sdf the object's volume still carries
         the ground)."""
-        if self.groups:
-            S, most = self.num_shared, self.max_group_grids
-            if S == 0 or most == 0:
-                raise ValueError("query_tsdf_seperately: needs at least one shared grid and one grid in a group")
-            scene = self._query(pose_R, pose_T, 0, S, self._init_base, out_scene, group_of=group_of)
-            obj = self._query(pose_R, pose_T, S, S + most, self._ground, out_obj, group_of=group_of)
-            return scene, obj
-        scene = self._query(pose_R, pose_T, 0, self.part_num - 1, self._init_base, out_scene)
-        obj = self._query(pose_R, pose_T, self.part_num - 1, self.part_num, self._ground, out_obj)
+        s, e = self._row_range()
+        if self.groups and (s == 0 or e == s):
+            raise ValueError("query_tsdf_seperately: needs at least one shared grid and one grid in a group")
+        group_of = group_of if self.groups else None                                 # without groups it has always been ignored here
+        scene = self._query(pose_R, pose_T, 0, s, self._init_base, out_scene, group_of=group_of)
+        obj = self._query(pose_R, pose_T, s, e, self._ground, out_obj, group_of=group_of)
         return scene, obj

@@ -1376,22 +1376,25 @@ def tsdf_integrate(depth, pix_idx, pix_z, trunc, default_tsdf):
     return out
 
 
-def mesh_tsdf_query(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, res, vox_size, origin,
-                    sdf_trunc, base, p0=0, p1=None, out=None, brick_skip=True):
-    """The mesh-TSDF observation of parts [p0, p1) (pm_mesh_tsdf_query_f32): fields (flat float32), part_off (M) int64,
-    part_shape (M,3) int32, part_bbox_min (M,3), part_voxel_size (M), pose_R (B,M,3,3), pose_T (B,M,3), origin = 3 floats,
-    base (res^3) or (B, res^3).  out: None (a fresh (B, res^3)) or a 2-D float32 view (B, >= res^3) with unit inner stride --
-    columns past res^3 are left alone.  Returns out."""
-    _one_device("mesh_tsdf_query", fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, base, out)
-    for t_, name in ((fields, "fields"), (part_bbox_min, "part_bbox_min"), (part_voxel_size, "part_voxel_size"),
-                     (pose_R, "pose_R"), (pose_T, "pose_T"), (base, "base")):
-        _f32c(t_, name)
-    if part_off.dtype != torch.int64 or not part_off.is_contiguous():
-        raise ValueError("part_off: expected a contiguous int64 tensor")
+def _mesh_tsdf_tables(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, base, grouped):
+    """The table checks mesh_tsdf_query and mesh_tsdf_query_groups share.  The tables have one row per pose slot (M parts), or when
+    `grouped` one per grid of a library (NG >= 1 grids, any M).  Returns (the tables' rows, B, M)."""
+    _f32c(fields, "fields"), _f32c(part_bbox_min, "part_bbox_min"), _f32c(part_voxel_size, "part_voxel_size")
+    _f32c(pose_R, "pose_R"), _f32c(pose_T, "pose_T"), _f32c(base, "base")
+    n = part_off.numel()
+    if part_off.dtype != torch.int64 or not part_off.is_contiguous() or (grouped and n == 0):
+        raise ValueError("part_off: expected a contiguous int64 tensor" + (" of at least one row" if grouped else ""))
     _i32c(part_shape, "part_shape")
-    B, M = check_poses(pose_R, pose_T, part_off.numel())
-    if tuple(part_shape.shape) != (M, 3) or tuple(part_bbox_min.shape) != (M, 3) or part_voxel_size.numel() != M:
-        raise ValueError("part tables: expected part_shape (M,3), part_bbox_min (M,3), part_voxel_size (M)")
+    B, M = check_poses(pose_R, pose_T, None if grouped else n)
+    if tuple(part_shape.shape) != (n, 3) or tuple(part_bbox_min.shape) != (n, 3) or part_voxel_size.numel() != n:
+        what, r = ("grid", "NG") if grouped else ("part", "M")
+        raise ValueError(f"{what} tables: expected part_shape ({r},3), part_bbox_min ({r},3), part_voxel_size ({r})")
+    return n, B, M
+
+
+def _mesh_tsdf_volume(res, origin, base, B, out, device):
+    """The volume arguments the two queries share, checked once their tables are: base (res^3) or (B, res^3), the `out=` rule and
+    the origin's three floats.  Returns (per_env, out, its row stride, ox, oy, oz)."""
     n = int(res) ** 3
     if tuple(base.shape) == (n,):
         per_env = 0
@@ -1399,8 +1402,20 @@ def mesh_tsdf_query(fields, part_off, part_shape, part_bbox_min, part_voxel_size
         per_env = 1
     else:
         raise ValueError(f"base: expected ({n},) or ({B}, {n}), got {tuple(base.shape)}")
-    out, ldo = _out_rows(out, B, n, pose_R.device)
+    out, ldo = _out_rows(out, B, n, device)
     ox, oy, oz = (float(v) for v in origin)
+    return per_env, out, ldo, ox, oy, oz
+
+
+def mesh_tsdf_query(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, res, vox_size, origin,
+                    sdf_trunc, base, p0=0, p1=None, out=None, brick_skip=True):
+    """The mesh-TSDF observation of parts [p0, p1) (pm_mesh_tsdf_query_f32): fields (flat float32), part_off (M) int64,
+    part_shape (M,3) int32, part_bbox_min (M,3), part_voxel_size (M), pose_R (B,M,3,3), pose_T (B,M,3), origin = 3 floats,
+    base (res^3) or (B, res^3).  out: None (a fresh (B, res^3)) or a 2-D float32 view (B, >= res^3) with unit inner stride --
+    columns past res^3 are left alone.  Returns out."""
+    _one_device("mesh_tsdf_query", fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, base, out)
+    _, B, M = _mesh_tsdf_tables(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, base, grouped=False)
+    per_env, out, ldo, ox, oy, oz = _mesh_tsdf_volume(res, origin, base, B, out, pose_R.device)
     with TIMER.bracket("mesh_tsdf_query"):
         check(lib.pm_mesh_tsdf_query_f32(_ptr(fields), _ptr(part_off), _ptr(part_shape), _ptr(part_bbox_min), _ptr(part_voxel_size),
                                          _ptr(pose_R), _ptr(pose_T), B, M, int(p0), M if p1 is None else int(p1), int(res),
@@ -1419,16 +1434,7 @@ def mesh_tsdf_query_groups(fields, part_off, part_shape, part_bbox_min, part_vox
     integers (checked against [0, M) and copied) or an int32 device tensor (type and length only; the kernel leaves a row with a
     slot outside [0, M) unsampled).  group_off / env_group / max_group_grids as face_groups takes them; everything else, and the
     result, as mesh_tsdf_query."""
-    for t_, name in ((fields, "fields"), (part_bbox_min, "part_bbox_min"), (part_voxel_size, "part_voxel_size"),
-                     (pose_R, "pose_R"), (pose_T, "pose_T"), (base, "base")):
-        _f32c(t_, name)
-    if part_off.dtype != torch.int64 or not part_off.is_contiguous() or part_off.numel() == 0:
-        raise ValueError("part_off: expected a contiguous int64 tensor of at least one row")
-    _i32c(part_shape, "part_shape")
-    NG = part_off.numel()
-    B, M = check_poses(pose_R, pose_T)
-    if tuple(part_shape.shape) != (NG, 3) or tuple(part_bbox_min.shape) != (NG, 3) or part_voxel_size.numel() != NG:
-        raise ValueError("grid tables: expected part_shape (NG,3), part_bbox_min (NG,3), part_voxel_size (NG)")
+    NG, B, M = _mesh_tsdf_tables(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, base, grouped=True)
     if torch.is_tensor(grid_slot) and grid_slot.is_cuda:
         _i32c(grid_slot, "grid_slot")
         if tuple(grid_slot.shape) != (NG,):
@@ -1445,15 +1451,7 @@ def mesh_tsdf_query_groups(fields, part_off, part_shape, part_bbox_min, part_vox
     t0, t1 = int(t0), int(NG_shared) + most if t1 is None else int(t1)
     if not 0 <= t0 < t1 <= int(NG_shared) + most:
         raise ValueError(f"t0, t1: expected 0 <= t0 < t1 <= NG_shared + max_group_grids = {int(NG_shared) + most}, got {t0}, {t1}")
-    n = int(res) ** 3
-    if tuple(base.shape) == (n,):
-        per_env = 0
-    elif tuple(base.shape) == (B, n):
-        per_env = 1
-    else:
-        raise ValueError(f"base: expected ({n},) or ({B}, {n}), got {tuple(base.shape)}")
-    out, ldo = _out_rows(out, B, n, pose_R.device)
-    ox, oy, oz = (float(v) for v in origin)
+    per_env, out, ldo, ox, oy, oz = _mesh_tsdf_volume(res, origin, base, B, out, pose_R.device)
     with TIMER.bracket("mesh_tsdf_query_groups"):
         check(lib.pm_mesh_tsdf_query_groups_f32(_ptr(fields), _ptr(part_off), _ptr(part_shape), _ptr(part_bbox_min),
                                                 _ptr(part_voxel_size), _ptr(grid_slot), NG, int(NG_shared), _ptr(group_off), G,
@@ -1518,19 +1516,33 @@ def _mesh_camera_args(verts, vert_part, faces, pose_R, pose_T, cam_pose, im_h, i
     return NV, B, M, V, im_h, im_w
 
 
-def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h, im_w, near=0.01, far=100.0, out=None):
+def mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h, im_w, near=0.01, far=100.0, out=None,
+                      groups=None):
     """Depth images of the posed part meshes (pm_mesh_depth_render_f32): verts (NV, 3) canonical vertices of all parts, vert_part (NV)
     int32, faces (F, 3) int32 into verts, pose_R (B, M, 3, 3), pose_T (B, M, 3), cam_pose (V, 4, 4) camera->world (camera looks along
     +z, x right, y down).  out: None (a fresh (B, V h w)) or a 2-D float32 view (B, >= V h w) with unit inner stride -- columns past
     V h w are left alone.  Returns out; out[b, (v h + r) w + c] = z-depth of the nearest surface through pixel (r, c) of view v, `far`
-    where nothing is hit; the fp32 arithmetic is fixed (include/partmanip_hip.h), so the bits repeat."""
-    _one_device("mesh_depth_render", verts, vert_part, faces, pose_R, pose_T, cam_pose, out)
+    where nothing is hit; the fp32 arithmetic is fixed (include/partmanip_hip.h), so the bits repeat.
+    groups: None, or mesh_depth_render_groups' (F_shared, group_off, env_group, max_group_faces)."""
+    if groups is None:                                       # each entry keeps its own order of refusals: devices first here, tables first below
+        _one_device("mesh_depth_render", verts, vert_part, faces, pose_R, pose_T, cam_pose, out)
     NV, B, M, V, im_h, im_w = _mesh_camera_args(verts, vert_part, faces, pose_R, pose_T, cam_pose, im_h, im_w, near, far)
+    if groups is not None:
+        F_shared, group_off, env_group, most = groups
+        group_off, env_group, G, most = face_groups(group_off, env_group, faces.shape[0], F_shared, B, pose_R.device, most)
+        _one_device("mesh_depth_render_groups", verts, vert_part, faces, group_off, env_group, pose_R, pose_T, cam_pose, out)
     out, ldo = _out_rows(out, B, V * im_h * im_w, pose_R.device)
-    with TIMER.bracket("mesh_depth_render"):
-        check(lib.pm_mesh_depth_render_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], _ptr(pose_R), _ptr(pose_T),
-                                           B, M, _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w,
-                                           float(near), float(far), _ptr(out), ldo, _stream()), "pm_mesh_depth_render_f32")
+    # the arguments after F, which both entries share; the grouped entry takes five more before them
+    rest = (_ptr(pose_R), _ptr(pose_T), B, M, _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w, float(near),
+            float(far), _ptr(out), ldo, _stream())
+    if groups is None:
+        with TIMER.bracket("mesh_depth_render"):
+            check(lib.pm_mesh_depth_render_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], *rest),
+                  "pm_mesh_depth_render_f32")
+        return out
+    with TIMER.bracket("mesh_depth_render_groups"):
+        check(lib.pm_mesh_depth_render_groups_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], int(F_shared),
+                                                  _ptr(group_off), G, _ptr(env_group), most, *rest), "pm_mesh_depth_render_groups_f32")
     return out
 
 
@@ -1578,16 +1590,8 @@ def mesh_depth_render_groups(verts, vert_part, faces, F_shared, group_off, env_g
     """mesh_depth_render over a scene whose environments differ (pm_mesh_depth_render_groups_f32): environment b draws rows
     [0, F_shared) of faces and the rows of group env_group[b] (-1: none), group g being rows F_shared + [group_off[g], group_off[g + 1]).
     group_off / env_group / max_group_faces as face_groups takes them; everything else, and the result, as mesh_depth_render."""
-    NV, B, M, V, im_h, im_w = _mesh_camera_args(verts, vert_part, faces, pose_R, pose_T, cam_pose, im_h, im_w, near, far)
-    group_off, env_group, G, most = face_groups(group_off, env_group, faces.shape[0], F_shared, B, pose_R.device, max_group_faces)
-    _one_device("mesh_depth_render_groups", verts, vert_part, faces, group_off, env_group, pose_R, pose_T, cam_pose, out)
-    out, ldo = _out_rows(out, B, V * im_h * im_w, pose_R.device)
-    with TIMER.bracket("mesh_depth_render_groups"):
-        check(lib.pm_mesh_depth_render_groups_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], int(F_shared),
-                                                  _ptr(group_off), G, _ptr(env_group), most, _ptr(pose_R), _ptr(pose_T), B, M,
-                                                  _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w, float(near),
-                                                  float(far), _ptr(out), ldo, _stream()), "pm_mesh_depth_render_groups_f32")
-    return out
+    return mesh_depth_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h, im_w, near, far, out,
+                             groups=(F_shared, group_off, env_group, max_group_faces))
 
 
 def mesh_frame_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy, cx, cy, im_h, im_w, near, far, workspace,
@@ -1630,27 +1634,21 @@ def mesh_frame_render(verts, vert_part, faces, pose_R, pose_T, cam_pose, fx, fy,
     if rgb is not False:
         rgb, ldc = _out_rows(None if rgb is True else rgb, B, 3 * n, dev, torch.uint8, "rgb")
     d_, s_, c_ = (None if o is False else o for o in (depth, seg, rgb))
-    if groups is not None:
-        F_shared, group_off, env_group, most = groups
-        group_off, env_group, G, most = face_groups(group_off, env_group, faces.shape[0], F_shared, B, dev, most)
-        _one_device("mesh_frame_render_groups", verts, group_off, env_group)
-        with TIMER.bracket("mesh_frame_render_groups"):
-            check(lib.pm_mesh_frame_render_groups_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], int(F_shared),
-                                                      _ptr(group_off), G, _ptr(env_group), most, _ptr(pose_R), _ptr(pose_T), B, M,
-                                                      _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w,
-                                                      float(near), float(far), _ptr(part_label), int(miss_label), _ptr(palette),
-                                                      float(ambient), one_minus_ambient, bg[0], bg[1], bg[2], _ptr(d_), ldd, _ptr(s_),
-                                                      lds, _ptr(c_), ldc, _ptr(workspace),
-                                                      workspace.numel() * workspace.element_size(), _stream()),
-                  "pm_mesh_frame_render_groups_f32")
+    # the arguments after F, which both entries share; the grouped entry takes five more before them
+    rest = (_ptr(pose_R), _ptr(pose_T), B, M, _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w, float(near),
+            float(far), _ptr(part_label), int(miss_label), _ptr(palette), float(ambient), one_minus_ambient, bg[0], bg[1], bg[2], _ptr(d_),
+            ldd, _ptr(s_), lds, _ptr(c_), ldc, _ptr(workspace), workspace.numel() * workspace.element_size(), _stream())
+    if groups is None:
+        with TIMER.bracket("mesh_frame_render"):
+            check(lib.pm_mesh_frame_render_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], *rest),
+                  "pm_mesh_frame_render_f32")
         return d_, s_, c_
-    with TIMER.bracket("mesh_frame_render"):
-        check(lib.pm_mesh_frame_render_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], _ptr(pose_R), _ptr(pose_T),
-                                           B, M, _ptr(cam_pose), V, float(fx), float(fy), float(cx), float(cy), im_h, im_w,
-                                           float(near), float(far), _ptr(part_label), int(miss_label), _ptr(palette), float(ambient),
-                                           one_minus_ambient, bg[0], bg[1], bg[2], _ptr(d_), ldd, _ptr(s_), lds, _ptr(c_), ldc,
-                                           _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
-              "pm_mesh_frame_render_f32")
+    F_shared, group_off, env_group, most = groups
+    group_off, env_group, G, most = face_groups(group_off, env_group, faces.shape[0], F_shared, B, dev, most)
+    _one_device("mesh_frame_render_groups", verts, group_off, env_group)
+    with TIMER.bracket("mesh_frame_render_groups"):
+        check(lib.pm_mesh_frame_render_groups_f32(_ptr(verts), _ptr(vert_part), NV, _ptr(faces), faces.shape[0], int(F_shared),
+                                                  _ptr(group_off), G, _ptr(env_group), most, *rest), "pm_mesh_frame_render_groups_f32")
     return d_, s_, c_
 
 

@@ -156,10 +156,12 @@ def test_frame_equals_the_definition_on_every_environments_own_subset(scene, loa
     seen = set(np.unique(npy(frame.seg)))
     assert {-3, 5} <= seen and seen & {1, 2, 3}
     # a one-environment slice with its own group_of: the recorder's call
-    one = cam.render_frame(R[1:2], T[1:2], depth=False, seg=False, group_of=[1])
-    assert torch.equal(one.rgb[0], frame.rgb[1])
+    one_host = cam.render_frame(R[1:2], T[1:2], depth=False, seg=False, group_of=[1])
+    assert torch.equal(one_host.rgb[0], frame.rgb[1])
     one = cam.render(R[2:3], T[2:3], group_of=cam._group_of[2:3])
     assert torch.equal(one[0], frame.depth[2])
+    dev = cam.render_frame(R[1:2], T[1:2], depth=False, seg=False, group_of=cam._group_of[1:2])    # ... and as an int32 device tensor
+    assert dev.rgb.dtype == torch.uint8 and torch.equal(dev.rgb[0], frame.rgb[1]) and torch.equal(dev.rgb, one_host.rgb)
 
 
 # ------------------------------------------------------------------------------------------- 3. body poses, 4. the closed loop

@@ -249,6 +249,47 @@ def test_cloud_without_groups_is_as_before():
     assert ob.width == 3 * K and torch.equal(ob.sel, grouped.group_sel())
 
 
+# ------------------------------------------------------------------------------------------- the three observers agree
+def test_the_three_observers_lay_one_object_structure_out_alike():
+    """3 objects of 1, 4 and 0 bodies, the second body of the 4-body object without a mesh, behind 2 shared parts, 6 environments."""
+    from tests import depth_render_ref as D
+    from partmanip_amd.mesh2depth import DepthFromMesh
+    from partmanip_amd.mesh2pc import PCfromMesh
+    from partmanip_amd.mesh2sdf import TSDFfromMesh
+    sc = S.small_scene()
+    p = sc["parts"]
+    box = [MB.box_mesh((0.02 + 0.01 * i, 0.03, 0.04), (0.0, 0.0, 0.01 * i)) for i in range(6)]       # 8 vertices, 12 faces each
+    structure = lambda b: [[b[2]], [b[3], None, b[4], b[5]], []]                              # noqa: E731
+    intr = np.array([[60.0, 0, 20.0], [0, 60.0, 12.0], [0, 0, 1]])
+
+    def build(group_of):
+        return (DepthFromMesh(6, "cpu", np.stack([D.look_at((0.3, 0.1, 0.2))]), intr, 24, 40, meshes=box[:2], groups=structure(box), group_of=group_of),
+                TSDFfromMesh(6, S.SIZE, S.RES, "cpu", sdf_dicts=p[:2], groups=structure(p), group_of=group_of),
+                PCfromMesh(6, "cpu", num_points=K, meshes=box[:2], groups=structure(box), group_of=group_of, seed=7))
+
+    cam, grids, pc = build(sc["env_group"])
+    for o in (cam, grids, pc):
+        assert o.groups and o.num_shared == 2 and o.part_num == 2 + 4
+        assert o.group_of.tolist() == sc["env_group"].tolist() and o.group_of.dtype == np.int32
+        assert len(o.group_off) - 1 == 3
+    # the rows of one body, per observer: 12 faces over 8 vertices, 1 grid, K points
+    assert cam.group_off.tolist() == [0, 12, 48, 48] and grids.group_off.tolist() == [0, 1, 4, 4] and pc.group_off.tolist() == [0, K, 4 * K, 4 * K]
+    assert (cam.max_group_faces, grids.max_group_grids, pc.max_group_points) == (36, 3, 3 * K)
+    assert (cam.face_shared, pc.pts_shared) == (24, 2 * K)
+    # every library row of body j names slot num_shared + j; the mesh-less body (slot 3) has no row anywhere: 6 bodies' rows in all
+    slots = [0, 1, 2 + 0, 2 + 0, 2 + 2, 2 + 3]
+    vert_slot, point_slot = cam.vert_part.numpy().reshape(-1, 8), pc.part_of.numpy().reshape(-1, K)
+    assert tuple(cam.faces.shape) == (6 * 12, 3) and grids.sdf_field_off.numel() == 6 and tuple(pc.pts.shape) == (6 * K, 3)
+    assert (vert_slot == np.asarray(slots)[:, None]).all() and vert_slot.shape[0] == 6
+    assert grids.grid_slot.tolist() == slots
+    assert (point_slot == np.asarray(slots)[:, None]).all() and point_slot.shape[0] == 6
+    face_slot = cam.vert_part.numpy()[cam.faces.numpy()]
+    assert (face_slot == np.repeat(slots, 12)[:, None]).all()
+    # the default: env % num_objs, for all three
+    for o in build(None):
+        assert o.group_of.tolist() == [0, 1, 2, 0, 1, 2] and o.group_of.dtype == np.int32
+
+
 # ------------------------------------------------------------------------------------------- bake_groups
 def test_bake_groups_refuses_a_grid_of_2_to_the_31_cells_before_baking():
     from partmanip_amd.mesh2sdf import bake_grid_layout, bake_groups
