@@ -922,6 +922,22 @@ class PointNet2(_HipNet):
             if need_dx:
                 dpooled = drows if direct else ops.group_concat_bwd(drows, rec.idx, B, rec.P, rec.cf, rec.ldo).view(B * rec.P, rec.cf)
 
+
+class _GatheredOperand(NamedTuple):       # what SparseUNet._conv keeps of a gathered layer for its backward
+    src: torch.Tensor                     # the rows the table points into
+    idx: torch.Tensor                     # the table the forward used (PADDED: the widened one)
+    C: int
+    cols: Optional[torch.Tensor]          # MATERIALISED: the operand
+    K: int                                # the layer's own K = J * C, the width of its weight
+
+
+class _DecoderGrads(NamedTuple):          # what each of SparseUNet's three decoder backwards hands to the strided levels 1 and 0
+    dzD2: torch.Tensor                    # gradient of conv2's input
+    dzH: tuple                            # [level] the skip half's gradient of H0 / H1 (where skip[level] is set: a buffer to fill)
+    skip: tuple                           # [level] None, or a sparse raw skip gradient: (values (N, C), row -> values-row map)
+    acc: int                              # ops.ACC_*: what dzH holds when the strided layer's contribution arrives
+
+
 class SparseUNet(_HipNet):
     """3D sparse-voxel U-Net encoder as a backbone plug-in (`network.name: SparseUNet`).
 
@@ -980,36 +996,30 @@ class SparseUNet(_HipNet):
         grid0, coords0, feat0 = ops.voxel_grid0(x, P, C, R)
         l1 = ops.voxel_down(coords0, grid0, R, B)
         l2 = ops.voxel_down(l1["coords"], l1["grid"], l1["R"], B)
-        # conv0's operand is 27 taps x 4 channels = 108 columns: the level-0 table is built 32 taps wide (five absent taps), so
-        # that the layer is four whole K-steps of the gathered GEMM without a padded copy of the table per forward
-        pad0 = 32 if (self.fused_gather and self.in_channels >= 3) else 27
-        nbr0p = ops.voxel_nbr27(coords0, grid0, R, pad0)
+        # conv0 (27 taps x 4 channels = 108 columns) is a PADDED layer: its table is built 32 taps wide here, not widened per forward
+        nbr0p = ops.voxel_nbr27(coords0, grid0, R, 32 if ops.sparse_operand_form(self.fused_gather, 27, 4) == ops.PADDED else 27)
         return dict(feat0=feat0, nbr0=nbr0p[:, :27], nbr0p=nbr0p, nbr1=ops.voxel_nbr27(l1["coords"], l1["grid"], l1["R"]),
                     nbr2=ops.voxel_nbr27(l2["coords"], l2["grid"], l2["R"]), l1=l1, l2=l2, rows=(B * P, l1["rows"], l2["rows"]))
 
+    # The PADDED form lives in this pair: the weight goes in with zero columns behind it (_widened), its gradient comes out that
+    # wide and is cropped back (_conv_wgrad).  A table that is not padded passes through both untouched.
     @staticmethod
-    def _mirror(nbr):
-        """Mirrored neighbour table for the data gradient: row r reads s as neighbour j  <=>  s reads r as neighbour 26 - j,
-        so the rows whose output used s are nbr[s].flip.  A row that is nobody's neighbour (a duplicate coordinate: its centre
-        tap points at the canonical row, not at itself) gets -1 everywhere and a gradient of exactly zero."""
-        return ops.voxel_mirror27(nbr)
+    def _widened(W, K):
+        if K == W.shape[1]:
+            return W
+        W_p = torch.zeros(W.shape[0], K, device=W.device)
+        W_p[:, :W.shape[1]].copy_(W)
+        return W_p
 
-    def _conv_dgrad(self, name, dz, nbr, y_in, dx):
-        """dx = d loss / d (pre-activation of the layer that produced y_in) of the 3^3 convolution `name`, dz its output
-        gradient: fused -- a gathered GEMM through the mirrored table, the (rows x 27*C_in) column gradient never exists --
-        or, with fused_gather off, the Linear data gradient + the mirrored column gather."""
-        lin = getattr(self, name)
-        cout, cin = lin.weight.shape[0], lin.weight.shape[1] // 27
-        if self.fused_gather and (27 * cout) % 32 == 0:
-            wt = lin.weight.data.view(cout, 27, cin).permute(2, 1, 0).reshape(cin, 27 * cout).contiguous()
-            g = self._saved["g"]
-            key = "mirror_" + name                              # (kept with the geometry: cached tables are mirrored once)
-            if key not in g:
-                g[key] = self._mirror(nbr)
-            return ops.sparse_conv_bwd_data(dz, g[key], wt, y_in, dx, self._act, self._zero(dz.device))
-        dcols = torch.empty(dz.shape[0], 27 * cin, device=dz.device)
-        ops.linear_bwd_data(dz, lin.weight.data, None, dcols, ops.ACT_NONE)
-        return ops.rows_gather_bwd(dcols, nbr, cin, dx, reverse=True, self_col=13, y_tanh=y_in)
+    def _conv_wgrad(self, name, dz, op, ws):
+        dW, db = self._g[name]
+        if ops.sparse_operand_form(self.fused_gather, op.K // op.C, op.C) == ops.MATERIALISED:
+            return ops.linear_bwd_weight(dz, op.cols, dW, db, ws)
+        K = op.idx.shape[1] * op.C
+        dW_p = dW if K == op.K else torch.empty(dW.shape[0], K, device=dz.device)
+        ops.sparse_conv_bwd_weight(dz, op.src, op.idx, op.C, dW_p, db, self._zero(dz.device), ws)
+        if K != op.K:
+            dW.copy_(dW_p[:, :op.K])
 
     def _lin(self, name, x, y):
         lin = getattr(self, name)
@@ -1017,38 +1027,37 @@ class SparseUNet(_HipNet):
         return y
 
     def _conv(self, name, src, idx, C, y, idx_pad=None):
-        """Sparse convolution `name` of the rows of `src` through the neighbour table `idx` (rows, J): fused -- the gather runs
-        inside the GEMM's LDS-DMA loader and the (rows x J*C) operand never reaches HBM -- when J*C is a multiple of the K-step
-        (every layer but conv0, whose 108-wide operand is small); returns the materialised operand or None."""
+        """Sparse convolution `name` of the rows of `src` through the table `idx` (rows, J) in the form sparse_operand_form picks ->
+        the layer's operand record.  idx_pad: `idx` at the PADDED form's width (geometry() builds level 0's); else widened here."""
         lin = getattr(self, name)
-        if self.fused_gather and (idx.shape[1] * C) % 32 == 0:
-            ops.sparse_conv_fwd(src, idx, C, lin.weight.data, lin.bias.data, y, self._act, self._zero(src.device))
-            return None
-        pad = (-idx.shape[1] * C) % 32
-        if self.fused_gather and pad % C == 0:
-            # conv0: 27 taps x 4 input channels = 108 columns; five absent taps (index -1 -> zero rows) and zero weight columns
-            # make it 128 = four K-steps, and the layer runs fused like the others.  Returns the padded table for the
-            # weight gradient (geometry() builds the level-0 table that wide: `idx_pad`).
-            idx_p = idx_pad if (idx_pad is not None and idx_pad.shape[1] == idx.shape[1] + pad // C) else \
-                torch.nn.functional.pad(idx, (0, pad // C), value=-1)
-            w_p = torch.zeros(lin.weight.shape[0], idx_p.shape[1] * C, device=src.device)
-            w_p[:, :lin.weight.shape[1]].copy_(lin.weight.data)
-            ops.sparse_conv_fwd(src, idx_p, C, w_p, lin.bias.data, y, self._act, self._zero(src.device))
-            return idx_p
-        cols = ops.rows_gather(src, idx, C, torch.empty(idx.shape[0], idx.shape[1] * C, device=src.device))
-        self._lin(name, cols, y)
-        return cols
+        J, K = idx.shape[1], lin.weight.shape[1]
+        if ops.sparse_operand_form(self.fused_gather, J, C) == ops.MATERIALISED:
+            cols = ops.rows_gather(src, idx, C, torch.empty(idx.shape[0], K, device=src.device))
+            self._lin(name, cols, y)
+            return _GatheredOperand(src, idx, C, cols, K)
+        Jp = J + ((-K) % 32) // C                               # whole absent taps fill the last K-step (FUSED: none)
+        if Jp != J:
+            idx = idx_pad if (idx_pad is not None and idx_pad.shape[1] == Jp) else torch.nn.functional.pad(idx, (0, Jp - J), value=-1)
+        ops.sparse_conv_fwd(src, idx, C, self._widened(lin.weight.data, Jp * C), lin.bias.data, y, self._act, self._zero(src.device))
+        return _GatheredOperand(src, idx, C, None, K)
 
-    def _conv_wgrad(self, name, dz, src, idx, C, cols, ws):
-        dW, db = self._g[name]
-        if cols is None:
-            ops.sparse_conv_bwd_weight(dz, src, idx, C, dW, db, self._zero(src.device), ws)
-        elif cols.dtype == torch.int32:                       # the padded table of a fused layer with a ragged K (conv0)
-            dW_p = torch.empty(dW.shape[0], cols.shape[1] * C, device=src.device)
-            ops.sparse_conv_bwd_weight(dz, src, cols, C, dW_p, db, self._zero(src.device), ws)
-            dW.copy_(dW_p[:, :dW.shape[1]])
-        else:
-            ops.linear_bwd_weight(dz, cols, dW, db, ws)
+    def _conv_dgrad(self, name, dz, op, nbr):
+        """d loss / d (pre-activation of the layer that produced op.src) of the 3^3 convolution `name` over its 27-wide table `nbr`:
+        a gathered GEMM through the mirrored table -- the (rows x 27*C_in) column gradient never exists -- or the Linear data
+        gradient + the mirrored column gather.  Mirrored: row r reads s as neighbour j  <=>  s reads r as neighbour 26 - j, so the
+        rows whose output used s are nbr[s].flip; a row that is nobody's neighbour (a duplicate coordinate: its centre tap points
+        at the canonical row) gets -1 everywhere and a gradient of exactly zero.  (Kept with the geometry: mirrored once.)"""
+        lin = getattr(self, name)
+        cout, cin = lin.weight.shape[0], op.C
+        dx = torch.empty_like(op.src)
+        if ops.sparse_dgrad_fused(self.fused_gather, cout):
+            wt = lin.weight.data.view(cout, 27, cin).permute(2, 1, 0).reshape(cin, 27 * cout).contiguous()
+            g = self._saved["g"]
+            if "mirror_" + name not in g:
+                g["mirror_" + name] = ops.voxel_mirror27(nbr)
+            return ops.sparse_conv_bwd_data(dz, g["mirror_" + name], wt, op.src, dx, self._act, self._zero(dz.device))
+        dcols = ops.linear_bwd_data(dz, lin.weight.data, None, torch.empty(dz.shape[0], 27 * cin, device=dz.device), ops.ACT_NONE)
+        return ops.rows_gather_bwd(dcols, nbr, cin, dx, reverse=True, self_col=13, y_tanh=op.src)
 
     def _zero(self, device):
         z = getattr(self, "_zero_row", None)
@@ -1077,11 +1086,6 @@ class SparseUNet(_HipNet):
         c0, c1, c2 = self.channels
         return self.fused_gather and c2 % c1 == 0 and c1 % c0 == 0 and (c2 + c1) % 32 == 0 and (c1 + c0) % 32 == 0
 
-    @staticmethod
-    def _vcat_table(parent, m, rows_hi):
-        """(rows, m + 1) gather table of a virtual [unpool | skip] operand: m chunks of the parent's row, then the row's own."""
-        return ops.voxel_vcat_table(parent.view(-1), m, rows_hi)
-
     # ---- geometry once per rollout (ppo.update): the tables depend on the coordinates only, and a sequential mini-batch is the
     # same slice of the rollout in every epoch and for both networks -- 10 forwards share one set of tables (and the two host
     # reads that size the strided levels happen once per mini-batch instead of once per forward)
@@ -1097,25 +1101,26 @@ class SparseUNet(_HipNet):
         k + 1 on a side stream under the GEMMs of mini-batch k -- the tables are latency-bound hash lookups, the GEMMs MFMA-bound)."""
         object.__setattr__(self, "_geom_ready", g)
 
-    def _hip_forward(self, x, out=None):
-        B, P = x.shape[0], self.point_num
-        c0, c1, c2 = self.channels
-        dev = x.device
-        nxt = getattr(self, "_geom_next", None)
-        object.__setattr__(self, "_geom_next", None)
-        ready = getattr(self, "_geom_ready", None)
+    def _tables(self, x):
+        """This forward's tables: handed over (take_geometry), cached for its slice (use_geometry; built on first use), or fresh."""
+        ready, nxt = getattr(self, "_geom_ready", None), getattr(self, "_geom_next", None)
         object.__setattr__(self, "_geom_ready", None)
+        object.__setattr__(self, "_geom_next", None)
         if ready is not None:
-            if ready["rows"][0] != B * P:
+            if ready["rows"][0] != x.shape[0] * self.point_num:
                 raise ValueError("take_geometry(): the tables were built for another batch size")
-            g = ready
-        elif nxt is not None and nxt[1][1] == B:
-            g = nxt[0].get(nxt[1])
-            if g is None:
-                g = nxt[0][nxt[1]] = self.geometry(x)
-        else:
-            g = self.geometry(x)
-        R0, R1, R2 = g["rows"]
+            return ready
+        if nxt is None or nxt[1][1] != x.shape[0]:
+            return self.geometry(x)
+        cache, rows = nxt
+        if rows not in cache:
+            cache[rows] = self.geometry(x)
+        return cache[rows]
+
+    def _hip_forward(self, x, out=None):
+        B, P, dev = x.shape[0], self.point_num, x.device
+        g = self._tables(x)
+        (c0, c1, c2), (R0, R1, R2) = self.channels, g["rows"]
         e = lambda r, c: torch.empty(r, c, device=dev)
         vcat = self._vcat_ok()
         if vcat:
@@ -1124,41 +1129,37 @@ class SparseUNet(_HipNet):
             comb0 = e(m0 * R1 + R0, c0)                         # [E1 as m0 rows of c0 per voxel | H0]
             H2, H1 = comb1[:m1 * R2].view(R2, c2), comb1[m1 * R2:]
             E1, H0 = comb0[:m0 * R1].view(R1, c1), comb0[m0 * R1:]
-            cat0 = cat1 = None
         else:
-            cat0 = e(R0, c1 + c0)                               # [unpool(E1) | H0]
-            H0 = cat0[:, c1:]
-            cat1 = e(R1, c2 + c1)                               # [unpool(H2) | H1]
-            H1 = cat1[:, c2:]
-            H2, E1 = e(R2, c2), e(R1, c1)
-        cols0 = self._conv("conv0", g["feat0"], g["nbr0"], 4, H0, idx_pad=g["nbr0p"])
+            comb0, comb1 = e(R0, c1 + c0), e(R1, c2 + c1)       # [unpool(E1) | H0] and [unpool(H2) | H1], materialised
+            H0, H1, H2, E1 = comb0[:, c1:], comb1[:, c2:], e(R2, c2), e(R1, c1)
+        op = {"conv0": self._conv("conv0", g["feat0"], g["nbr0"], 4, H0, idx_pad=g["nbr0p"])}
         D1 = e(R1, c1)
-        colsd0 = self._conv("down0", H0, g["l1"]["child"], c0, D1)
-        cols1 = self._conv("conv1", D1, g["nbr1"], c1, H1)
+        op["down0"] = self._conv("down0", H0, g["l1"]["child"], c0, D1)
+        op["conv1"] = self._conv("conv1", D1, g["nbr1"], c1, H1)
         D2 = e(R2, c2)
-        colsd1 = self._conv("down1", H1, g["l2"]["child"], c1, D2)
-        cols2 = self._conv("conv2", D2, g["nbr2"], c2, H2)
+        op["down1"] = self._conv("down1", H1, g["l2"]["child"], c1, D2)
+        op["conv2"] = self._conv("conv2", D2, g["nbr2"], c2, H2)
         E0 = e(R0, c0)
         if vcat:
+            # the virtual [unpool | skip] operands are FUSED layers over (rows, m + 1) tables: m chunks of the parent's row, the row's own
             if "up1_idx" not in g:
-                g["up1_idx"] = self._vcat_table(g["l2"]["parent"], m1, R2)
-                g["up0_idx"] = self._vcat_table(g["l1"]["parent"], m0, R1)
-            lin = self.up1
-            ops.sparse_conv_fwd(comb1, g["up1_idx"], c1, lin.weight.data, lin.bias.data, E1, self._act, self._zero(dev))
-            lin = self.up0
-            ops.sparse_conv_fwd(comb0, g["up0_idx"], c0, lin.weight.data, lin.bias.data, E0, self._act, self._zero(dev))
+                g["up1_idx"] = ops.voxel_vcat_table(g["l2"]["parent"].view(-1), m1, R2)
+                g["up0_idx"] = ops.voxel_vcat_table(g["l1"]["parent"].view(-1), m0, R1)
+            op["up1"] = self._conv("up1", comb1, g["up1_idx"], c1, E1)
+            op["up0"] = self._conv("up0", comb0, g["up0_idx"], c0, E0)
         else:
-            ops.rows_gather(H2, g["l2"]["parent"].view(-1, 1), c2, cat1[:, :c2])
-            self._lin("up1", cat1, E1)
-            ops.rows_gather(E1, g["l1"]["parent"].view(-1, 1), c1, cat0[:, :c1])
-            self._lin("up0", cat0, E0)
+            ops.rows_gather(H2, g["l2"]["parent"].view(-1, 1), c2, comb1[:, :c2])
+            self._lin("up1", comb1, E1)
+            ops.rows_gather(E1, g["l1"]["parent"].view(-1, 1), c1, comb0[:, :c1])
+            self._lin("up0", comb0, E0)
         fbuf = torch.empty(B, c0 + self.proprio_shape, device=dev)
         arg = ops.maxpool_rows(E0, B, P, fbuf[:, :c0])
         if self.proprio_shape != 0:
             fbuf[:, c0:].copy_(x[:, -self.proprio_shape:])
-        object.__setattr__(self, "_saved", dict(g=g, cols0=cols0, cat0=cat0, colsd0=colsd0, D1=D1, cols1=cols1, cat1=cat1,
-                                                colsd1=colsd1, D2=D2, cols2=cols2, H2=H2, E0=E0, arg=arg, B=B, vcat=vcat,
-                                                H0=H0, H1=H1, E1=E1, comb0=comb0 if vcat else None, comb1=comb1 if vcat else None))
+        # cols2: None exactly when conv2 ran FUSED on its own 27-wide table (bench.py prices the compact backward from it and `vcat`)
+        cols2 = {ops.FUSED: None, ops.PADDED: op["conv2"].idx, ops.MATERIALISED: op["conv2"].cols}[ops.sparse_operand_form(self.fused_gather, 27, c2)]
+        object.__setattr__(self, "_saved", dict(g=g, vcat=vcat, cols2=cols2, arg=arg, E0=E0, B=B, op=op, H2=H2, E1=E1,
+                                                comb1=comb1, comb0=comb0))
         return self._head.forward(fbuf, out)
 
     def _decoder_backward_compact(self, s, g, dfbuf, ws):
@@ -1179,10 +1180,8 @@ class SparseUNet(_HipNet):
         `parent`, which every row has.  They agree because a duplicate-coordinate row can never be a max-pool winner: its table
         entries are its canonical twin's (its own centre tap points at the twin), so its E0 row EQUALS the twin's bit for bit,
         and the max-pool takes the lowest row among equals -- the twin, which by construction has the lower row index.)"""
-        c0, c1, c2 = self.channels
-        P, B = self.point_num, s["B"]
-        dev = dfbuf.device
-        R0, R1, R2 = g["rows"]
+        (c0, c1, c2), (R0, R1, R2) = self.channels, g["rows"]
+        P, B, dev = self.point_num, s["B"], dfbuf.device
         W = lambda n: getattr(self, n).weight.data
         zero = self._zero(dev)
         e = lambda r, c: torch.empty(r, c, device=dev)
@@ -1211,80 +1210,81 @@ class SparseUNet(_HipNet):
         # level 2
         sum1 = ops.child_sum(dzE1, rank2, e(N, c1))
         dzH2c = ops.linear_bwd_data(sum1, W("up1")[:, :c2], sel(s["H2"], um2), e(N, c2), self._act)
-        ops.sparse_conv_bwd_weight(dzH2c, s["D2"], ops.table_rows(g["nbr2"], um2.view(-1)), c2, *self._g["conv2"], zero, ws)
+        D2 = s["op"]["conv2"].src
+        ops.sparse_conv_bwd_weight(dzH2c, D2, ops.table_rows(g["nbr2"], um2.view(-1)), c2, *self._g["conv2"], zero, ws)
         # conv2's data gradient: the column gradient of the B * c0 rows only ((rows x 27 c2) = dz W), then every level-2 row sums
         # the blocks of its neighbours THAT ARE among them (row -> compact row map; most taps miss) -- B * c0 x 27 c2 x c2 MACs
         # + a gather instead of the gathered GEMM over all of the level's rows
         dcols = ops.linear_bwd_data(dzH2c, W("conv2"), None, e(N, 27 * c2), ops.ACT_NONE)
-        dzD2 = ops.rows_gather_bwd(dcols, g["nbr2"], c2, torch.empty_like(s["D2"]), reverse=True, self_col=13, y_tanh=s["D2"],
+        dzD2 = ops.rows_gather_bwd(dcols, g["nbr2"], c2, torch.empty_like(D2), reverse=True, self_col=13, y_tanh=D2,
                                    rowmap=ops.rowmap_scatter(R2, u2.view(-1), R2))
-        return (skip0, ops.rowmap_scatter(R0, u0.view(-1), R0)), (skip1, ops.rowmap_scatter(R1, u1.view(-1), R1)), dzD2
+        skip = ((skip0, ops.rowmap_scatter(R0, u0.view(-1), R0)), (skip1, ops.rowmap_scatter(R1, u1.view(-1), R1)))
+        return _DecoderGrads(dzD2, (e(R0, c0), e(R1, c1)), skip, ops.ACC_OVERWRITE)
+
+    def _conv2_backward(self, s, g, dzH2, ws):
+        """conv2's weight and data gradient over all level-2 rows (the two dense decoder backwards) -> dzD2."""
+        self._conv_wgrad("conv2", dzH2, s["op"]["conv2"], ws)
+        return self._conv_dgrad("conv2", dzH2, s["op"]["conv2"], g["nbr2"])
+
+    def _decoder_backward_vcat(self, s, g, dfbuf, ws):
+        """The dense backward of the VIRTUAL concatenated operands (see _vcat_ok): weight gradients gather them again; the data
+        gradients are taken RAW (no activation derivative: nothing to read back) -- tanh' of the un-pooled half is applied after
+        the sum over a coarse row's children, tanh' of the skip half after the strided layer's contribution has been added.
+        The un-pooled half by linearity: sum_children (dz[child] W_u) = (sum_children dz[child]) W_u -- the children's gradient
+        rows are summed FIRST (c_out-wide rows, fixed order) and the GEMM runs on the coarse level's rows, so the (fine rows x
+        c_hi) block of the data gradient is never formed."""
+        (c0, c1, c2), (R0, R1, R2) = self.channels, g["rows"]
+        W = lambda n: getattr(self, n).weight.data
+        e = lambda r, c: torch.empty(r, c, device=dfbuf.device)
+        dzE0 = ops.maxpool_rows_bwd(dfbuf[:, :c0], s["arg"], self.point_num, y_tanh=s["E0"])       # pre-activation gradient of up0
+        self._conv_wgrad("up0", dzE0, s["op"]["up0"], ws)
+        sum0 = ops.rows_gather_bwd(dzE0, g["l1"]["child"], c0, e(R1, c0), mode=2)
+        dzE1 = ops.linear_bwd_data(sum0, W("up0")[:, :c1], s["E1"], e(R1, c1), self._act)
+        dzH0 = ops.linear_bwd_data(dzE0, W("up0")[:, c1:], None, e(R0, c0), ops.ACT_NONE)           # skip half, raw
+        self._conv_wgrad("up1", dzE1, s["op"]["up1"], ws)
+        sum1 = ops.rows_gather_bwd(dzE1, g["l2"]["child"], c1, e(R2, c1), mode=2)
+        dzH2 = ops.linear_bwd_data(sum1, W("up1")[:, :c2], s["H2"], e(R2, c2), self._act)
+        dzH1 = ops.linear_bwd_data(dzE1, W("up1")[:, c2:], None, e(R1, c1), ops.ACT_NONE)
+        return _DecoderGrads(self._conv2_backward(s, g, dzH2, ws), (dzH0, dzH1), (None, None), ops.ACC_RAW_SKIP)
+
+    def _decoder_backward_cat(self, s, g, dfbuf, ws):
+        """The dense backward of the MATERIALISED concatenated operands: tanh' of both halves is folded into the Linear data
+        gradients, so the skip halves arrive as finished pre-activation gradients."""
+        c0, c1, c2 = self.channels
+        W = lambda n: getattr(self, n).weight.data
+        cat0, cat1, e = s["comb0"], s["comb1"], lambda r, c: torch.empty(r, c, device=dfbuf.device)
+        dzE0 = ops.maxpool_rows_bwd(dfbuf[:, :c0], s["arg"], self.point_num, y_tanh=s["E0"])
+        ops.linear_bwd_weight(dzE0, cat0, *self._g["up0"], ws)
+        dcat0 = ops.linear_bwd_data(dzE0, W("up0"), cat0, torch.empty_like(cat0), self._act)
+        dzE1 = ops.rows_gather_bwd(dcat0[:, :c1], g["l1"]["child"], c1, e(g["rows"][1], c1), mode=2)
+        ops.linear_bwd_weight(dzE1, cat1, *self._g["up1"], ws)
+        dcat1 = ops.linear_bwd_data(dzE1, W("up1"), cat1, torch.empty_like(cat1), self._act)
+        dzH2 = ops.rows_gather_bwd(dcat1[:, :c2], g["l2"]["child"], c2, e(g["rows"][2], c2), mode=2)
+        return _DecoderGrads(self._conv2_backward(s, g, dzH2, ws), (dcat0[:, c1:], dcat1[:, c2:]), (None, None), ops.ACC_ADD)
+
+    def _level_backward(self, l, dzD, dzH, skip, acc, ws):
+        """Backward of strided level l (1, then 0): down<l>'s weight gradient and its data gradient into 8 * c columns, gathered
+        back onto the level's rows through parent_canon / slot and joined with the skip gradient in dzH as `acc` says (`skip`: the
+        compact form's sparse one), then conv<l>'s weight gradient and -- above level 0, whose input is data -- its data gradient."""
+        g, tabs = self._saved["g"], self._saved["g"][f"l{l + 1}"]
+        down, conv = self._saved["op"][f"down{l}"], self._saved["op"][f"conv{l}"]
+        self._conv_wgrad(f"down{l}", dzD, down, ws)
+        dcols = ops.linear_bwd_data(dzD, getattr(self, f"down{l}").weight.data, None, dzD.new_empty(dzD.shape[0], 8 * down.C), ops.ACT_NONE)
+        ops.rows_gather_bwd(dcols, tabs["parent_canon"].view(-1, 1), down.C, dzH, tslot=tabs["slot"].view(-1, 1), mode=1,
+                            y_tanh=down.src, accumulate=acc, skip=skip)
+        self._conv_wgrad(f"conv{l}", dzH, conv, ws)
+        return self._conv_dgrad(f"conv{l}", dzH, conv, g[f"nbr{l}"]) if l > 0 else None
 
     def _hip_backward(self, dy):
-        s, g = self._saved, self._saved["g"]
-        c0, c1, c2 = self.channels
-        P, B = self.point_num, s["B"]
+        s, g, c0 = self._saved, self._saved["g"], self.channels[0]
         ws = self._workspace(dy.device)
-        W = lambda n: getattr(self, n).weight.data
-        dfbuf = torch.empty(B, c0 + self.proprio_shape, device=dy.device)
+        dfbuf = torch.empty(s["B"], c0 + self.proprio_shape, device=dy.device)
         self._head.backward(dy, ws, dx_out=dfbuf)
-        H0, H1 = s["H0"], s["H1"]
-        compact = self.sparse_top and s["vcat"] and s["cols2"] is None and c0 <= 64
-        skip0 = skip1 = None
-        if compact:
-            skip0, skip1, dzD2 = self._decoder_backward_compact(s, g, dfbuf, ws)
-            dzH0, dzH1 = torch.empty(g["rows"][0], c0, device=dy.device), torch.empty(g["rows"][1], c1, device=dy.device)
-            acc_mode = False
-        else:
-            dzE0 = ops.maxpool_rows_bwd(dfbuf[:, :c0], s["arg"], P, y_tanh=s["E0"])        # pre-activation gradient of up0
-        if compact:
-            pass
-        elif s["vcat"]:
-            # the concatenated operands are virtual (see _vcat_ok): weight gradients gather them again; the data gradients are
-            # taken RAW (no activation derivative: nothing to read back) -- tanh' of the un-pooled half is applied after the sum
-            # over a coarse row's children, tanh' of the skip half after the strided layer's contribution has been added
-            # The un-pooled half by linearity: sum_children (dz[child] W_u) = (sum_children dz[child]) W_u -- the children's
-            # gradient rows are summed FIRST (c_out-wide rows, fixed order) and the GEMM runs on the coarse level's rows, so
-            # the (fine rows x c_hi) block of the data gradient is never formed.
-            zero = self._zero(dy.device)
-            e = lambda r, c: torch.empty(r, c, device=dy.device)
-            ops.sparse_conv_bwd_weight(dzE0, s["comb0"], g["up0_idx"], c0, *self._g["up0"], zero, ws)
-            sum0 = ops.rows_gather_bwd(dzE0, g["l1"]["child"], c0, e(s["D1"].shape[0], c0), mode=2)
-            dzE1 = ops.linear_bwd_data(sum0, W("up0")[:, :c1], s["E1"], e(s["D1"].shape[0], c1), self._act)
-            dzH0 = ops.linear_bwd_data(dzE0, W("up0")[:, c1:], None, e(dzE0.shape[0], c0), ops.ACT_NONE)      # skip half, raw
-            ops.sparse_conv_bwd_weight(dzE1, s["comb1"], g["up1_idx"], c1, *self._g["up1"], zero, ws)
-            sum1 = ops.rows_gather_bwd(dzE1, g["l2"]["child"], c1, e(s["D2"].shape[0], c1), mode=2)
-            dzH2 = ops.linear_bwd_data(sum1, W("up1")[:, :c2], s["H2"], e(s["D2"].shape[0], c2), self._act)
-            dzH1 = ops.linear_bwd_data(dzE1, W("up1")[:, c2:], None, e(dzE1.shape[0], c1), ops.ACT_NONE)
-            acc_mode = 2                                                                    # (skip + strided) * tanh'
-        else:
-            cat0, cat1 = s["cat0"], s["cat1"]
-            ops.linear_bwd_weight(dzE0, cat0, *self._g["up0"], ws)
-            dcat0 = torch.empty_like(cat0)
-            ops.linear_bwd_data(dzE0, W("up0"), cat0, dcat0, self._act)                    # tanh' of both halves folded in
-            dzE1 = ops.rows_gather_bwd(dcat0[:, :c1], g["l1"]["child"], c1, torch.empty_like(s["D1"]), mode=2)
-            ops.linear_bwd_weight(dzE1, cat1, *self._g["up1"], ws)
-            dcat1 = torch.empty_like(cat1)
-            ops.linear_bwd_data(dzE1, W("up1"), cat1, dcat1, self._act)
-            dzH2 = ops.rows_gather_bwd(dcat1[:, :c2], g["l2"]["child"], c2, torch.empty_like(s["D2"]), mode=2)
-            dzH1, dzH0 = dcat1[:, c2:], dcat0[:, c1:]
-            acc_mode = True                                                                 # skip part already pre-activation
-        if not compact:
-            self._conv_wgrad("conv2", dzH2, s["D2"], g["nbr2"], c2, s["cols2"], ws)
-            dzD2 = self._conv_dgrad("conv2", dzH2, g["nbr2"], s["D2"], torch.empty_like(s["D2"]))
-        self._conv_wgrad("down1", dzD2, H1, g["l2"]["child"], c1, s["colsd1"], ws)
-        dcolsd1 = torch.empty(dzD2.shape[0], 8 * c1, device=dy.device)
-        ops.linear_bwd_data(dzD2, W("down1"), None, dcolsd1, ops.ACT_NONE)
-        ops.rows_gather_bwd(dcolsd1, g["l2"]["parent_canon"].view(-1, 1), c1, dzH1, tslot=g["l2"]["slot"].view(-1, 1), mode=1,
-                            y_tanh=H1, accumulate=acc_mode, skip=skip1)
-        self._conv_wgrad("conv1", dzH1, s["D1"], g["nbr1"], c1, s["cols1"], ws)
-        dzD1 = self._conv_dgrad("conv1", dzH1, g["nbr1"], s["D1"], torch.empty_like(s["D1"]))
-        self._conv_wgrad("down0", dzD1, H0, g["l1"]["child"], c0, s["colsd0"], ws)
-        dcolsd0 = torch.empty(dzD1.shape[0], 8 * c0, device=dy.device)
-        ops.linear_bwd_data(dzD1, W("down0"), None, dcolsd0, ops.ACT_NONE)
-        ops.rows_gather_bwd(dcolsd0, g["l1"]["parent_canon"].view(-1, 1), c0, dzH0, tslot=g["l1"]["slot"].view(-1, 1), mode=1,
-                            y_tanh=H0, accumulate=acc_mode, skip=skip0)
-        self._conv_wgrad("conv0", dzH0, g["feat0"], g["nbr0"], 4, s["cols0"], ws)           # the input features are data
+        compact = self.sparse_top and s["vcat"] and s["cols2"] is None and c0 <= 64       # (c0: the 64 slots of pm_rows_uniq_i32)
+        form = self._decoder_backward_compact if compact else self._decoder_backward_vcat if s["vcat"] else self._decoder_backward_cat
+        d = form(s, g, dfbuf, ws)
+        dzD1 = self._level_backward(1, d.dzD2, d.dzH[1], d.skip[1], d.acc, ws)
+        self._level_backward(0, dzD1, d.dzH[0], d.skip[0], d.acc, ws)
 
 
 class _ConvEncoder(nn.Module):

@@ -1131,6 +1131,23 @@ def rows_gather(src, idx, C, dst):
     return dst
 
 
+# How a gathered layer (a (rows, J) table over rows of C channels) feeds its GEMM: ONE decision, for the forward, the weight gradient
+# and the tests.  FUSED: the GEMM's LDS-DMA loader gathers, the (rows x J*C) operand never reaches HBM (J*C is whole K-steps of 32).
+# PADDED: the same on a table widened by absent taps (index -1 -> zero rows) against zero weight columns, where the missing columns
+# are whole taps (27 taps x 4 channels = 108 columns -> 32 taps).  MATERIALISED: rows_gather writes the operand for the Linear kernels.
+FUSED, PADDED, MATERIALISED = "fused", "padded", "materialised"
+
+
+def sparse_operand_form(fused_gather, J, C):
+    if not fused_gather or ((-J * C) % 32) % C != 0:
+        return MATERIALISED
+    return FUSED if (J * C) % 32 == 0 else PADDED
+
+
+def sparse_dgrad_fused(fused_gather, cout):   # the data gradient of a 3^3 convolution is another GEMM shape: K = 27 * C_out
+    return fused_gather and (27 * cout) % 32 == 0
+
+
 def sparse_conv_fwd(src, idx, C, w, b, y, act, zero):
     """y = act(gather(src, idx) @ w.T + b) with the gather inside the GEMM loader (J*C % 32 == 0)."""
     _req(src, idx, w, b, y, zero)
@@ -1176,9 +1193,16 @@ def sparse_conv_bwd_weight(dy, src, idx, C, dw, db, zero, ws):
           "pm_sparse_conv_bwd_weight_f32")
 
 
-def rows_gather_bwd(dcols, tidx, C, dsrc, tslot=None, mode=0, reverse=False, self_col=-1, y_tanh=None, accumulate=False, rowmap=None,
+# `accumulate` of rows_gather_bwd (pm_rows_gather_bwd_f32): what dsrc holds when the call starts
+ACC_OVERWRITE = 0         # nothing: dsrc is overwritten
+ACC_ADD = 1               # a finished gradient: the (already multiplied) result is added to it
+ACC_RAW_SKIP = 2          # a RAW contribution, added to the gathered sum BEFORE the activation derivative: (skip + strided) * act'
+
+
+def rows_gather_bwd(dcols, tidx, C, dsrc, tslot=None, mode=0, reverse=False, self_col=-1, y_tanh=None, accumulate=ACC_OVERWRITE, rowmap=None,
                     skip=None):
-    """rowmap (int32, one entry per row the table can name): dcols holds a subset of those rows -- rowmap[row] = its row in dcols or -1.
+    """accumulate: ACC_OVERWRITE, ACC_ADD or ACC_RAW_SKIP (above).
+    rowmap (int32, one entry per row the table can name): dcols holds a subset of those rows -- rowmap[row] = its row in dcols or -1.
     skip = (values (N, C), skipmap (rows) int32): a sparse raw contribution added before the activation derivative (dsrc is overwritten)."""
     _req(dcols, tidx, dsrc, tslot, y_tanh, rowmap)
     rows = tidx.shape[0]

@@ -43,7 +43,13 @@ def test_geometry_tables_equal_the_restatement(dups):
 NET_WIDE = dict(NET, channels=[32, 64, 64])        # every layer but conv0 has J*C % 32 == 0: all gathers fused into the GEMM loader
 
 
-@pytest.mark.parametrize("proprio,dups,NET", [(0, False, NET), (5, True, NET), (0, True, NET_WIDE), (3, False, dict(NET_WIDE, fused_gather=False))])
+# conv1 has 27 x 12 = 324 columns and the 28 missing ones are no whole taps of 12: the one layer that materialises its operand (and
+# its data gradient) inside an otherwise fused network
+NET_MIXED = dict(NET, channels=[16, 12, 32])
+
+
+@pytest.mark.parametrize("proprio,dups,NET", [(0, False, NET), (5, True, NET), (0, True, NET_WIDE), (3, False, dict(NET_WIDE, fused_gather=False)),
+                                              (0, True, NET_MIXED)])
 def test_forward_and_parameter_gradients_match_the_restatement(proprio, dups, NET):
     from partmanip_amd.algo_utils import ActorCritic
     from partmanip_amd.autograd import backbone_apply
@@ -220,6 +226,103 @@ def test_compact_decoder_backward_equals_the_dense_one(net, monkeypatch):
         (backbone_apply(ac.actor, x) * w).sum().backward()
         gs.append([p_.grad.clone() for p_ in ac.actor.parameters()])
     assert all(torch.equal(a, b) for a, b in zip(*gs))
+
+
+def _forward_backward(net, B, seed, sparse_top=None):
+    """One forward + backward of a fresh actor on duplicate-voxel clouds -> (actor, clouds, output, parameter gradients by name)."""
+    from partmanip_amd.algo_utils import ActorCritic
+    from partmanip_amd.autograd import backbone_apply
+    P, Rg, A = net["point_num"], net["grid"], 4
+    ac = ActorCritic(4 * P, A, _model(net)).to(DEV)
+    ac.load_state_dict({k: t(v.copy()) for k, v in cases.actor_critic_state(net, 4 * P, A, 0.5, seed).items()})
+    ac.flat()
+    if sparse_top is not None:
+        ac.actor.sparse_top = sparse_top                       # (read at step time)
+    x = t(cases.sparse_clouds(B, P, Rg, 16, n_distinct=75, pad_tail=4)).to(DEV)
+    w = torch.randn(B, A, device=DEV, generator=torch.Generator(device=DEV).manual_seed(6))
+    out = backbone_apply(ac.actor, x)
+    (out * w).sum().backward()
+    return ac.actor, x, out.detach().clone(), {n: p.grad.clone() for n, p in ac.actor.named_parameters()}
+
+
+def _count_ops(monkeypatch, run):
+    """Calls per public `partmanip_amd.ops` function (every one is wrapped, so a path that starts calling another one shows) in run();
+    `check` and the two host-side criteria launch nothing and are left out."""
+    import collections
+    import inspect
+    from partmanip_amd import ops
+    counts = collections.Counter()
+
+    def wrap(name, fn):
+        def call(*a, **k):
+            counts[name] += 1
+            return fn(*a, **k)
+        return call
+    with monkeypatch.context() as m:
+        for name, fn in inspect.getmembers(ops, inspect.isfunction):
+            if fn.__module__ == ops.__name__ and not name.startswith("_") and name not in ("check", "sparse_operand_form", "sparse_dgrad_fused"):
+                m.setattr(ops, name, wrap(name, fn))
+        run()
+    return dict(counts)
+
+
+# Which operand path every layer takes, as launches per `ops` function in one forward + backward (tables included).  The counts were
+# RECORDED ON THE PARENT COMMIT of the host-path refactor with _count_ops above, not derived from the code under test: a layer that
+# quietly falls back to the materialised operand keeps every numeric test green (and writes an 18.5 GB matrix at 2048 clouds) but
+# moves rows_gather / linear_fwd / linear_bwd_weight here.
+_PATHS = {
+    # conv0 and conv1 on padded tables, conv1's data gradient materialised, materialised decoder
+    "ragged": (NET, None,
+        dict(linear_bwd_data=8, linear_bwd_weight=5, linear_fwd=5, maxpool_rows=1, maxpool_rows_bwd=1, rows_gather=2,
+             rows_gather_bwd=5, sparse_conv_bwd_data=1, sparse_conv_bwd_weight=5, sparse_conv_fwd=5, voxel_down=2,
+             voxel_grid0=1, voxel_mirror27=1, voxel_nbr27=3)),
+    "wide, compact decoder backward": (NET_WIDE, True,
+        dict(child_sum=2, linear_bwd_data=10, linear_bwd_weight=3, linear_fwd=3, maxpool_rows=1, maxpool_rows_bwd=1,
+             rowmap_scatter=3, rows_gather=3, rows_gather_bwd=3, rows_uniq=3, sparse_conv_bwd_data=1,
+             sparse_conv_bwd_weight=7, sparse_conv_fwd=7, table_rows=3, voxel_down=2, voxel_grid0=1, voxel_mirror27=1,
+             voxel_nbr27=3, voxel_vcat_table=2)),
+    "wide, virtual-concat decoder backward": (NET_WIDE, False,
+        dict(linear_bwd_data=9, linear_bwd_weight=3, linear_fwd=3, maxpool_rows=1, maxpool_rows_bwd=1, rows_gather_bwd=4,
+             sparse_conv_bwd_data=2, sparse_conv_bwd_weight=7, sparse_conv_fwd=7, voxel_down=2, voxel_grid0=1,
+             voxel_mirror27=2, voxel_nbr27=3, voxel_vcat_table=2)),
+    "wide, every operand materialised": (dict(NET_WIDE, fused_gather=False), None,
+        dict(linear_bwd_data=9, linear_bwd_weight=10, linear_fwd=10, maxpool_rows=1, maxpool_rows_bwd=1, rows_gather=7,
+             rows_gather_bwd=6, voxel_down=2, voxel_grid0=1, voxel_nbr27=3)),
+    # conv1 (324 columns) materialises inside a fused network
+    "mixed": (NET_MIXED, None,
+        dict(linear_bwd_data=8, linear_bwd_weight=6, linear_fwd=6, maxpool_rows=1, maxpool_rows_bwd=1, rows_gather=3,
+             rows_gather_bwd=5, sparse_conv_bwd_data=1, sparse_conv_bwd_weight=4, sparse_conv_fwd=4, voxel_down=2,
+             voxel_grid0=1, voxel_mirror27=1, voxel_nbr27=3)),
+}
+
+
+@pytest.mark.parametrize("case", list(_PATHS))
+def test_path_matrix_launch_counts_are_the_recorded_ones(case, monkeypatch):
+    net, sparse_top, want = _PATHS[case]
+    got = _count_ops(monkeypatch, lambda: _forward_backward(net, 5, 48, sparse_top))
+    print(case, sorted(got.items()))
+    assert got == want
+
+
+def test_more_than_64_channels_at_level_0_turn_the_compact_backward_off():
+    """The virtual concat holds for channels 96 / 96 / 96, but c0 exceeds the 64 slots per cloud of pm_rows_uniq_i32: `sparse_top` on
+    and off run the same (virtual-concat) backward, so nothing may differ by a bit."""
+    net = dict(NET, channels=[96, 96, 96])
+    (_, _, out1, g1), (_, _, out0, g0) = (_forward_backward(net, 5, 49, top) for top in (True, False))
+    assert torch.equal(out1, out0)
+    for n in g1:
+        assert torch.equal(g1[n], g0[n]), n
+
+
+def test_take_geometry_refuses_tables_built_for_another_batch_size():
+    actor, x, _, _ = _forward_backward(NET, 5, 50)
+    want = actor(x)
+    actor.take_geometry(actor.geometry(x[:3]))
+    with pytest.raises(ValueError, match="another batch size"):
+        actor(x)
+    assert torch.equal(actor(x), want)                          # nothing pending any more: the forward builds its own tables
+    actor.take_geometry(actor.geometry(x))
+    assert torch.equal(actor(x), want)
 
 
 # =========================================================================================================== cfg 5 at its own size

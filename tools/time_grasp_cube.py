@@ -183,7 +183,8 @@ def main():
                          torch_ms={k: round(v, 5) for k, v in mean["torch"].items()},
                          speedup={k: round(mean["torch"][k] / mean["hip"][k], 2) for k in mean["hip"]}, launches=launches,
                          bytes_per_step={k: per_env[k] * N for k in per_env}, floor_ms={k: round(v, 7) for k, v in floor.items()},
-                         share_of_bytes_floor={k: round(floor[k] / mean["hip"][k], 5) for k in floor},
+                         # (three significant digits: at --tiny's N = 4 the share is ~5e-6, which five decimals round to 0 or 1e-5)
+                         share_of_bytes_floor={k: float(f"{floor[k] / mean['hip'][k]:.3g}") for k in floor},
                          hip_ms_rounds={k: [round(x, 5) for x in v] for k, v in ms["hip"].items()},
                          torch_ms_rounds={k: [round(x, 5) for x in v] for k, v in ms["torch"].items()}, calls=3 * calls,
                          max_abs_diff_hip_vs_torch=dict(end_step=diff, begin_step=diff_ctl), flags_equal=flags_equal))
