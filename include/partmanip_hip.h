@@ -257,6 +257,14 @@ int pm_pointnet_enc_bwd_f32(const float* x, long ldx, int B, int P, int C, int s
                             float* db1, float* dW2, float* db2, float* dW3, float* db3,
                             const float* h2_saved /* NULL = recompute layer 2; else what the forward saved */,
                             int act /* as the forward's */, void* workspace, size_t workspace_bytes, void* stream);
+/* The same call pinned to the 4-wave kernel: pm_pointnet_enc_bwd_f32 runs a saved layer 2 on the 16-wave kernel and only the
+ * recomputing backward on the 4-wave one; this entry runs the 4-wave kernel for both (same arguments, same results class), so its
+ * saved-layer-2 form stays tested.  PM_ABI_VERSION stays 163 with this addition (no existing signature changed). */
+int pm_pointnet_enc_bwd_w4_f32(const float* x, long ldx, int B, int P, int C, int sub_mean, const float* W1,
+                               const float* b1, const float* b2, const float* W3, const float* packed,
+                               int max_mean, const float* dfeat, long ldf, const int32_t* argmax, float* dW1,
+                               float* db1, float* dW2, float* db2, float* dW3, float* db3, const float* h2_saved,
+                               int act, void* workspace, size_t workspace_bytes, void* stream);
 /* OPT-IN fp32-class split-bf16 form of the same call (csrc/pointnet_enc_bwd_bf6.h): the two dense GEMMs of the backward
  * (dW2 = dz2^T h1, dh1 = dz2 W2) run on bf16 MFMAs with every operand split into three bf16 planes and six products summed in
  * the fp32 accumulator -- the fp32 kernel's error level at 2.7x less matrix-pipe time; everything else is the fp32 code.  tanh

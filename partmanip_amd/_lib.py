@@ -60,6 +60,7 @@ SIGNATURES = {
     "pm_pointnet_enc_fwd_bf6": (I, [P, L, I, I, I, I, P, P, P, P, P, I, P, L, P, P, P]),
     "pm_pointnet_enc_bwd_workspace_bytes": (Z, [I, I, I]),
     "pm_pointnet_enc_bwd_f32": (I, [P, L, I, I, I, I, P, P, P, P, P, I, P, L, P, P, P, P, P, P, P, P, I, P, Z, P]),
+    "pm_pointnet_enc_bwd_w4_f32": (I, [P, L, I, I, I, I, P, P, P, P, P, I, P, L, P, P, P, P, P, P, P, P, I, P, Z, P]),
     "pm_pointnet_packed_bwd_bf6_bytes": (Z, []),
     "pm_pointnet_pack_weights_bwd_bf6": (I, [P, P, P]),
     "pm_pointnet_enc_bwd_bf6": (I, [P, L, I, I, I, I, P, P, P, P, P, P, I, P, L, P, P, P, P, P, P, P, P, P, Z, P]),

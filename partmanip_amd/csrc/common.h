@@ -154,7 +154,7 @@ __device__ __forceinline__ f32x2 pm_tanh2(float a, float b) { return pm_tanh2((f
 __device__ __forceinline__ float pm_act(float z, int act) {
     switch (act) {
         case PM_ACT_TANH: return pm_tanh(z);
-        case PM_ACT_RELU: return fmaxf(z, 0.0f);
+        case PM_ACT_RELU: return z != z ? z : fmaxf(z, 0.0f);      // fmaxf alone returns 0 for a NaN; torch.relu returns the NaN
         case PM_ACT_LRELU: return z > 0.0f ? z : 0.01f * z;
         case PM_ACT_ELU: return z > 0.0f ? z : expm1f(z);
         case PM_ACT_SELU: return PM_SELU_L * (z > 0.0f ? z : PM_SELU_A * expm1f(z));

@@ -1306,7 +1306,7 @@ static int pn_enc_bwd_impl(const float* x, long ldx, int B, int P, int C, int su
                            const float* packed, int max_mean, const float* dfeat, long ldf,
                            const int32_t* argmax, float* dW1, float* db1, float* dW2, float* db2,
                            float* dW3, float* db3, const float* h2_saved, int act, void* workspace,
-                           size_t workspace_bytes, void* stream, const unsigned short* packW2_bf6) {
+                           size_t workspace_bytes, void* stream, const unsigned short* packW2_bf6, int four_wave = 0) {
     PM_REQUIRE(x && W1 && b1 && b2 && W3 && packed && dfeat && argmax && dW1 && db1 && dW2 && db2 && dW3 && db3);
     PM_REQUIRE(act > PM_ACT_NONE && act <= PM_ACT_MAX);
     // the split-bf16 kernel is the saved-layer-2, tanh form only: anything else is refused, not silently run in fp32
@@ -1348,7 +1348,7 @@ static int pn_enc_bwd_impl(const float* x, long ldx, int B, int P, int C, int su
         else if (C == 4) PN_BF6_LAUNCH(4);
         else PN_BF6_LAUNCH(0);
 #undef PN_BF6_LAUNCH
-    } else if (PN_BWD16 && h2_saved) {            // saved layer 2: one 16-wave work-group per CU
+    } else if (PN_BWD16 && h2_saved && !four_wave) {   // saved layer 2: one 16-wave work-group per CU
         const int ncu = pn_cu_count();
         G = B < ncu ? B : ncu;
         int32_t* keys_g = (int32_t*)(ws + w.off_keys);
@@ -1418,6 +1418,18 @@ extern "C" int pm_pointnet_enc_bwd_f32(const float* x, long ldx, int B, int P, i
                                        size_t workspace_bytes, void* stream) {
     return pn_enc_bwd_impl(x, ldx, B, P, C, sub_mean, W1, b1, b2, W3, packed, max_mean, dfeat, ldf, argmax, dW1, db1, dW2, db2,
                            dW3, db3, h2_saved, act, workspace, workspace_bytes, stream, nullptr);
+}
+
+// the same call on the 4-wave kernel (pn_bwd_kernel) whether or not h2_saved is given: with PN_BWD16 == 1 the entry above sends a
+// saved layer 2 to pn_bwd16_kernel, and pn_bwd_kernel<CT, true, *> -- what a PN_BWD16 == 0 build runs -- would go untested
+extern "C" int pm_pointnet_enc_bwd_w4_f32(const float* x, long ldx, int B, int P, int C, int sub_mean,
+                                          const float* W1, const float* b1, const float* b2, const float* W3,
+                                          const float* packed, int max_mean, const float* dfeat, long ldf,
+                                          const int32_t* argmax, float* dW1, float* db1, float* dW2, float* db2,
+                                          float* dW3, float* db3, const float* h2_saved, int act, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    return pn_enc_bwd_impl(x, ldx, B, P, C, sub_mean, W1, b1, b2, W3, packed, max_mean, dfeat, ldf, argmax, dW1, db1, dW2, db2,
+                           dW3, db3, h2_saved, act, workspace, workspace_bytes, stream, nullptr, 1);
 }
 
 // the same call with dW2 / dh1 on split-bf16 MFMAs (three planes, six products: pointnet_enc_bwd_bf6.h); tanh, saved layer 2

@@ -519,19 +519,19 @@ def pointnet_enc_fwd_bf6(x, P, Cc, sub_mean, w1, b1, b2, b3, packed, max_mean, f
 
 
 def pointnet_enc_bwd(x, P, Cc, sub_mean, w1, b1, b2, w3, packed, max_mean, dfeat, argmax, dw1, db1, dw2, db2, dw3, db3,
-                     ws, h2_saved=None, act=None):
+                     ws, h2_saved=None, act=None, four_wave=False):
+    """four_wave: run the 4-wave kernel also when h2_saved is given (pm_pointnet_enc_bwd_w4_f32; the default entry sends a saved
+    layer 2 to the 16-wave kernel)."""
     _req(x, w1, b1, b2, w3, packed, dfeat, argmax, dw1, db1, dw2, db2, dw3, db3, h2_saved)
+    fn, name = (lib.pm_pointnet_enc_bwd_w4_f32, "pm_pointnet_enc_bwd_w4_f32") if four_wave else (lib.pm_pointnet_enc_bwd_f32, "pm_pointnet_enc_bwd_f32")
     B = x.shape[0]
     w = ws.get(lib.pm_pointnet_enc_bwd_workspace_bytes(B, P, Cc) + 256)
     base = w.data_ptr()
     al = (-base) % 256
     with TIMER.bracket("pointnet_enc_bwd"):
-        check(lib.pm_pointnet_enc_bwd_f32(_ptr(x), _rows(x, "x"), B, P, Cc, int(sub_mean), _ptr(w1), _ptr(b1), _ptr(b2),
-                                          _ptr(w3), _ptr(packed), int(max_mean), _ptr(dfeat), _rows(dfeat, "dfeat"),
-                                          _ptr(argmax), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(dw3),
-                                          _ptr(db3), _ptr(h2_saved), int(ACT_TANH if act is None else act), base + al,
-                                          w.numel() - al, _stream()),
-              "pm_pointnet_enc_bwd_f32")
+        check(fn(_ptr(x), _rows(x, "x"), B, P, Cc, int(sub_mean), _ptr(w1), _ptr(b1), _ptr(b2), _ptr(w3), _ptr(packed), int(max_mean),
+                 _ptr(dfeat), _rows(dfeat, "dfeat"), _ptr(argmax), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(dw3), _ptr(db3),
+                 _ptr(h2_saved), int(ACT_TANH if act is None else act), base + al, w.numel() - al, _stream()), name)
 
 
 def pointnet_pack_bwd_bf6(w2, packed):
