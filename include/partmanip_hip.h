@@ -51,7 +51,7 @@ extern "C" {
 #define PM_ACT_MAX 6
 
 /* ABI version: major*10000 + minor*100 + patch */
-#define PM_ABI_VERSION 163 /* bumped whenever an entry point is added or a signature changes */
+#define PM_ABI_VERSION 163 /* bumped whenever a signature changes; additions that change none keep it */
 int pm_version(void);      /* returns PM_ABI_VERSION of the built library: loaders compare it with their header */
 
 /* ------------------------------------------------------------------ K1  GAE return scan
@@ -1193,6 +1193,53 @@ int pm_rowmap_scatter_i32(int32_t* map, long n, const int32_t* ids, long N, int 
 int pm_table_rows_i32(const int32_t* table, long ldt, int J, const int32_t* sel, long N, int32_t* out, void* stream);
 int pm_voxel_vcat_table_i32(const int32_t* parent, long rows, int m, long rows_hi, int32_t* out, void* stream);
 int pm_exclusive_scan_i32(const int32_t* counts, int n, int32_t* base, int32_t* total, void* stream);
+
+/* ------------------------------------------------------------------ 2-D residual network building blocks
+ * `network.name: depthResNet` (reference network.py:237-271: a ResNet-34 on the 1 x 72 x 128 depth image).  Its convolutions
+ * are the gathered GEMMs above over host-built 2-D patch tables; these are the layers between them.  Every activation is a
+ * channels-last matrix (rows = b*H*W, C) with a row stride ld >= C in elements; C % 4 == 0, C <= 1024, pointers 16-byte aligned,
+ * strides multiples of 4.  No atomics: every sum has a fixed order that depends on (rows, C) only, so two runs give the same bits.
+ *
+ *   pm_bn2d_stats_f32: per channel over the rows, mean, biased variance (var may be NULL) and invstd = 1/sqrt(var + eps).  The
+ *     sums are taken in fp64 about the channel's first row (a depth image holds 100.0 beside values near 1: E[x^2] - E[x]^2 in
+ *     fp32 loses the variance); a constant channel gives variance exactly 0.  running_mean / running_var (NULL: untouched) become
+ *     (1 - momentum) * running + momentum * batch with the unbiased variance var * n / (n - 1); num_batches_tracked (one int64,
+ *     NULL: untouched) is incremented.  rows < 2 -> PM_EINVAL (torch.nn.BatchNorm2d refuses the same case in training).
+ *     Workspace (8-byte aligned): pm_bn2d_workspace_bytes(rows, C), also what pm_bn2d_bwd_f32 needs.
+ *   pm_bn2d_apply_f32: y = gamma * (x - mean) * invstd + beta [+ residual] [then ReLU], one pass; NaN propagates.  Inference: hand
+ *     it running_mean and 1/sqrt(running_var + eps).
+ *   pm_bn2d_bwd_f32: with dy_m = (dy [+ dy2]) [masked by y > 0 when relu], xhat = (x - mean) * invstd, n = rows:
+ *       dbeta = sum dy_m, dgamma = sum dy_m * xhat (fp64 sums), dx = gamma * invstd * (dy_m - dbeta / n - xhat * dgamma / n);
+ *     dy_masked (NULL: not wanted) receives dy_m for the residual branch.  dy2 (NULL: none) is a second gradient of the same
+ *     output (a block's input feeds its first convolution and its shortcut).  y is the layer's OUTPUT (read only when relu).
+ *     Three launches: partial sums, their fixed-order total, the apply pass.
+ *   pm_pool2d_max3s2_*: 3 x 3 max pool, stride 2, padding 1 over (B, H, W, C) -> (B, Ho, Wo, C), Ho = pm_pool2d_out(H).  idx
+ *     (B*Ho*Wo, C) int32 = ih * W + iw of the winner (torch's return_indices): a tie goes to the first tap in row-major window
+ *     order, the padding never wins, a NaN wins.  The backward is a gather: every input pixel sums the (at most four) windows
+ *     whose winner it is in ascending window order; dx is written everywhere.
+ *   pm_pool2d_avg_*: mean over the HW rows of each sample (ascending order) -> y (B, C) whose row stride may be any value >= C
+ *     (the head's [features | proprio] rows); backward dx[b*HW + r] = dy[b] / HW.
+ *   pm_im2col2d_c1_f32: patch matrix of a single-channel image, x (B rows of stride ldx, H*W pixels each) -> dst
+ *     (B*Ho*Wo, ldd), dst[.][kh*k + kw] = the pixel under tap (kh, kw) or 0 in the padding, columns k*k .. ldd-1 zeros (the stem's
+ *     K = 49 is no multiple of 4, so it cannot be a gathered operand; it runs on the Linear kernels over this matrix). */
+size_t pm_bn2d_workspace_bytes(long rows, int C);
+int pm_bn2d_stats_f32(const float* x, long ldx, long rows, int C, float eps, float* mean, float* var, float* invstd,
+                      float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int pm_bn2d_invstd_f32(const float* var, int C, float eps, float* invstd, void* stream); /* invstd = 1/sqrt(var + eps): inference */
+int pm_bn2d_apply_f32(const float* x, long ldx, long rows, int C, const float* mean, const float* invstd, const float* gamma,
+                      const float* beta, const float* residual, long ldr, int relu, float* y, long ldy, void* stream);
+int pm_bn2d_bwd_f32(const float* dy, long lddy, const float* dy2, long lddy2, const float* x, long ldx, const float* y, long ldy,
+                    int relu, long rows, int C, const float* mean, const float* invstd, const float* gamma, float* dgamma,
+                    float* dbeta, float* dx, long lddx, float* dy_masked, long lddym, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int pm_pool2d_out(int n);
+int pm_pool2d_max3s2_fwd_f32(const float* x, long ldx, int B, int H, int W, int C, float* y, long ldy, int32_t* idx, void* stream);
+int pm_pool2d_max3s2_bwd_f32(const float* dy, long lddy, const float* dy2, long lddy2, const int32_t* idx, int B, int H, int W, int C,
+                             float* dx, long lddx, void* stream);
+int pm_pool2d_avg_fwd_f32(const float* x, long ldx, int B, int HW, int C, float* y, long ldy, void* stream);
+int pm_pool2d_avg_bwd_f32(const float* dy, long lddy, int B, int HW, int C, float* dx, long lddx, void* stream);
+int pm_im2col2d_c1_f32(const float* x, long ldx, int B, int H, int W, int k, int stride, int pad, float* dst, int ldd, void* stream);
 
 #ifdef __cplusplus
 }

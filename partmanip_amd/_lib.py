@@ -155,6 +155,17 @@ SIGNATURES = {
     "pm_table_rows_i32": (I, [P, L, I, P, L, P, P]),
     "pm_voxel_vcat_table_i32": (I, [P, L, I, L, P, P]),
     "pm_exclusive_scan_i32": (I, [P, I, P, P, P]),
+    "pm_bn2d_workspace_bytes": (Z, [L, I]),
+    "pm_bn2d_stats_f32": (I, [P, L, L, I, F, P, P, P, P, P, P, F, P, Z, P]),
+    "pm_bn2d_invstd_f32": (I, [P, I, F, P, P]),
+    "pm_bn2d_apply_f32": (I, [P, L, L, I, P, P, P, P, P, L, I, P, L, P]),
+    "pm_bn2d_bwd_f32": (I, [P, L, P, L, P, L, P, L, I, L, I, P, P, P, P, P, P, L, P, L, P, Z, P]),
+    "pm_pool2d_out": (I, [I]),
+    "pm_pool2d_max3s2_fwd_f32": (I, [P, L, I, I, I, I, P, L, P, P]),
+    "pm_pool2d_max3s2_bwd_f32": (I, [P, L, P, L, P, I, I, I, I, P, L, P]),
+    "pm_pool2d_avg_fwd_f32": (I, [P, L, I, I, I, P, L, P]),
+    "pm_pool2d_avg_bwd_f32": (I, [P, L, I, I, I, P, L, P]),
+    "pm_im2col2d_c1_f32": (I, [P, L, I, I, I, I, I, I, P, I, P]),
     "pm_sa_supported": (I, [I, I, I, I]),
     "pm_sa_packed_elems": (Z, [I, I, I]),
     "pm_sa_pack_weights_f32": (I, [P, P, I, I, I, P, P]),

@@ -1490,16 +1490,330 @@ class Conv3DNet(_HipNet):
             ops.col2im3d(dcols, as5(dz), k, st, k // 2, as5(y_prev), self._act)
 
 
-def _out_of_scope(name):
+def conv2d_patch_table(B, H, W, k, stride, pad, device="cpu"):
+    """(B*Ho*Wo, k*k) int32: row of the channels-last input (b, ih, iw) under tap (kh, kw) of output (b, oh, ow), -1 in the
+    padding.  Depends on the batch size and the geometry only."""
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    t = torch.arange(k, device=device)
+    ph = torch.arange(Ho, device=device)[:, None] * stride - pad + t[None, :]           # (Ho, k) input row per (output, tap)
+    pw = torch.arange(Wo, device=device)[:, None] * stride - pad + t[None, :]
+    ok = ((ph >= 0) & (ph < H))[:, None, :, None] & ((pw >= 0) & (pw < W))[None, :, None, :]
+    lin = (ph[:, None, :, None] * W + pw[None, :, None, :]).expand(Ho, Wo, k, k)
+    lin = torch.where(ok, lin, torch.full_like(lin, -1)).reshape(Ho * Wo, k * k)
+    b = torch.arange(B, device=device)[:, None, None] * (H * W)
+    return torch.where(lin[None] >= 0, lin[None] + b, lin[None]).reshape(B * Ho * Wo, k * k).to(torch.int32).contiguous()
+
+
+def conv2d_transposed_table(B, H, W, k, stride, pad, device="cpu"):
+    """(B*H*W, k*k) int32: the OUTPUT row (b, oh, ow) that read input (b, ih, iw) through its tap (kh, kw) -- oh * stride - pad + kh
+    = ih -- or -1 where no output did (out of range, or, with a stride, a tap of the wrong parity): the table the data gradient
+    gathers through (ops.sparse_conv_bwd_data)."""
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    t = torch.arange(k, device=device)
+    nh = torch.arange(H, device=device)[:, None] + pad - t[None, :]                     # (H, k) = oh * stride
+    nw = torch.arange(W, device=device)[:, None] + pad - t[None, :]
+    oh, ow = torch.div(nh, stride, rounding_mode="floor"), torch.div(nw, stride, rounding_mode="floor")
+    okh = (nh >= 0) & (nh % stride == 0) & (oh < Ho)
+    okw = (nw >= 0) & (nw % stride == 0) & (ow < Wo)
+    ok = okh[:, None, :, None] & okw[None, :, None, :]
+    lin = (oh[:, None, :, None] * Wo + ow[None, :, None, :]).expand(H, W, k, k)
+    lin = torch.where(ok, lin, torch.full_like(lin, -1)).reshape(H * W, k * k)
+    b = torch.arange(B, device=device)[:, None, None] * (Ho * Wo)
+    return torch.where(lin[None] >= 0, lin[None] + b, lin[None]).reshape(B * H * W, k * k).to(torch.int32).contiguous()
+
+
+class _BasicBlock(nn.Module):
+    """Parameter container of a ResNet BasicBlock under torchvision's names: conv1, bn1, conv2, bn2 [, downsample.0, downsample.1]."""
+
+    def __init__(self, cin, cout, stride):
+        super().__init__()
+        self.conv1 = nn.Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(cout)
+        self.conv2 = nn.Conv2d(cout, cout, 3, stride=1, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(cout)
+        self.stride = stride
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride=stride, bias=False), nn.BatchNorm2d(cout))
+        else:
+            self.downsample = None
+
+
+class _ResNet34(nn.Module):
+    """Parameter container of the published ResNet-34 (He et al. 2016, table 1) without its classifier, under torchvision's names,
+    with a single-channel stem.  Initialisation as the reference gets it: Kaiming-normal (fan_out, ReLU) in every body convolution,
+    nn.Conv2d's default in the replaced stem, batch-norm weight 1 and bias 0."""
+
+    BLOCKS, WIDTHS = (3, 4, 6, 3), (64, 128, 256, 512)
+
+    def __init__(self):
+        super().__init__()
+        self.conv1 = nn.Conv2d(1, 64, 7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        cin = 64
+        for l, (n, c) in enumerate(zip(self.BLOCKS, self.WIDTHS)):
+            blocks = []
+            for i in range(n):
+                blocks.append(_BasicBlock(cin, c, 2 if (i == 0 and l > 0) else 1))
+                cin = c
+            setattr(self, f"layer{l + 1}", nn.Sequential(*blocks))
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d) and m is not self.conv1:
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+
+    def blocks(self):
+        return [b for l in range(4) for b in getattr(self, f"layer{l + 1}")]
+
+
+class _BnSaved(NamedTuple):               # what a training batch norm keeps for its backward
+    z: torch.Tensor                       # its input (the convolution's output)
+    mean: torch.Tensor
+    invstd: torch.Tensor
+    y: torch.Tensor                       # its output (after the residual and the ReLU, when it has them)
+
+
+class _BlockSaved(NamedTuple):            # what a BasicBlock keeps of a training forward
+    blk: nn.Module
+    src: torch.Tensor                     # the block's input rows (B*H*W, Cin)
+    hw_in: tuple
+    hw_out: tuple
+    bn1: _BnSaved
+    idx1: torch.Tensor                    # patch table of conv1 (on src)
+    bn2: _BnSaved
+    idx2: torch.Tensor                    # patch table of conv2 (on bn1.y)
+    bnd: Optional[_BnSaved]               # the shortcut's batch norm, table and tap-major weight (None: identity shortcut)
+    idxd: Optional[torch.Tensor]
+    wpd: Optional[torch.Tensor]
+
+
+class depthResNet(_HipNet):
+    """network.py:237-271: the depth-image student.  x[:, :72*128] is a (B, 1, 72, 128) depth image, the proprio tail is kept:
+    ResNet-34 (single-channel 7 x 7 / 2 stem - BN - ReLU - max pool 3 / 2 / 1 - BasicBlocks (3, 4, 6, 3) at (64, 128, 256, 512)
+    channels - global average pool) -> cat proprio -> Linear 128 - act - Linear 32 - act - Linear out.  `state_dict` keys are
+    torchvision's (`resnet34.*`, `final_mlp.{0,2,4}.*`), so a checkpoint of the reference loads.
+
+    Activations are channels-last matrices (b*H*W rows, C).  The 3 x 3 and 1 x 1 convolutions are the gathered GEMMs of the sparse
+    convolutions over cached 2-D patch tables (no patch matrix in HBM; the data gradient of a 3 x 3 layer gathers through the
+    transposed table, that of a 1 x 1 stride-2 shortcut scatters); the single-channel stem (K = 49) is a patch matrix
+    (pm_im2col2d_c1_f32) + the Linear kernels and needs no data gradient.  Batch norm, the pools: csrc/bn_pool2d.hip.
+    Modes follow nn.Module.training as torch does: in training mode EVERY forward (the rollout's under no_grad too) normalises with
+    batch statistics and updates the running statistics; in eval mode the forward reads the running statistics and writes nothing."""
+
+    H, W = 288 // 4, 512 // 4
+
+    def __init__(self, input_dim, output_dim, net_cfg, proprio_shape):
+        super().__init__()
+        if input_dim != self.H * self.W + proprio_shape:
+            raise ValueError(f"depthResNet: input_dim {input_dim} is not {self.H} * {self.W} + proprio {proprio_shape}")
+        act = net_cfg['activation']
+        code = _act_code(act, linear_only=True)
+        self.resnet34 = _ResNet34()
+        self.proprio_shape = proprio_shape
+        self.activation = get_activation(act)
+        self.final_mlp = nn.Sequential(
+            nn.Linear(512 + proprio_shape, 128), self.activation,
+            nn.Linear(128, 32), self.activation,
+            nn.Linear(32, output_dim),
+        )
+        object.__setattr__(self, "_head", _LinearChain([self.final_mlp[0], self.final_mlp[2], self.final_mlp[4]], code))
+        object.__setattr__(self, "_views", None)
+        object.__setattr__(self, "_saved", None)
+
+    def set_grad_views(self, views):
+        self._head.grads = [(views[f"final_mlp.{i}.weight"], views[f"final_mlp.{i}.bias"]) for i in (0, 2, 4)]
+        object.__setattr__(self, "_views", views)
+
+    # ---- cached geometry / constants
+    def _zero(self, device):
+        z = getattr(self, "_zero_row", None)
+        if z is None or z.device != device:
+            z = torch.zeros(512, device=device)          # absent taps of the widest layer; also every convolution's (absent) bias
+            object.__setattr__(self, "_zero_row", z)
+        return z
+
+    def _table(self, kind, B, H, W, k, stride, pad, device):
+        key = (kind, B, H, W, k, stride, pad, str(device))
+        cache = getattr(self, "_tables", None)
+        if cache is None:
+            cache = {}
+            object.__setattr__(self, "_tables", cache)
+        if key not in cache:
+            cache[key] = (conv2d_patch_table if kind == "fwd" else conv2d_transposed_table)(B, H, W, k, stride, pad, device)
+        return cache[key]
+
+    @staticmethod
+    def _tap_major(conv):
+        """conv.weight (Cout, Cin, k, k) as (Cout, k*k*Cin) with columns (tap, c): the forward's (and the scatter's) operand."""
+        co, ci = conv.out_channels, conv.in_channels
+        kk = conv.weight[0, 0].numel()
+        wp = torch.empty(co, kk * ci, device=conv.weight.device)
+        wp.view(co, kk, ci).copy_(conv.weight.data.view(co, ci, kk).transpose(1, 2))
+        return wp
+
+    @staticmethod
+    def _tap_major_t(conv):
+        """(Cin, k*k*Cout) with wt[ci, tap*Cout + co] = weight[co, ci, tap]: the gathered data gradient's operand."""
+        co, ci = conv.out_channels, conv.in_channels
+        kk = conv.weight[0, 0].numel()
+        wt = torch.empty(ci, kk * co, device=conv.weight.device)
+        wt.view(ci, kk, co).copy_(conv.weight.data.view(co, ci, kk).permute(1, 2, 0))
+        return wt
+
+    # ---- layers
+    def _bn(self, bn, z, residual=None, relu=False):
+        """Batch norm of z (rows, C) [+ residual] [ReLU]; training: batch statistics, running update; eval: running statistics."""
+        C, dev = z.shape[1], z.device
+        y = torch.empty_like(z)
+        if self.training:
+            mean, invstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
+            m = bn.momentum
+            if m is None:                                 # torch: cumulative moving average
+                m = 1.0 / (int(bn.num_batches_tracked) + 1)
+            ops.bn2d_stats(z, bn.eps, mean, invstd, self._workspace(dev), running_mean=bn.running_mean, running_var=bn.running_var,
+                           num_batches_tracked=bn.num_batches_tracked, momentum=m)
+        else:
+            mean, invstd = bn.running_mean, ops.bn2d_invstd(bn.running_var, bn.eps, torch.empty(C, device=dev))
+        ops.bn2d_apply(z, mean, invstd, bn.weight.data, bn.bias.data, y, residual, relu)
+        return _BnSaved(z, mean, invstd, y)
+
+    def _conv(self, conv, src, B, H, W):
+        """A 3 x 3 or 1 x 1 convolution of the channels-last rows `src` as a gathered GEMM -> (rows, Cout), (patch table, wp)."""
+        k, st = conv.kernel_size[0], conv.stride[0]
+        idx = self._table("fwd", B, H, W, k, st, k // 2, src.device)
+        wp = self._tap_major(conv)
+        z = torch.empty(idx.shape[0], conv.out_channels, device=src.device)
+        zero = self._zero(src.device)
+        ops.sparse_conv_fwd(src, idx, conv.in_channels, wp, zero, z, ops.ACT_NONE, zero)
+        return z, idx, wp
+
+    def hip_forward(self, x, out=None):
+        B, dev = x.shape[0], x.device
+        net = self.resnet34
+        HW = self.H * self.W
+        # stem: 7 x 7 / 2 on one channel = patch matrix (49 columns zero-padded to 64: whole K-steps) + Linear kernel
+        H1, W1 = (self.H + 6 - 7) // 2 + 1, (self.W + 6 - 7) // 2 + 1
+        cols = ops.im2col2d_c1(x[:, :HW], self.H, self.W, 7, 2, 3, torch.empty(B * H1 * W1, 64, device=dev))
+        w0 = torch.zeros(64, 64, device=dev)
+        w0[:, :49].copy_(net.conv1.weight.data.view(64, 49))
+        z0 = torch.empty(B * H1 * W1, 64, device=dev)
+        ops.linear_fwd(cols, w0, self._zero(dev), z0, ops.ACT_NONE)
+        s0 = self._bn(net.bn1, z0, relu=True)
+        H2, W2 = ops.pool2d_out(H1), ops.pool2d_out(W1)
+        p = torch.empty(B * H2 * W2, 64, device=dev)
+        pidx = torch.empty(B * H2 * W2, 64, dtype=torch.int32, device=dev)
+        ops.pool2d_max_fwd(s0.y, B, H1, W1, p, pidx)
+        cur, H, W = p, H2, W2
+        recs = []
+        for blk in net.blocks():
+            st = blk.stride
+            Ho, Wo = (H - 1) // st + 1, (W - 1) // st + 1
+            z1, idx1, _ = self._conv(blk.conv1, cur, B, H, W)
+            s1 = self._bn(blk.bn1, z1, relu=True)
+            z2, idx2, _ = self._conv(blk.conv2, s1.y, B, Ho, Wo)
+            if blk.downsample is not None:
+                zd, idxd, wpd = self._conv(blk.downsample[0], cur, B, H, W)
+                sd = self._bn(blk.downsample[1], zd)
+                short = sd.y
+            else:
+                sd = idxd = wpd = None
+                short = cur
+            s2 = self._bn(blk.bn2, z2, residual=short, relu=True)
+            recs.append(_BlockSaved(blk, cur, (H, W), (Ho, Wo), s1, idx1, s2, idx2, sd, idxd, wpd))
+            cur, H, W = s2.y, Ho, Wo
+        fbuf = torch.empty(B, 512 + self.proprio_shape, device=dev)
+        ops.pool2d_avg_fwd(cur, B, H * W, fbuf)
+        if self.proprio_shape != 0:
+            fbuf[:, 512:].copy_(x[:, -self.proprio_shape:])
+        object.__setattr__(self, "_saved", dict(B=B, training=self.training, cols=cols, s0=s0, pool=(H1, W1, H2, W2, pidx), recs=recs,
+                                                last=(H, W)))
+        return self._head.forward(fbuf, out)
+
+    def saved_signs(self):
+        """What the backward of the last training forward routes through, in forward order, as NCHW tensors: the stem's ReLU
+        mask, the max pool's winners as torch's `return_indices` gives them (int64), then the two ReLU masks of each block."""
+        s = self._saved
+        if s is None or not s["training"]:
+            raise RuntimeError("depthResNet.saved_signs: no training forward has run")
+        B = s["B"]
+        H1, W1, H2, W2, pidx = s["pool"]
+        nchw = lambda t, h, w: t.view(B, h, w, t.shape[1]).permute(0, 3, 1, 2)       # noqa: E731
+        out = [nchw(s["s0"].y, H1, W1) > 0, nchw(pidx, H2, W2).to(torch.int64)]
+        for rec in s["recs"]:
+            out += [nchw(rec.bn1.y, *rec.hw_out) > 0, nchw(rec.bn2.y, *rec.hw_out) > 0]
+        return out
+
+    def _wgrad(self, conv, name, dz, src, idx, ws):
+        """Weight gradient of a gathered convolution into the parameter's gradient view (torch's (Cout, Cin, k, k) order)."""
+        co, ci = conv.out_channels, conv.in_channels
+        kk = idx.shape[1]
+        dwp = torch.empty(co, kk * ci, device=dz.device)
+        ops.sparse_conv_bwd_weight(dz, src, idx, ci, dwp, None, self._zero(dz.device), ws)
+        self._views[name].view(co, ci, kk).copy_(dwp.view(co, kk, ci).transpose(1, 2))
+
+    def _bn_bwd(self, name, s, dy, relu, ws, dy2=None, want_masked=False):
+        """Backward of the batch norm `name` (its dotted module path) -> (d input, the masked dy when wanted)."""
+        v = self._views
+        mod = self.get_submodule(name)
+        dx = torch.empty_like(s.z)
+        dym = torch.empty_like(s.z) if want_masked else None
+        ops.bn2d_bwd(dy, s.z, s.y, s.mean, s.invstd, mod.weight.data, v[name + ".weight"], v[name + ".bias"], dx, ws, relu=relu, dy2=dy2,
+                     dy_masked=dym)
+        return dx, dym
+
+    def hip_backward(self, dy):
+        s = self._saved
+        if s is None or not s["training"]:
+            raise RuntimeError("depthResNet.hip_backward: the last forward ran in eval mode (running statistics): call .train() first")
+        if self._views is None:
+            raise RuntimeError("depthResNet.hip_backward needs the owner's flat gradient views (ActorCritic.flat())")
+        B, dev = s["B"], dy.device
+        ws = self._workspace(dev)
+        zero = self._zero(dev)
+        dfbuf = torch.empty(B, 512 + self.proprio_shape, device=dev)
+        self._head.backward(dy, ws, dx_out=dfbuf)
+        H, W = s["last"]
+        d = ops.pool2d_avg_bwd(dfbuf, B, H * W, torch.empty(B * H * W, 512, device=dev))
+        d2 = None
+        names = [f"resnet34.layer{l + 1}.{i}" for l, n in enumerate(_ResNet34.BLOCKS) for i in range(n)]
+        for name, rec in zip(reversed(names), reversed(s["recs"])):
+            blk, src, (H, W), (Ho, Wo), s1, idx1, s2, idx2, sd, idxd, wpd = rec
+            c_in, c = blk.conv1.in_channels, blk.conv1.out_channels
+            # out = relu(bn2(conv2(a1)) + shortcut): the masked gradient goes to bn2 and, as it is, to the shortcut
+            dz2, dm = self._bn_bwd(name + ".bn2", s2, d, True, ws, dy2=d2, want_masked=True)
+            self._wgrad(blk.conv2, name + ".conv2.weight", dz2, s1.y, idx2, ws)
+            da1 = torch.empty(B * Ho * Wo, c, device=dev)
+            ops.sparse_conv_bwd_data(dz2, self._table("bwd", B, Ho, Wo, 3, 1, 1, dev), self._tap_major_t(blk.conv2), None, da1,
+                                     ops.ACT_NONE, zero)
+            dz1, _ = self._bn_bwd(name + ".bn1", s1, da1, True, ws)
+            self._wgrad(blk.conv1, name + ".conv1.weight", dz1, src, idx1, ws)
+            dsrc = torch.empty(B * H * W, c_in, device=dev)
+            ops.sparse_conv_bwd_data(dz1, self._table("bwd", B, H, W, 3, blk.stride, 1, dev), self._tap_major_t(blk.conv1), None, dsrc,
+                                     ops.ACT_NONE, zero)
+            if sd is not None:
+                dzd, _ = self._bn_bwd(name + ".downsample.1", sd, dm, False, ws)
+                self._wgrad(blk.downsample[0], name + ".downsample.0.weight", dzd, src, idxd, ws)
+                # 1 x 1 / 2: every input pixel is read by at most one output, pixels at odd coordinates by none (zero gradient)
+                dshort = torch.zeros(B * H * W, c_in, device=dev)
+                ops.sparse_conv_bwd_data_scatter(dzd, wpd, idxd, c_in, None, dshort, ops.ACT_NONE)
+            else:
+                dshort = dm
+            d, d2 = dsrc, dshort
+        H1, W1, H2, W2, pidx = s["pool"]
+        dy0 = ops.pool2d_max_bwd(d, pidx, B, H1, W1, torch.empty(B * H1 * W1, 64, device=dev), dy2=d2)
+        dz0, _ = self._bn_bwd("resnet34.bn1", s["s0"], dy0, True, ws)
+        dw0 = torch.empty(64, 64, device=dev)
+        ops.linear_bwd_weight(dz0, s["cols"], dw0, None, ws)                # the image is data: no gradient to it
+        self._views["resnet34.conv1.weight"].view(64, 49).copy_(dw0[:, :49])
+
+
+def _out_of_scope(name, why):
     class _Stub(nn.Module):
         def __init__(self, *a, **k):
             raise NotImplementedError(
-                f"backbone '{name}' (reference network.py) is an image / pooled-TSDF student outside this build's hot-path "
-                "scope (SURVEY.md §8f rank 4); MLP, PointNet, PointNet2 and Conv3DNet are implemented")
+                f"backbone '{name}' (reference network.py) is not implemented: {why}; MLP, PointNet, PointNet2, Conv3DNet, "
+                "SparseUNet and depthResNet are")
     _Stub.__name__ = name
     return _Stub
 
 
-PoolConv3DNet = _out_of_scope("PoolConv3DNet")
-ResNet = _out_of_scope("ResNet")
-depthResNet = _out_of_scope("depthResNet")
+PoolConv3DNet = _out_of_scope("PoolConv3DNet", "the pooled-TSDF student is outside this build's hot-path scope (SURVEY.md §8f rank 4)")
+ResNet = _out_of_scope("ResNet", "the RGB student starts from pretrained ImageNet weights, which this package does not ship or fetch")

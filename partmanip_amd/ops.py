@@ -1193,6 +1193,155 @@ def sparse_conv_bwd_weight(dy, src, idx, C, dw, db, zero, ws):
           "pm_sparse_conv_bwd_weight_f32")
 
 
+# ----------------------------------------------------------------------------- 2-D residual network layers (csrc/bn_pool2d.hip)
+def _cl_rows(t, name, C=None):
+    """A channels-last activation: 2-D float32 (rows, C) with unit inner stride, C % 4 == 0, 16-byte rows.  Returns its row stride."""
+    ld = _rows(t, name)
+    if t.shape[1] % 4 or ld % 4 or t.data_ptr() % 16 or (C is not None and t.shape[1] != C):
+        raise ValueError(f"{name}: expected (rows, {'C' if C is None else C}) with C % 4 == 0, a row stride that is a multiple of 4 and "
+                         f"16-byte alignment, got {tuple(t.shape)} {t.stride()}")
+    return ld
+
+
+def _chan(t, name, C):
+    if t.dtype != torch.float32 or t.shape != (C,) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous float32 ({C},), got {t.dtype} {tuple(t.shape)}")
+
+
+def bn2d_stats(x, eps, mean, invstd, ws, var=None, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1):
+    """Batch statistics of x (rows, C) per channel into mean / invstd (/ var, biased); running_* and num_batches_tracked (int64, one
+    element) are updated in place when given (pm_bn2d_stats_f32).  rows < 2 is refused, as torch's training batch norm refuses it."""
+    _one_device("bn2d_stats", x, mean, invstd, var, running_mean, running_var, num_batches_tracked)
+    ld = _cl_rows(x, "x")
+    rows, C = x.shape
+    for t, n in ((mean, "mean"), (invstd, "invstd"), (var, "var"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None:
+            _chan(t, n, C)
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1):
+        raise ValueError("num_batches_tracked: expected one int64")
+    w = ws.get(lib.pm_bn2d_workspace_bytes(rows, C))
+    check(lib.pm_bn2d_stats_f32(_ptr(x), ld, rows, C, float(eps), _ptr(mean), _ptr(var), _ptr(invstd), _ptr(running_mean),
+                                _ptr(running_var), _ptr(num_batches_tracked), float(momentum), _ptr(w), w.numel(), _stream()),
+          "pm_bn2d_stats_f32")
+
+
+def bn2d_invstd(var, eps, invstd):
+    """invstd = 1 / sqrt(var + eps) per channel: what bn2d_apply takes beside running_mean at inference."""
+    _one_device("bn2d_invstd", var, invstd)
+    C = var.numel()
+    _chan(var, "var", C)
+    _chan(invstd, "invstd", C)
+    check(lib.pm_bn2d_invstd_f32(_ptr(var), C, float(eps), _ptr(invstd), _stream()), "pm_bn2d_invstd_f32")
+    return invstd
+
+
+def bn2d_apply(x, mean, invstd, gamma, beta, y, residual=None, relu=False):
+    """y = gamma (x - mean) invstd + beta [+ residual] [relu] (pm_bn2d_apply_f32); y may be x."""
+    _one_device("bn2d_apply", x, mean, invstd, gamma, beta, y, residual)
+    rows, C = x.shape
+    ldx, ldy = _cl_rows(x, "x"), _cl_rows(y, "y", C)
+    ldr = _cl_rows(residual, "residual", C) if residual is not None else 0
+    if y.shape[0] != rows or (residual is not None and residual.shape[0] != rows):
+        raise ValueError("bn2d_apply: x, y and residual must have the same rows")
+    for t, n in ((mean, "mean"), (invstd, "invstd"), (gamma, "gamma"), (beta, "beta")):
+        _chan(t, n, C)
+    check(lib.pm_bn2d_apply_f32(_ptr(x), ldx, rows, C, _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(residual), ldr, int(relu),
+                                _ptr(y), ldy, _stream()), "pm_bn2d_apply_f32")
+    return y
+
+
+def bn2d_bwd(dy, x, y, mean, invstd, gamma, dgamma, dbeta, dx, ws, relu=False, dy2=None, dy_masked=None):
+    """Backward of bn2d_stats + bn2d_apply (pm_bn2d_bwd_f32): dgamma, dbeta, dx, and dy_masked = (dy [+ dy2]) [* (y > 0)] for the
+    residual branch when wanted.  y (the layer's output) is read only with relu."""
+    _one_device("bn2d_bwd", dy, x, y, mean, invstd, gamma, dgamma, dbeta, dx, dy2, dy_masked)
+    rows, C = x.shape
+    ldx, lddy, lddx = _cl_rows(x, "x"), _cl_rows(dy, "dy", C), _cl_rows(dx, "dx", C)
+    if relu and y is None:
+        raise ValueError("bn2d_bwd: relu=True needs the layer's output y")
+    ldy = _cl_rows(y, "y", C) if relu else 0
+    lddy2 = _cl_rows(dy2, "dy2", C) if dy2 is not None else 0
+    lddym = _cl_rows(dy_masked, "dy_masked", C) if dy_masked is not None else 0
+    for t in (dy, dx, y if relu else None, dy2, dy_masked):
+        if t is not None and t.shape[0] != rows:
+            raise ValueError("bn2d_bwd: all activations must have the same rows")
+    for t, n in ((mean, "mean"), (invstd, "invstd"), (gamma, "gamma"), (dgamma, "dgamma"), (dbeta, "dbeta")):
+        _chan(t, n, C)
+    w = ws.get(lib.pm_bn2d_workspace_bytes(rows, C))
+    check(lib.pm_bn2d_bwd_f32(_ptr(dy), lddy, _ptr(dy2), lddy2, _ptr(x), ldx, _ptr(y) if relu else 0, ldy, int(relu), rows, C, _ptr(mean),
+                              _ptr(invstd), _ptr(gamma), _ptr(dgamma), _ptr(dbeta), _ptr(dx), lddx, _ptr(dy_masked), lddym, _ptr(w),
+                              w.numel(), _stream()), "pm_bn2d_bwd_f32")
+    return dx
+
+
+def pool2d_out(n):
+    """Output extent of the 3 x 3 / stride 2 / padding 1 pool (and of a 3 x 3 or 1 x 1 stride-2 convolution with padding k // 2)."""
+    return lib.pm_pool2d_out(int(n))
+
+
+def pool2d_max_fwd(x, B, H, W, y, idx):
+    """3 x 3 / 2 / 1 max pool of channels-last x (B*H*W, C) into y (B*Ho*Wo, C) and idx (same shape, int32: ih*W + iw of the winner)."""
+    _one_device("pool2d_max_fwd", x, y, idx)
+    C = x.shape[1]
+    ldx, ldy = _cl_rows(x, "x"), _cl_rows(y, "y", C)
+    n_out = B * pool2d_out(H) * pool2d_out(W)
+    if x.shape[0] != B * H * W or y.shape[0] != n_out or idx.shape != (n_out, C) or idx.dtype != torch.int32 or not idx.is_contiguous():
+        raise ValueError(f"pool2d_max_fwd: x ({B * H * W}, C), y ({n_out}, C) and a contiguous int32 idx ({n_out}, C) expected, got "
+                         f"{tuple(x.shape)}, {tuple(y.shape)}, {idx.dtype} {tuple(idx.shape)}")
+    check(lib.pm_pool2d_max3s2_fwd_f32(_ptr(x), ldx, B, H, W, C, _ptr(y), ldy, _ptr(idx), _stream()), "pm_pool2d_max3s2_fwd_f32")
+    return y, idx
+
+
+def pool2d_max_bwd(dy, idx, B, H, W, dx, dy2=None):
+    """dx (B*H*W, C) = the gather of dy [+ dy2] (B*Ho*Wo, C) through the winners idx of pool2d_max_fwd."""
+    _one_device("pool2d_max_bwd", dy, idx, dx, dy2)
+    C = dx.shape[1]
+    lddx, lddy = _cl_rows(dx, "dx"), _cl_rows(dy, "dy", C)
+    lddy2 = _cl_rows(dy2, "dy2", C) if dy2 is not None else 0
+    n_out = B * pool2d_out(H) * pool2d_out(W)
+    if dx.shape[0] != B * H * W or dy.shape[0] != n_out or idx.shape != (n_out, C) or idx.dtype != torch.int32 or not idx.is_contiguous() \
+            or (dy2 is not None and dy2.shape[0] != n_out):
+        raise ValueError(f"pool2d_max_bwd: dx ({B * H * W}, C), dy ({n_out}, C) and a contiguous int32 idx ({n_out}, C) expected")
+    check(lib.pm_pool2d_max3s2_bwd_f32(_ptr(dy), lddy, _ptr(dy2), lddy2, _ptr(idx), B, H, W, C, _ptr(dx), lddx, _stream()),
+          "pm_pool2d_max3s2_bwd_f32")
+    return dx
+
+
+def pool2d_avg_fwd(x, B, HW, y):
+    """y[:, :C] (B rows, any stride) = the mean over the HW rows of each sample of x (B*HW, C)."""
+    _one_device("pool2d_avg_fwd", x, y)
+    C = x.shape[1]
+    ldx = _cl_rows(x, "x")
+    if x.shape[0] != B * HW or y.shape[0] != B or y.shape[1] < C:
+        raise ValueError(f"pool2d_avg_fwd: x ({B * HW}, C) and y ({B}, >= C) expected, got {tuple(x.shape)}, {tuple(y.shape)}")
+    check(lib.pm_pool2d_avg_fwd_f32(_ptr(x), ldx, B, HW, C, _ptr(y), _rows(y, "y"), _stream()), "pm_pool2d_avg_fwd_f32")
+    return y
+
+
+def pool2d_avg_bwd(dy, B, HW, dx):
+    """dx (B*HW, C) rows of sample b = dy[b, :C] / HW."""
+    _one_device("pool2d_avg_bwd", dy, dx)
+    C = dx.shape[1]
+    lddx = _cl_rows(dx, "dx")
+    if dx.shape[0] != B * HW or dy.shape[0] != B or dy.shape[1] < C:
+        raise ValueError(f"pool2d_avg_bwd: dx ({B * HW}, C) and dy ({B}, >= C) expected, got {tuple(dx.shape)}, {tuple(dy.shape)}")
+    check(lib.pm_pool2d_avg_bwd_f32(_ptr(dy), _rows(dy, "dy"), B, HW, C, _ptr(dx), lddx, _stream()), "pm_pool2d_avg_bwd_f32")
+    return dx
+
+
+def im2col2d_c1(x, H, W, k, stride, pad, dst):
+    """Patch matrix of single-channel images: x (B, >= H*W) rows (the leading H*W columns are the image) -> dst (B*Ho*Wo, ldd >= k*k),
+    zero in the padding and in the columns past k*k."""
+    _one_device("im2col2d_c1", x, dst)
+    ldx = _rows(x, "x")
+    _f32c(dst, "dst")
+    B = x.shape[0]
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if x.shape[1] < H * W or dst.dim() != 2 or dst.shape[0] != B * Ho * Wo or dst.shape[1] < k * k:
+        raise ValueError(f"im2col2d_c1: x ({B}, >= {H * W}) and dst ({B * Ho * Wo}, >= {k * k}) expected, got {tuple(x.shape)}, {tuple(dst.shape)}")
+    check(lib.pm_im2col2d_c1_f32(_ptr(x), ldx, B, H, W, k, stride, pad, _ptr(dst), dst.shape[1], _stream()), "pm_im2col2d_c1_f32")
+    return dst
+
+
 # `accumulate` of rows_gather_bwd (pm_rows_gather_bwd_f32): what dsrc holds when the call starts
 ACC_OVERWRITE = 0         # nothing: dsrc is overwritten
 ACC_ADD = 1               # a finished gradient: the (already multiplied) result is added to it
