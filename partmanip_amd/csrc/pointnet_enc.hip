@@ -131,36 +131,53 @@ __device__ __forceinline__ void stage_points(const float* __restrict__ xb, int t
     }
 }
 
+// layer 1, CT = 3 / 4, on this thread's W1 row and bias already in registers (layer1_row loads them): one broadcast
+// ds_read_b128 per point, no branches.  A caller that walks many tiles loads the row once and calls this per tile.
+template <int CT, int TM, int NT, bool TANH = true>
+__device__ __forceinline__ void layer1_tile(const float* __restrict__ Xs, const float (&w)[4], float b1c, float* __restrict__ H1,
+                                            int act = PM_ACT_TANH) {
+    static_assert(CT == 3 || CT == 4, "the register form is the compile-time-C path");
+    constexpr int PPT = TM * 128 / NT;           // points per thread
+    static_assert(PPT % 2 == 0, "layer 1 pairs points for the packed tanh");
+    const int c = threadIdx.x & 127, p0 = (threadIdx.x >> 7) * PPT;
+#pragma unroll 4
+    for (int p = p0; p < p0 + PPT; p += 2) {
+        float s2[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float4 xv = *(const float4*)(Xs + (p + j) * PN_MAXC);
+            float s = fmaf(w[0], xv.x, b1c);
+            s = fmaf(w[1], xv.y, s);
+            s = fmaf(w[2], xv.z, s);
+            if (CT == 4) s = fmaf(w[3], xv.w, s);
+            s2[j] = s;
+        }
+        const f32x2 t = pn_act2<TANH>(s2[0], s2[1], act);
+        H1[p * PN_LD1 + c] = t.x;
+        H1[(p + 1) * PN_LD1 + c] = t.y;
+    }
+}
+template <int CT>
+__device__ __forceinline__ void layer1_row(const float* __restrict__ W1, const float* __restrict__ b1, float (&w)[4], float& b1c) {
+    const int c = threadIdx.x & 127;
+    b1c = b1[c];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) w[d] = (d < CT) ? W1[c * CT + d] : 0.f;
+}
+
 // layer 1: thread (c = tid&127, part = tid>>7) computes tanh(b1[c] + W1[c,:] . x[p,:]) for its PPT points.
 // CT = compile-time channel count (3: xyz clouds, 4: depth_sparse); 0 = generic runtime C <= 8.
 template <int CT, int TM, int NT, bool TANH = true>
 __device__ __forceinline__ void layer1_tile(const float* __restrict__ Xs, const float* __restrict__ W1,
                                             const float* __restrict__ b1, int C, float* __restrict__ H1, int act = PM_ACT_TANH) {
-    constexpr int PPT = TM * 128 / NT;           // points per thread
-    const int c = threadIdx.x & 127, p0 = (threadIdx.x >> 7) * PPT;
-    const float b1c = b1[c];
-    if (CT == 3 || CT == 4) {                  // one broadcast ds_read_b128 per point, no branches
-        float w[4];
-#pragma unroll
-        for (int d = 0; d < 4; ++d) w[d] = (d < CT) ? W1[c * CT + d] : 0.f;
-        static_assert(PPT % 2 == 0, "layer 1 pairs points for the packed tanh");
-#pragma unroll 4
-        for (int p = p0; p < p0 + PPT; p += 2) {
-            float s2[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float4 xv = *(const float4*)(Xs + (p + j) * PN_MAXC);
-                float s = fmaf(w[0], xv.x, b1c);
-                s = fmaf(w[1], xv.y, s);
-                s = fmaf(w[2], xv.z, s);
-                if (CT == 4) s = fmaf(w[3], xv.w, s);
-                s2[j] = s;
-            }
-            const f32x2 t = pn_act2<TANH>(s2[0], s2[1], act);
-            H1[p * PN_LD1 + c] = t.x;
-            H1[(p + 1) * PN_LD1 + c] = t.y;
-        }
+    if constexpr (CT == 3 || CT == 4) {
+        float w[4], b1r;
+        layer1_row<CT>(W1, b1, w, b1r);
+        layer1_tile<CT, TM, NT, TANH>(Xs, w, b1r, H1, act);
     } else {
+        constexpr int PPT = TM * 128 / NT;       // points per thread
+        const int c = threadIdx.x & 127, p0 = (threadIdx.x >> 7) * PPT;
+        const float b1c = b1[c];
         float w1[PN_MAXC];
 #pragma unroll
         for (int d = 0; d < PN_MAXC; ++d) w1[d] = (d < C) ? W1[c * C + d] : 0.f;

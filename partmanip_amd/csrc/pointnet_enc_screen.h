@@ -175,6 +175,31 @@ __device__ __forceinline__ void ps_copy_h2(const float* __restrict__ H, float* _
     }
 }
 
+// The next tile's points, one value per thread (PN_TM * PN_MAXC slots = PS_NW * 64 threads): the load is issued a tile ahead,
+// right after the loop-top barrier, and waited for only where stage_points used to load it -- behind layer 1, the layer-2 MFMAs
+// and their epilogue.  x is read once per rollout and every tile's lines are cold: the load is a full HBM miss.
+static_assert(PN_TM * PN_MAXC == PS_NW * 64, "one staged slot per thread");
+__device__ __forceinline__ float ps_point_load(const float* __restrict__ xb, int tile, int C, int tid) {
+    const int p = tid >> 3, d = tid & 7;
+    return d < C ? xb[(tile * PN_TM + p) * C + d] : 0.f;                  // slots d >= C stay zero, as in stage_points
+}
+__device__ __forceinline__ void ps_point_store(float v, int sub_mean, const float (&cen)[3], int tid, float* __restrict__ Xs) {
+    const int d = tid & 7;
+    if (sub_mean && d < 3) v -= cen[d];
+    Xs[tid] = v;
+}
+
+#ifdef PS_PROFILE   // A/B builds only (tools/ps_profile.py): cycle-counter stamps of work-groups 0-3 (one cloud each), tiles 0-15, every wave
+__device__ unsigned long long ps_prof[4 * 16 * PS_NW * 16];
+extern "C" int pm_debug_ps_prof_read(void* dst) {
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(ps_prof), sizeof(ps_prof)) == hipSuccess ? 0 : 1;
+}
+#define PS_STAMP(i)                                                                                         \
+    if (b < 4 && tile < 16 && lane0 == 0) ps_prof[((b * 16 + tile) * PS_NW + wave) * 16 + (i)] = __builtin_readcyclecounter()
+#else
+#define PS_STAMP(i)
+#endif
+
 template <int CT, int SCHED>
 __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
     const float* __restrict__ x, long ldx, int P, int C, int sub_mean, const float* __restrict__ W1,
@@ -207,14 +232,30 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
     int imax = 0;
     double csum = 0.0;                       // lanes < 32: column 32 wave + lane of h2
 
+    // Per-lane constants of the tile loop, loaded once per cloud (they depend on the lane and the wave only; the addresses
+    // are those the loop used to recompute from the laundered lane id): 5 VGPRs, + 5 for the W1 row and b1 when C is 3 or 4.
+    const int li0 = lane0 & 31;
+    const float b2r = b2[wave * 32 + li0];
+    const float b3r[2] = {b3[(wave * 2 + 0) * 32 + li0], b3[(wave * 2 + 1) * 32 + li0]};
+    const float epsr[2] = {epsg[(wave * 2 + 0) * 32 + li0], epsg[(wave * 2 + 1) * 32 + li0]};
+    float w1r[4] = {0.f, 0.f, 0.f, 0.f}, b1r = 0.f;
+    if constexpr (CT == 3 || CT == 4) layer1_row<CT>(W1, b1, w1r, b1r);
+
     const int ntiles = P / PN_TM;
     stage_points<PN_TM, NT>(xb, 0, C, sub_mean, cen, Xs);
     for (int tile = 0; tile < ntiles; ++tile) {
         int lane = lane0;                    // laundered per tile: see pn_fwd_kernel
         asm volatile("" : "+v"(lane));
         const int li = lane & 31, lh = lane >> 5;
+        PS_STAMP(0);
         __syncthreads();                     // Xs staged; the previous tile's reads of H and the planes are done
-        if (!(PS_ABLATE & 1)) layer1_tile<CT, PN_TM, NT, true>(Xs, W1, b1, C, H);   // ablated: H1 = what the last tile left in H
+        float xnext = 0.f;                   // tile + 1's point coordinate: in flight until the layer-2 epilogue is done
+        if (tile + 1 < ntiles) xnext = ps_point_load(xb, tile + 1, C, tid);
+        if (!(PS_ABLATE & 1)) {              // ablated: H1 = what the last tile left in H
+            if constexpr (CT == 3 || CT == 4) layer1_tile<CT, PN_TM, NT, true>(Xs, w1r, b1r, H);
+            else layer1_tile<CT, PN_TM, NT, true>(Xs, W1, b1, C, H);
+        }
+        PS_STAMP(1);
         __syncthreads();
         {
             f32x16 acc2[2][1];
@@ -228,10 +269,12 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
             } else {
                 layer2_mfma<2, 1>(H, P2v, wave, lane, acc2);
             }
+            PS_STAMP(2);
             __syncthreads();                 // every wave has finished reading H1 (and Xs)
+            PS_STAMP(3);
             // layer-2 epilogue: layer2_store's arithmetic, plus the bf16 planes and this tile's column sum
             const int col = wave * 32 + li;
-            const float b2c = b2[col];
+            const float b2c = b2r;
             float ts = 0.f;                  // fp32 within the tile, rows in increasing order
             const bool planes = !(PS_ABLATE & 8) || tile == 0;      // ablated: the screen keeps reading tile 0's planes
             // Lanes l and l ^ 1 hold columns col and col ^ 1 of the same rows: they swap one value of every row pair (r, r + 1), so
@@ -275,9 +318,11 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
                 }
             ts += __shfl_xor(ts, 32, 64);    // the other 32 rows; both halves hold the same sum
             csum += (double)ts;              // fp64 across tiles
-            if (tile + 1 < ntiles) stage_points<PN_TM, NT>(xb, tile + 1, C, sub_mean, cen, Xs);
+            if (tile + 1 < ntiles) ps_point_store(xnext, sub_mean, cen, tid, Xs);
         }
+        PS_STAMP(4);
         __syncthreads();                     // H2 and the planes are complete; nothing below writes them before the loop-top barrier
+        PS_STAMP(5);
 
         const bool copy = h2_save && !(PS_ABLATE & 128), late = ps_late_wave<SCHED>(wave);
         float* h2dst = copy ? h2_save + ((long)b * P + (long)tile * PN_TM) * PN_C2 : nullptr;
@@ -287,7 +332,7 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
         f32x16 acc[2][2];
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-            const float b3c = b3[(wave * 2 + nb) * 32 + li];
+            const float b3c = b3r[nb];
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[0][nb][r] = acc[1][nb][r] = b3c;
         }
@@ -303,6 +348,7 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
             ps_stream(Hh + li * PS_LDP + lh * 8, Hl + li * PS_LDP + lh * 8, S3h + (size_t)(wave * 2 * 16) * 64 + lane,
                       S3l + (size_t)(wave * 2 * 16) * 64 + lane, acc);
         }
+        PS_STAMP(6);
 
         unsigned msk[2];
         float tmax[2];                       // PS_ABLATE & 64 only
@@ -323,7 +369,7 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
 #pragma unroll
                 for (int r = 0; r < 16; ++r) m = fmaxf(m, acc[mb][nb][r]);
             m = fmaxf(m, __shfl_xor(m, 32, 64));
-            const float e = epsg[(wave * 2 + nb) * 32 + li];
+            const float e = epsr[nb];
             const float vm = __shfl(vmax, nb * 32 + li, 64);
             const float thr = m - 2.f * e;
             unsigned k = 0;
@@ -347,6 +393,7 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
             if (lane >= o) incl += t;
         }
         const int total = __builtin_amdgcn_readlane(incl, 63);
+        PS_STAMP(7);
 
         if (PS_ABLATE & 64) {
             // no finish: the running maximum follows the tile maxima of z~ instead, so that the second test keeps pruning
@@ -415,7 +462,7 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
             // ---- too many survivors: the dense fp32 layer 3 of pn_fwd_kernel for this wave and tile ----------
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
-                const float b3c = b3[(wave * 2 + nb) * 32 + li];
+                const float b3c = b3r[nb];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[0][nb][r] = acc[1][nb][r] = b3c;
             }
@@ -451,7 +498,9 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
             }
             if (counters && lane == 0) atomicAdd(counters + 1, 1ull);
         }
+        PS_STAMP(8);
         if (copy && !late) ps_copy_h2<NT>(H, h2dst, tid);    // SCHED 1, waves 0-3: under the SIMD partner's screen MFMAs
+        PS_STAMP(9);
     }
     // ---- epilogue: thread tid owns channel tid --------------------------------------------------------------
     if ((lane0 >> 5) == 0) cs[wave * 32 + lane0] = csum;
