@@ -506,6 +506,35 @@ int pm_tsdf_select_f32(const float* vol, int B, int res, float lo, float hi, flo
 int pm_tsdf_sparse_gather_f32(const float* coords, const int32_t* idx, const float* vol, int B, int res, int K,
                               float* out, void* stream);
 
+/* ------------------------------------------------------------------ depth images -> compact cloud with source pixels, part labels
+ * pm_depth_cloud_f32 = pm_depth_compact_f32(pm_depth_backproject_f32(...)) in one kernel that never writes the (B, P, 3) world cloud
+ * and records the pixel every kept point came from.  P = M H W; pixel r = view * H W + row * W + col; w(r) is what
+ * pm_depth_backproject_f32 writes for that pixel (the same device function computes it: same arithmetic, same zeroing outside the
+ * OPEN box (lo, hi); lo / hi are HOST pointers to 3 floats).  Kept pixels: every r with w(r) != (0, 0, 0) by value, plus the
+ * smallest r with w(r) == (0, 0, 0) if there is one (a pixel whose world point lies inside the box but exactly at the origin counts
+ * as zero, as in the composition).  The j-th kept pixel in ascending r goes to xyz[b, j] = w(r) and src[b, j] = r, for j < cap;
+ * lengths[b] = min(count, cap); rows at and past lengths[b] are NOT written.  xyz (B, cap, 3), src (B, cap) int32 or NULL (not
+ * wanted), lengths (B) int32.  With cap >= count, xyz[b, :lengths[b]] and lengths equal the composition bit for bit; with
+ * cap < count the first cap kept points survive (a truncation the caller chose, to bound memory).  One work-group per environment,
+ * no atomics on global memory, no workspace, stream-ordered, never synchronises.
+ * PM_EINVAL: a NULL depth / cam_pose / lo / hi / xyz / lengths, B, M, H, W or cap < 1, M H W > INT_MAX. */
+int pm_depth_cloud_f32(const float* depth, int B, int M, int H, int W, const float* cam_pose, float fx, float fy, float cx,
+                       float cy, const float* lo, const float* hi, int cap, float* xyz, int32_t* src, int32_t* lengths,
+                       void* stream);
+/* Rows (x, y, z, label) of sampled points of such a cloud.  xyz (B, ld, 3) and src (B, ld) as written above (ld = cap), idx (B, K)
+ * int32 (pm_fps_varlen_f32's), seg: int32 labels per pixel, row b at seg + b * seg_stride, P pixels per row.  With i = idx[b, k]:
+ *   out[b * out_stride + 4 k + 0..2] = xyz[b, i, :]
+ *   out[b * out_stride + 4 k + 3]    = zero_label if xyz[b, i] == (0, 0, 0) by value -- the one point that stands for everything
+ *                                      cropped away or missed: its pixel is whichever came first, so its label would mean nothing;
+ *                                      otherwise (float) seg[b * seg_stride + src[b, i]]
+ * i outside [0, ld): all four floats are NaN and nothing is read through i.  src[b, i] outside [0, P): the label is NaN and seg is
+ * not read.  Columns at and past 4 K of a row are never written (the proprio tail of an observation row); rows need 4-byte
+ * alignment only.  No workspace, no atomics, stream-ordered.
+ * PM_EINVAL: a NULL xyz / src / idx / seg / out, B, ld, K or P < 1, out_stride < 4 K, seg_stride < P. */
+int pm_cloud_gather_labeled_f32(const float* xyz, const int32_t* src, int B, int ld, const int32_t* idx, int K, const int32_t* seg,
+                                long seg_stride, int P, float zero_label, float* out, long out_stride, void* stream);
+/* PM_ABI_VERSION stays 163 with these additions and with pm_mesh_pc_query_labeled_f32 below (no existing signature changed). */
+
 /* algorithms/algo_utils/network.py:72,119 -- Conv3DNet's INPUT layer, Conv3d(1, Cout, k, stride, padding k/2), as a direct
  * stencil over the single-channel volume (no patch matrix): x (B, D, H, W) through element strides (sb, sd, sh, sw);
  * wt = conv.weight viewed (Cout, k^3) TRANSPOSED to (k^3, Cout); y (B*Do*Ho*Wo, ldy) rows of Cout = act(conv + bias)
@@ -621,6 +650,15 @@ int pm_mesh_sdf_bake_f32(const float* tri, int F, int X, int Y, int Z, float vox
  * out_stride < 3 K, sel == NULL with K != Q, a non-zero sel_stride < K. */
 int pm_mesh_pc_query_f32(const float* pts, const int32_t* part_of, int Q, const float* pose_R, const float* pose_T, int B, int M,
                          const int32_t* sel, long sel_stride, int K, float* out, long out_stride, void* stream);
+/* The same cloud with a fourth column, the label of the point's part: labels (M) float32, one number per pose slot.
+ *   out[b * out_stride + 4 k + j], j < 3: exactly what pm_mesh_pc_query_f32 defines for out[b * out_stride + 3 k + j]
+ *   out[b * out_stride + 4 k + 3] = labels[p]
+ * (the same kernel with four floats per point instead of three).  q outside [0, Q) or p outside [0, M): the point's FOUR outputs
+ * are NaN and nothing is read through that index, labels included.  out_stride >= 4 K; columns at and past 4 K are not touched.
+ * PM_EINVAL: as above with 4 K for 3 K, and a NULL labels. */
+int pm_mesh_pc_query_labeled_f32(const float* pts, const int32_t* part_of, int Q, const float* pose_R, const float* pose_T, int B,
+                                 int M, const int32_t* sel, long sel_stride, int K, float* out, long out_stride,
+                                 const float* labels, void* stream);
 
 /* ------------------------------------------------------------------ depth camera over the posed part meshes (observation side)
  * The producer of the depth observations of tasks/hand_base.py:312-343 (there: the simulator's camera sensors): out (B, V, H, W) =

@@ -91,6 +91,8 @@ SIGNATURES = {
     "pm_maxpool_rows_bwd_f32": (I, [P, L, P, L, I, I, P, P, P]),
     "pm_depth_backproject_f32": (I, [P, I, I, I, I, P, F, F, F, F, P, P, P, P]),
     "pm_depth_compact_f32": (I, [P, I, I, P, P, P]),
+    "pm_depth_cloud_f32": (I, [P, I, I, I, I, P, F, F, F, F, P, P, I, P, P, P, P]),
+    "pm_cloud_gather_labeled_f32": (I, [P, P, I, I, P, I, P, L, I, F, P, L, P]),
     "pm_fps_varlen_f32": (I, [P, I, I, I, I, P, I, P, P, Z, P]),
     "pm_fps_varlen_workspace_bytes": (Z, [I, I]),
     "pm_tsdf_select_f32": (I, [P, I, I, F, F, P, P, P]),
@@ -113,6 +115,7 @@ SIGNATURES = {
     "pm_mesh_sdf_bake_workspace_bytes": (Z, [I]),
     "pm_mesh_sdf_bake_f32": (I, [P, I, I, I, I, F, F, F, F, F, I, P, P, Z, P]),
     "pm_mesh_pc_query_f32": (I, [P, P, I, P, P, I, I, P, L, I, P, L, P]),
+    "pm_mesh_pc_query_labeled_f32": (I, [P, P, I, P, P, I, I, P, L, I, P, L, P, P]),
     "pm_mesh_depth_render_f32": (I, [P, P, I, P, I, P, P, I, I, P, I, F, F, F, F, I, I, F, F, P, L, P]),
     "pm_mesh_frame_workspace_bytes": (Z, [I, I, I, I]),
     "pm_mesh_frame_render_f32": (I, [P, P, I, P, I, P, P, I, I, P, I, F, F, F, F, I, I, F, F, P, I, P, F, F, I, I, I, P, L, P, L, P, L, P, Z,

@@ -30,6 +30,10 @@
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), <STAGE, PER_ENV>: <true, false> (shared or no selection, the
 // default) 45 VGPRs, 38 SGPRs; <true, true> 56 / 46; <false, false> 32 / 46; <false, true> 56 / 50; all without scratch, occupancy
 // 8 waves / SIMD; LDS (dynamic) eb * M * 48 bytes = 9 KB at 12 parts and 16 environments per block.
+// The labelled cloud (pm_mesh_pc_query_labeled_f32) is the same kernel with NF = 4 floats per point: lane e owns column e % 4 of
+// point e / 4, and the lane of column 3 fetches labels[p] where the others fetch the point (no pose, no arithmetic).  The NF = 3
+// instantiations compile to the figures above, unchanged; NF = 4: <true, false> 45 VGPRs, 46 SGPRs; <true, true> 45 / 52;
+// <false, false> 32 / 52; <false, true> 44 / 56; no scratch, 8 waves / SIMD.
 // Measured A/B on one MI355X, 12 parts x 1024 points, select = 'all' (K = 12288, 604 MB of output at B = 4096, where the floor is
 // 0.096 ms at the 6.29 TB/s copy rate) / a 1024-point shared selection, ms per call at B = 4096 (tools/time_mesh_pc.py), kept = the
 // last: one environment per block, one float per thread, poses read from memory per float 0.426 / 0.052 -> 16 environments per
@@ -54,18 +58,26 @@ typedef float mp_f4 __attribute__((ext_vector_type(4)));
 
 struct mp_pt {
     float x0, x1, x2;
-    int pj;                                                  // p * 3 + j, or -1: NaN
+    int pj;                                                  // p * 3 + j; -1: NaN; MP_LABEL (NF = 4, column 3): the value is x0
 };
+#define MP_LABEL (-2)
 
+// NF = floats per point: 3 (x, y, z) or 4 (x, y, z, labels[p]); n3 = NF * K
+template <int NF>
 __device__ __forceinline__ mp_pt mp_fetch(const float* __restrict__ pts, const int32_t* __restrict__ part_of, int Q, int M,
-                                          const int32_t* __restrict__ selrow, long e, long n3) {
+                                          const int32_t* __restrict__ selrow, const float* __restrict__ labels, long e, long n3) {
     mp_pt r = {0.f, 0.f, 0.f, -1};
     if (e >= n3) return r;
-    const int k = (int)(e / 3), j = (int)(e - 3L * k);
+    const int k = (int)(e / NF), j = (int)(e - (long)NF * k);
     const int q = selrow ? selrow[k] : k;
     if (q < 0 || q >= Q) return r;
     const int p = part_of[q];
     if (p < 0 || p >= M) return r;
+    if (NF == 4 && j == 3) {
+        r.x0 = labels[p];
+        r.pj = MP_LABEL;
+        return r;
+    }
     r.x0 = pts[3L * q];
     r.x1 = pts[3L * q + 1];
     r.x2 = pts[3L * q + 2];
@@ -73,16 +85,17 @@ __device__ __forceinline__ mp_pt mp_fetch(const float* __restrict__ pts, const i
     return r;
 }
 
-template <bool STAGE, bool PER_ENV>
+template <int NF, bool STAGE, bool PER_ENV>
 __global__ __launch_bounds__(MP_THREADS) void mesh_pc_kernel(const float* __restrict__ pts, const int32_t* __restrict__ part_of,
                                                               int Q, const float* __restrict__ pose_R,
                                                               const float* __restrict__ pose_T, int B, int M,
                                                               const int32_t* __restrict__ sel, long sel_stride, int K, int eb,
-                                                              float* __restrict__ out, long out_stride) {
+                                                              float* __restrict__ out, long out_stride,
+                                                              const float* __restrict__ labels) {
     extern __shared__ mp_f4 mp_tab[];                        // [env in block][part][row j] = (R[j,0], R[j,1], R[j,2], T[j])
     const int b0 = blockIdx.y * eb;
     const int nb = min(eb, B - b0);
-    const long n3 = 3L * K;
+    const long n3 = (long)NF * K;
     const long e0 = (long)blockIdx.x * (MP_THREADS * MP_PER) + threadIdx.x;
 
     if (STAGE) {
@@ -99,7 +112,7 @@ __global__ __launch_bounds__(MP_THREADS) void mesh_pc_kernel(const float* __rest
     mp_pt pt[MP_PER];
     if (!PER_ENV) {
 #pragma unroll
-        for (int u = 0; u < MP_PER; ++u) pt[u] = mp_fetch(pts, part_of, Q, M, sel, e0 + u * MP_THREADS, n3);
+        for (int u = 0; u < MP_PER; ++u) pt[u] = mp_fetch<NF>(pts, part_of, Q, M, sel, labels, e0 + u * MP_THREADS, n3);
     }
     if (STAGE) __syncthreads();
 
@@ -108,7 +121,7 @@ __global__ __launch_bounds__(MP_THREADS) void mesh_pc_kernel(const float* __rest
         float* row = out + b * out_stride;
         if (PER_ENV) {
 #pragma unroll
-            for (int u = 0; u < MP_PER; ++u) pt[u] = mp_fetch(pts, part_of, Q, M, sel + b * sel_stride, e0 + u * MP_THREADS, n3);
+            for (int u = 0; u < MP_PER; ++u) pt[u] = mp_fetch<NF>(pts, part_of, Q, M, sel + b * sel_stride, labels, e0 + u * MP_THREADS, n3);
         }
 #pragma unroll
         for (int u = 0; u < MP_PER; ++u) {
@@ -116,7 +129,9 @@ __global__ __launch_bounds__(MP_THREADS) void mesh_pc_kernel(const float* __rest
             if (e >= n3) continue;
             float v = __builtin_nanf("");
             const int pj = pt[u].pj;
-            if (pj >= 0) {
+            if (NF == 4 && pj == MP_LABEL) {
+                v = pt[u].x0;
+            } else if (pj >= 0) {
                 float r0, r1, r2, t;
                 if (STAGE) {
                     const mp_f4 w = mp_tab[bl * M * 3 + pj];
@@ -132,24 +147,24 @@ __global__ __launch_bounds__(MP_THREADS) void mesh_pc_kernel(const float* __rest
     }
 }
 
-extern "C" int pm_mesh_pc_query_f32(const float* pts, const int32_t* part_of, int Q, const float* pose_R, const float* pose_T,
-                                    int B, int M, const int32_t* sel, long sel_stride, int K, float* out, long out_stride,
-                                    void* stream) {
-    PM_REQUIRE(pts && part_of && pose_R && pose_T && out);
+template <int NF>
+static int mp_query(const float* pts, const int32_t* part_of, int Q, const float* pose_R, const float* pose_T, int B, int M,
+                    const int32_t* sel, long sel_stride, int K, float* out, long out_stride, const float* labels, void* stream) {
+    PM_REQUIRE(pts && part_of && pose_R && pose_T && out && (NF == 3 || labels));
     PM_REQUIRE(B >= 1 && M >= 1 && Q >= 1 && K >= 1 && B <= 65535 * MP_EB);
-    PM_REQUIRE(out_stride >= 3L * K);
+    PM_REQUIRE(out_stride >= (long)NF * K);
     PM_REQUIRE(sel || K == Q);
     PM_REQUIRE(sel_stride == 0 || sel_stride >= K);
-    const long chunks = (3L * K + MP_THREADS * MP_PER - 1) / (MP_THREADS * MP_PER);
+    const long chunks = ((long)NF * K + MP_THREADS * MP_PER - 1) / (MP_THREADS * MP_PER);
     // fewer environments per block while the grid would leave most of the chip idle (same bits: the arithmetic does not change)
     int eb = MP_EB;
     while (eb > 1 && chunks * ((B + eb - 1) / eb) < 1024) eb >>= 1;
     const dim3 grid((unsigned)chunks, (unsigned)((B + eb - 1) / eb)), block(MP_THREADS);
     const bool stage = M <= MP_STAGE_MAX_M, per_env = sel && sel_stride != 0;
     const size_t lds = stage ? (size_t)eb * M * 3 * sizeof(mp_f4) : 0;
-#define MP_LAUNCH(S, P)                                                                                                       \
-    hipLaunchKernelGGL((mesh_pc_kernel<S, P>), grid, block, lds, pm_stream(stream), pts, part_of, Q, pose_R, pose_T, B, M, sel, \
-                       sel_stride, K, eb, out, out_stride)
+#define MP_LAUNCH(S, P)                                                                                                           \
+    hipLaunchKernelGGL((mesh_pc_kernel<NF, S, P>), grid, block, lds, pm_stream(stream), pts, part_of, Q, pose_R, pose_T, B, M, sel, \
+                       sel_stride, K, eb, out, out_stride, labels)
     if (stage && per_env) MP_LAUNCH(true, true);
     else if (stage) MP_LAUNCH(true, false);
     else if (per_env) MP_LAUNCH(false, true);
@@ -157,4 +172,16 @@ extern "C" int pm_mesh_pc_query_f32(const float* pts, const int32_t* part_of, in
 #undef MP_LAUNCH
     PM_CHECK_LAUNCH();
     return PM_OK;
+}
+
+extern "C" int pm_mesh_pc_query_f32(const float* pts, const int32_t* part_of, int Q, const float* pose_R, const float* pose_T,
+                                    int B, int M, const int32_t* sel, long sel_stride, int K, float* out, long out_stride,
+                                    void* stream) {
+    return mp_query<3>(pts, part_of, Q, pose_R, pose_T, B, M, sel, sel_stride, K, out, out_stride, nullptr, stream);
+}
+
+extern "C" int pm_mesh_pc_query_labeled_f32(const float* pts, const int32_t* part_of, int Q, const float* pose_R,
+                                            const float* pose_T, int B, int M, const int32_t* sel, long sel_stride, int K,
+                                            float* out, long out_stride, const float* labels, void* stream) {
+    return mp_query<4>(pts, part_of, Q, pose_R, pose_T, B, M, sel, sel_stride, K, out, out_stride, labels, stream);
 }

@@ -1186,27 +1186,38 @@ extern "C" int pm_tsdf_sparse_gather_f32(const float* coords, const int32_t* idx
 // expression bit for bit (checked against its own output, tests/golden/depth2pc_small.npz):
 //   p0 = ((col - cx) * z) / fx,  p1 = ((row - cy) * z) / fy,  p2 = z   (each op rounded)
 //   w[d] = fma(p2, R[d][2], fma(p1, R[d][1], p0 * R[d][0])) + t[d]      (torch.bmm's K=3 inner product)
+// One pixel of that expression: the world point of depth z at (row, col) of the view whose row-major 4x4 pose is T, zeroed outside
+// the open box.  The ONE statement of the arithmetic: depth_backproject_kernel and depth_cloud_kernel both call it, so the cloud the
+// fused kernel compacts is bit for bit the cloud the two-step path writes.
+struct depth_cam {
+    float fx, fy, cx, cy, lo0, lo1, lo2, hi0, hi1, hi2;
+};
+
+__device__ __forceinline__ void depth_world_point(float z, int row, int col, const float* __restrict__ T, const depth_cam& c,
+                                                  float w[3]) {
+    const float p0 = __fdiv_rn(mul_rn(sub_rn((float)col, c.cx), z), c.fx);
+    const float p1 = __fdiv_rn(mul_rn(sub_rn((float)row, c.cy), z), c.fy);
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+        w[d] = add_rn(__fmaf_rn(z, T[d * 4 + 2], __fmaf_rn(p1, T[d * 4 + 1], mul_rn(p0, T[d * 4]))), T[d * 4 + 3]);
+    const bool ok = w[0] < c.hi0 && w[1] < c.hi1 && w[2] < c.hi2 && w[0] > c.lo0 && w[1] > c.lo1 && w[2] > c.lo2;
+    w[0] = ok ? w[0] : 0.f;
+    w[1] = ok ? w[1] : 0.f;
+    w[2] = ok ? w[2] : 0.f;
+}
+
 __global__ __launch_bounds__(256) void depth_backproject_kernel(const float* __restrict__ depth, long n_per_env,
                                                                  int HW, int W, const float* __restrict__ pose,
-                                                                 float fx, float fy, float cx, float cy, float lo0,
-                                                                 float lo1, float lo2, float hi0, float hi1, float hi2,
-                                                                 long total, float* __restrict__ out) {
+                                                                 depth_cam cam, long total, float* __restrict__ out) {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const long r = e % n_per_env;                     // pixel inside the env: view * HW + pix
         const int m = (int)(r / HW), pix = (int)(r - (long)m * HW);
         const int row = pix / W, col = pix - row * W;
-        const float z = depth[e];
-        const float p0 = __fdiv_rn(mul_rn(sub_rn((float)col, cx), z), fx);
-        const float p1 = __fdiv_rn(mul_rn(sub_rn((float)row, cy), z), fy);
-        const float* T = pose + m * 16;                   // row-major 4x4
         float w[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-            w[d] = add_rn(__fmaf_rn(z, T[d * 4 + 2], __fmaf_rn(p1, T[d * 4 + 1], mul_rn(p0, T[d * 4]))), T[d * 4 + 3]);
-        const bool ok = w[0] < hi0 && w[1] < hi1 && w[2] < hi2 && w[0] > lo0 && w[1] > lo1 && w[2] > lo2;
-        out[e * 3] = ok ? w[0] : 0.f;
-        out[e * 3 + 1] = ok ? w[1] : 0.f;
-        out[e * 3 + 2] = ok ? w[2] : 0.f;
+        depth_world_point(depth[e], row, col, pose + m * 16, cam, w);
+        out[e * 3] = w[0];
+        out[e * 3 + 1] = w[1];
+        out[e * 3 + 2] = w[2];
     }
 }
 
@@ -1218,8 +1229,164 @@ extern "C" int pm_depth_backproject_f32(const float* depth, int B, int M, int H,
     long nb = (total + 255) / 256;
     if (nb > 16384) nb = 16384;
     hipLaunchKernelGGL(depth_backproject_kernel, dim3((unsigned)nb), dim3(256), 0, pm_stream(stream), depth,
-                       (long)M * H * W, H * W, W, cam_pose, fx, fy, cx, cy, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2],
+                       (long)M * H * W, H * W, W, cam_pose, depth_cam{fx, fy, cx, cy, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]},
                        total, out);
+    PM_CHECK_LAUNCH();
+    return PM_OK;
+}
+
+// ---------------------------------------------------------------------------------- depth -> compact cloud + source pixels
+// pm_depth_backproject_f32 followed by pm_depth_compact_f32 in one kernel that never writes the full (B, P, 3) cloud and remembers
+// which pixel every kept point came from (src), which is what a per-pixel image such as the part mask is gathered through.
+// One work-group of 1024 threads per environment, the shape of depth_compact_kernel: pass 1 finds `first`, the lowest pixel whose
+// world point is (0, 0, 0) by value (cropped, or in the box and exactly at the origin); pass 2 is the same stable compaction (wave
+// ballot + popcount, LDS prefix over the 16 waves, a running base per chunk of 1024 pixels) over "non-zero, or first".  w(r) is
+// recomputed in each pass by depth_world_point, not stored: per pixel the kernel reads the depth twice (8 B; 12 pose floats per
+// pixel come from the cache) and writes 16 B per KEPT point, where the pair it replaces moves 4 + 12 read-back + 24 + 12 x kept.
+// Rows at and past lengths[b] = min(count, cap) are not written; pass 2 stops at the round that fills `cap`.
+// Bound: latency, not bandwidth.  A work-group walks its environment's pixels in dependent rounds (load, two IEEE divisions, ballot,
+// two barriers), and B work-groups occupy B of the 256 CUs: at 64 environments a quarter of the chip, one work-group per CU.  Two
+// things measured beyond the plain shape of depth_compact_kernel, ms per call on one MI355X against backproject + compact in the
+// same process (tools/time_depth_cloud.py), shipped rig 3 x 288 x 512 at 64 environments / image rig 1 x 72 x 128 at 1024, the pair
+// taking 0.667 / 0.076: 64-bit pixel index (p / HW as a long division) 0.742 / 0.093 -> 32-bit (P <= INT_MAX) 0.701 / 0.085 ->
+// DC_CHUNKS = 2 chunks of 1024 pixels per pair of barriers (their loads in flight together) 0.632 / 0.085 -> 4 (kept) 0.594 / 0.084
+// -> 8: 0.581 / 0.093 (81 VGPRs).  So 0.89 of the pair on the shipped rig (0.63 at 256 environments, where the pair writes and reads back
+// 2 x 1.36 GB of cloud), 0.92 on the image rig at 64 and 1.12 at 1024 environments of the image rig, where nine
+// rounds per work-group are all there is to overlap.  Order is kept: chunk u of a round holds pixels p0 + 1024 u + tid, and the
+// chunks of a round are placed one after the other.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): 56 VGPRs, 104 SGPRs, no scratch, 260 bytes of LDS, occupancy 7
+// waves / SIMD (one 16-wave work-group per CU).  No atomics on global memory (one LDS atomicMin per wave in pass 1), no workspace,
+// stream-ordered.
+#ifndef DC_CHUNKS
+#define DC_CHUNKS 4                                          // chunks of 1024 pixels per pair of barriers in pass 2
+#endif
+
+// pixel p (< P <= INT_MAX, so 32-bit divisions) of an environment -> its world point
+__device__ __forceinline__ void depth_cloud_point(const float* __restrict__ dep, int p, int HW, int W, const float* __restrict__ pose,
+                                                  const depth_cam& cam, float w[3]) {
+    const int m = p / HW, pix = p - m * HW;
+    const int row = pix / W;
+    depth_world_point(dep[p], row, pix - row * W, pose + m * 16, cam, w);
+}
+
+__global__ __launch_bounds__(1024) void depth_cloud_kernel(const float* __restrict__ depth, int P, int HW, int W,
+                                                            const float* __restrict__ pose, depth_cam cam, int cap,
+                                                            float* __restrict__ xyz, int32_t* __restrict__ src,
+                                                            int32_t* __restrict__ lengths) {
+    __shared__ int wcnt[DC_CHUNKS][16];
+    __shared__ int s_first;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* dep = depth + (long)b * P;
+    float* dst = xyz + (long)b * cap * 3;
+    int32_t* sdst = src ? src + (long)b * cap : nullptr;
+    if (tid == 0) s_first = 0x7fffffff;
+    __syncthreads();
+    int first = 0x7fffffff;
+    for (long p = tid; p < P; p += 1024) {                   // (the counter is 64-bit: p + 1024 may pass INT_MAX; a pixel never does)
+        float w[3];
+        depth_cloud_point(dep, (int)p, HW, W, pose, cam, w);
+        if (w[0] == 0.f && w[1] == 0.f && w[2] == 0.f) {
+            first = (int)p;                               // ascending p per thread: the first hit is the thread's minimum
+            break;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+    if (lane == 0 && first != 0x7fffffff) atomicMin(&s_first, first);
+    __syncthreads();
+    first = s_first;
+    int base = 0;
+    // base is the same in every thread: the whole block leaves together, at the round that fills `cap`
+    for (long p0 = 0; p0 < P && base < cap; p0 += 1024 * DC_CHUNKS) {
+        float w[DC_CHUNKS][3];
+        bool keep[DC_CHUNKS];
+        int within[DC_CHUNKS];
+#pragma unroll
+        for (int u = 0; u < DC_CHUNKS; ++u) {
+            const long p = p0 + u * 1024 + tid;
+            keep[u] = false;
+            w[u][0] = w[u][1] = w[u][2] = 0.f;
+            if (p < P) {
+                depth_cloud_point(dep, (int)p, HW, W, pose, cam, w[u]);
+                keep[u] = (w[u][0] != 0.f || w[u][1] != 0.f || w[u][2] != 0.f) || (int)p == first;
+            }
+            const unsigned long long mk = __ballot(keep[u]);
+            within[u] = __popcll(mk & ((1ull << lane) - 1ull));
+            if (lane == 0) wcnt[u][wave] = __popcll(mk);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < DC_CHUNKS; ++u) {
+            int before = 0, total = 0;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int c = wcnt[u][v];
+                before += (v < wave) ? c : 0;
+                total += c;
+            }
+            const int q = base + before + within[u];      // <= P: fits an int
+            if (keep[u] && q < cap) {
+                dst[(long)q * 3] = w[u][0]; dst[(long)q * 3 + 1] = w[u][1]; dst[(long)q * 3 + 2] = w[u][2];
+                if (sdst) sdst[q] = (int32_t)(p0 + u * 1024 + tid);
+            }
+            base += total;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) lengths[b] = min(base, cap);
+}
+
+extern "C" int pm_depth_cloud_f32(const float* depth, int B, int M, int H, int W, const float* cam_pose, float fx, float fy,
+                                  float cx, float cy, const float* lo, const float* hi, int cap, float* xyz, int32_t* src,
+                                  int32_t* lengths, void* stream) {
+    PM_REQUIRE(depth && cam_pose && lo && hi && xyz && lengths && B > 0 && M > 0 && H > 0 && W > 0 && cap > 0);
+    const long P = (long)M * H * W;
+    PM_REQUIRE((long)H * W <= 0x7fffffffL && P <= 0x7fffffffL);
+    hipLaunchKernelGGL(depth_cloud_kernel, dim3(B), dim3(1024), 0, pm_stream(stream), depth, (int)P, H * W, W, cam_pose,
+                       depth_cam{fx, fy, cx, cy, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]}, cap, xyz, src, lengths);
+    PM_CHECK_LAUNCH();
+    return PM_OK;
+}
+
+// out[b, 4k..4k+3] = (x, y, z, label) of point i = idx[b, k] of the compact cloud: the label is seg at the pixel the point came from,
+// or zero_label for THE zero point (the one point that stands for every cropped or missed pixel: its pixel is whichever came first,
+// so its label would mean nothing).  One lane owns one output float, as in mesh_pc_kernel: a wave stores 256 contiguous bytes at any
+// row alignment.  i outside [0, ld): four NaN, nothing read through i; src outside [0, P): a NaN label, seg not read.  Columns at
+// and past 4K of a row are never written.  A latency-bound gather of B * 4K floats (1 MB at 64 environments of 1024 points).
+// Resources (gfx950): 16 VGPRs, 46 SGPRs, no scratch, no LDS, occupancy 8 waves / SIMD.
+__global__ __launch_bounds__(256) void cloud_gather_labeled_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ src,
+                                                                    int B, int ld, const int32_t* __restrict__ idx, int K,
+                                                                    const int32_t* __restrict__ seg, long seg_stride, int P,
+                                                                    float zero_label, float* __restrict__ out, long out_stride) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= 4L * K) return;
+    const int k = (int)(e >> 2), j = (int)(e & 3);
+    for (long b = blockIdx.y; b < B; b += gridDim.y) {
+        const int i = idx[b * K + k];
+        float v = __builtin_nanf("");
+        if (i >= 0 && i < ld) {
+            const float* pt = xyz + (b * ld + i) * 3;
+            if (j < 3) {
+                v = pt[j];
+            } else if (pt[0] == 0.f && pt[1] == 0.f && pt[2] == 0.f) {
+                v = zero_label;
+            } else {
+                const int s = src[b * ld + i];
+                if (s >= 0 && s < P) v = (float)seg[b * seg_stride + s];
+            }
+        }
+        out[b * out_stride + e] = v;
+    }
+}
+
+extern "C" int pm_cloud_gather_labeled_f32(const float* xyz, const int32_t* src, int B, int ld, const int32_t* idx, int K,
+                                           const int32_t* seg, long seg_stride, int P, float zero_label, float* out,
+                                           long out_stride, void* stream) {
+    PM_REQUIRE(xyz && src && idx && seg && out && B > 0 && ld > 0 && K > 0 && P > 0);
+    PM_REQUIRE(out_stride >= 4L * K && seg_stride >= P);
+    const dim3 grid((unsigned)((4L * K + 255) / 256), (unsigned)(B < 65535 ? B : 65535));
+    hipLaunchKernelGGL(cloud_gather_labeled_kernel, grid, dim3(256), 0, pm_stream(stream), xyz, src, B, ld, idx, K, seg,
+                       seg_stride, P, zero_label, out, out_stride);
     PM_CHECK_LAUNCH();
     return PM_OK;
 }

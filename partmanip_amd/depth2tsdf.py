@@ -73,6 +73,36 @@ class TSDFVolume(object):
         idx = ops.fps_varlen(compact, lengths, K, self._ws)                        # (b, K) int32 into `compact`
         return ops.group_points(compact, idx.view(idx.shape[0], K, 1)).view(idx.shape[0], K, 3)
 
+    def depth2pc_masked(self, depth_im, seg, K=1024, out=None, cap=None, zero_label=0.0):
+        """depth_im (b, m, h, w) float32 and seg (b, m, h, w) int32 (DepthFromMesh.render_frame's images), contiguous on the device ->
+        (b, K, 4) rows (x, y, z, label): depth2pc's cloud, bit for bit, with the seg value of the pixel each point came from.  The
+        point (0, 0, 0), which stands for every pixel outside the workspace, gets zero_label.  One launch goes from the depth images
+        to the compact cloud and its source pixels (ops.depth_cloud: the full world cloud is never written), then the sampler as
+        depth2pc calls it, then ops.cloud_gather_labeled.  cap: rows kept per environment before the sampling (default: every pixel);
+        an environment with more points than cap inside the workspace loses those past the first cap -- the caller's bound on
+        memory, b * cap * 16 bytes.  out: None, or a 2-D float32 view (b, >= 4K) with unit inner stride (the head of an
+        observation row); the result is then a view of its first 4K columns."""
+        if tuple(depth_im.shape) != tuple(self.registered_shape):
+            raise ValueError(f"depth_im: expected the registered shape {tuple(self.registered_shape)}, got {tuple(depth_im.shape)}")
+        if not torch.is_tensor(seg) or seg.dtype != torch.int32 or tuple(seg.shape) != tuple(depth_im.shape) or not seg.is_contiguous():
+            raise ValueError(f"seg: expected a contiguous int32 tensor {tuple(depth_im.shape)}, got "
+                             f"{getattr(seg, 'dtype', type(seg))} {tuple(getattr(seg, 'shape', ()))}")
+        K = int(K)
+        if K < 1:
+            raise ValueError(f"K: expected a positive point count, got {K}")
+        b = depth_im.shape[0]
+        if out is not None:
+            ops._out_rows(out, b, 4 * K)                                            # a bad view is reported before the device
+        intr = self.cam_intr
+        cam_cx, cam_cy = float(intr[0][2]), float(intr[1][2])                       # as in depth2pc
+        cam_fx, cam_fy = float(intr[0][0]), float(intr[1][1])
+        lo = self._vol_origin.cpu().numpy().astype(np.float32)
+        hi = (np.float32(self._size) + lo).astype(np.float32)
+        xyz, src, lengths = ops.depth_cloud(depth_im.float().contiguous(), self.cam_pose, cam_fx, cam_fy, cam_cx, cam_cy, lo, hi, cap=cap)
+        idx = ops.fps_varlen(xyz, lengths, K, self._ws)
+        res = ops.cloud_gather_labeled(xyz, src, idx, seg, zero_label=zero_label, out=out)
+        return res[:, :4 * K].unflatten(1, (K, 4))
+
     def integrate(self, depth_im):
         """depth_im (b, m, h, w) -> TSDF volume (b, res, res, res) (depth2tsdf.py:68-86)."""
         assert tuple(depth_im.shape) == tuple(self.registered_shape)

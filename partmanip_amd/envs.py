@@ -35,15 +35,16 @@ class _Observer:
         self.width, self.write = int(width), write
 
 
-def pc_observer(pc, sel=None):
+def pc_observer(pc, sel=None, mask=False):
     """mesh2pc.PCfromMesh -> 3 * num_points columns.  sel (K) int32 on the device: the subset of the scene's points, drawn once here
     from torch's CPU generator where None (the reference draws one per call; a fixed one keeps the step free of host work).  A cloud
-    built with groups= gives its own default, pc.group_sel(): (N, K) rows, every environment's from its own cabinet's cloud."""
+    built with groups= gives its own default, pc.group_sel(): (N, K) rows, every environment's from its own cabinet's cloud.
+    mask=True: 4 * num_points columns, rows (x, y, z, pc.labels[part])."""
     if sel is None and getattr(pc, "groups", False):
         sel = pc.group_sel()
     elif sel is None:
         sel = torch.randperm(pc.pts.shape[0])[:pc.num_points].to(torch.int32).to(pc.device)
-    obs = _Observer(3 * sel.shape[-1], lambda R, T, out: pc.query_pc(R, T, out=out, sel=sel))
+    obs = _Observer((4 if mask else 3) * sel.shape[-1], lambda R, T, out: pc.query_pc(R, T, out=out, sel=sel, mask=bool(mask)))
     obs.sel = sel
     return obs
 
@@ -54,9 +55,18 @@ def tsdf_observer(tsdf):
     return _Observer(res ** 3, lambda R, T, out: tsdf.query_tsdf(R, T, out=out))
 
 
-def depth_pc_observer(cam, volume, num_points=1024):
+def depth_pc_observer(cam, volume, num_points=1024, mask=False, zero_label=0.0):
     """mesh2depth.DepthFromMesh and a depth2tsdf.TSDFVolume with the same cameras registered -> 3 * num_points columns: the rendered
-    depth images back-projected and thinned (depth2pc returns its own tensor, so this one copies into the row)."""
+    depth images back-projected and thinned (depth2pc returns its own tensor, so this one copies into the row).
+    mask=True: 4 * num_points columns, rows (x, y, z, label): one render_frame gives the depth and the part image (cam's labels),
+    and depth2pc_masked writes the sampled rows straight into the observation row (no copy); zero_label: the label of the point
+    (0, 0, 0) that stands for everything outside the workspace."""
+    if mask:
+        def write_masked(R, T, out):
+            frame = cam.render_frame(R, T, depth=True, seg=True, rgb=False)
+            volume.depth2pc_masked(frame.depth, frame.seg, K=num_points, out=out, zero_label=zero_label)
+        return _Observer(4 * num_points, write_masked)
+
     def write(R, T, out):
         out[:, :3 * num_points].copy_(volume.depth2pc(cam.render(R, T), K=num_points).reshape(out.shape[0], -1))
     return _Observer(3 * num_points, write)

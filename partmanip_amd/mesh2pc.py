@@ -51,11 +51,15 @@ class PCfromMesh:
     torch.Generator().manual_seed(seed + GROUP_SEED_STRIDE * (k + 1) + j).  group_of (num_envs,) ints in [-1, len(groups)): the object
     each environment holds, -1 for none (default: env % len(groups), the reference's rule).  part_num is then num_shared + the
     largest body count; attributes: num_shared, pts_shared (the shared rows of pts), group_off (numpy, rows of pts relative to
-    pts_shared), group_of (numpy), max_group_points.  With groups, `meshes` may be empty."""
+    pts_shared), group_of (numpy), max_group_points.  With groups, `meshes` may be empty.
+    labels: None, or part_num numbers, the value query_pc(mask=True) puts in a point's fourth column, by pose SLOT (None: the slot
+    index); with groups= slot num_shared + j is body j of whichever object the environment holds, so a label there names "body j",
+    not a particular cabinet's link.  Kept as float32 on the device (`labels`)."""
 
     GROUP_SEED_STRIDE = 4096
 
-    def __init__(self, num_envs, device, num_points=1024, asset_root='.', meshes=None, part_pcs=None, seed=0, groups=None, group_of=None):
+    def __init__(self, num_envs, device, num_points=1024, asset_root='.', meshes=None, part_pcs=None, seed=0, groups=None, group_of=None,
+                 labels=None):
         self.num_envs = num_envs
         self.device = device
         self.num_points = int(num_points)
@@ -81,12 +85,22 @@ class PCfromMesh:
         self.last_sel = None
         if self.groups:
             self._init_groups(pcs, groups, group_of)
+            self._init_labels(labels)
             return
+        self._init_labels(labels)
         self.part_pc = torch.from_numpy(pcs).to(self.device)                                   # (m, p, 3)
         self.pts = self.part_pc.view(-1, 3)                                                    # (m p, 3), the same memory
         self.part_of = torch.arange(self.part_num, dtype=torch.int32).repeat_interleave(self.points_per_part).to(self.device)
         self._full = None                                                                      # scratch of select='fps'
         self._fps_ws = None
+
+    def _init_labels(self, labels):
+        """labels (part_num,) float32 on the device: the given numbers, or the slot index."""
+        m = self.part_num
+        lab = np.arange(m) if labels is None else np.asarray(labels.cpu().numpy() if torch.is_tensor(labels) else labels)
+        if lab.shape != (m,) or lab.dtype.kind not in "iuf":
+            raise ValueError(f"labels: expected {m} numbers, one per part, got {lab.dtype} {lab.shape}")
+        self.labels = torch.from_numpy(np.ascontiguousarray(lab, dtype=np.float32)).to(self.device)
 
     def _init_groups(self, pcs, groups, group_of):
         """The point library of a scene whose environments differ: the shared parts' points, then every object's bodies."""
@@ -183,8 +197,9 @@ class PCfromMesh:
         (600 MB at 4096 environments); nothing here reads it."""
         return self.part_pc.unsqueeze(0).repeat(self.num_envs, 1, 1, 1).reshape(-1, self.points_per_part, 3)
 
-    def query_pc(self, pose_R, pose_T, out=None, sel=None, select='random', group_of=None):
-        """pose_R [b, m, 3, 3], pose_T [b, m, 3] (any b) -> [b, K, 3].
+    def query_pc(self, pose_R, pose_T, out=None, sel=None, select='random', group_of=None, mask=False):
+        """pose_R [b, m, 3, 3], pose_T [b, m, 3] (any b) -> [b, K, 3]; mask=True: [b, K, 4], the fourth column labels[part] of the
+        point (pm_mesh_pc_query_labeled_f32), the first three the same bits; out then needs >= 4K columns.
         select='random' (the reference): the first num_points entries of torch.randperm(m p) from the CPU global generator, one
         subset for all environments (mesh2pc.py:63-64).  select='all': every point, K = m p.  select='fps': the posed cloud of all
         points is thinned to num_points per environment by farthest-point sampling (ops.fps, start index 0), so large parts are
@@ -195,6 +210,7 @@ class PCfromMesh:
         environment's own points; 'fps' is refused; sel keeps its meaning (rows of pts).  b = num_envs, or group_of= (b,) names the
         object of each row of this call."""
         Q = self.pts.shape[0]
+        nf = 4 if mask else 3
         b, _ = ops.check_poses(pose_R, pose_T, self.part_num)
         if group_of is not None and not self.groups:
             raise ValueError("group_of: this cloud was built without groups=")
@@ -212,7 +228,7 @@ class PCfromMesh:
         else:
             K = Q if select == 'all' else min(self.num_points, Q)
         if out is not None:
-            ops._out_rows(out, b, 3 * K)                                                       # a bad view is reported before the device and any launch
+            ops._out_rows(out, b, nf * K)                                                      # a bad view is reported before the device and any launch
         env = self._call_groups(b, group_of) if self.groups and sel is None else None          # ... and so is a slice without its group_of
         ops._req(pose_R, pose_T, sel, out, self.pts)
         pose_R, pose_T = pose_R.contiguous(), pose_T.contiguous()
@@ -229,6 +245,6 @@ class PCfromMesh:
                 self._fps_ws = ops.Workspace(pose_R.device)
             ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, None, self._full)
             sel = ops.fps(self._full.view(b, Q, 3), self.num_points, self._fps_ws)
-        res = ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, sel, out)
+        res = ops.mesh_pc_query(self.pts, self.part_of, pose_R, pose_T, sel, out, labels=self.labels if mask else None)
         self.last_sel = sel
-        return res[:, :3 * K].unflatten(1, (K, 3))
+        return res[:, :nf * K].unflatten(1, (K, nf))

@@ -1470,6 +1470,79 @@ def depth_backproject(depth, cam_pose, fx, fy, cx, cy, lo, hi):
     return out
 
 
+def depth_cloud(depth, cam_pose, fx, fy, cx, cy, lo, hi, cap=None, want_src=True):
+    """depth_compact(depth_backproject(...)) in one launch that never writes the (B, P, 3) world cloud (pm_depth_cloud_f32):
+    depth (B, M, H, W), cam_pose (M, 4, 4) -> (xyz (B, cap, 3), src (B, cap) int32 or None, lengths (B) int32).  xyz[b, :lengths[b]]
+    are the non-zero world points plus the first zero one, in pixel order, src their pixels r = view * H W + row * W + col; rows at
+    and past lengths[b] are not written.  cap (default P = M H W): the rows kept per environment; fewer than an environment's count
+    truncates its cloud to the first cap points.  want_src=False: no src buffer."""
+    import ctypes
+    for t_, name, nd in ((depth, "depth", 4), (cam_pose, "cam_pose", 3)):
+        if not torch.is_tensor(t_) or t_.dim() != nd or 0 in t_.shape:
+            raise ValueError(f"{name}: expected a non-empty {nd}-D tensor, got {tuple(t_.shape) if torch.is_tensor(t_) else type(t_)}")
+        _f32c(t_, name)
+    B, M, H, W = depth.shape
+    if tuple(cam_pose.shape) != (M, 4, 4):
+        raise ValueError(f"cam_pose: expected ({M}, 4, 4), got {tuple(cam_pose.shape)}")
+    P = M * H * W
+    if P > 2 ** 31 - 1:
+        raise ValueError(f"depth: {P} pixels per environment, more than 2^31 - 1")
+    cap = P if cap is None else int(cap)
+    if cap < 1:
+        raise ValueError(f"cap: expected a positive row count, got {cap}")
+    box = [np.asarray(v, dtype=np.float32).reshape(-1) for v in (lo, hi)]
+    if box[0].size != 3 or box[1].size != 3:
+        raise ValueError("lo, hi: expected three numbers each")
+    _one_device("depth_cloud", depth, cam_pose)
+    xyz = torch.empty(B, cap, 3, dtype=torch.float32, device=depth.device)
+    src = torch.empty(B, cap, dtype=torch.int32, device=depth.device) if want_src else None
+    lengths = torch.empty(B, dtype=torch.int32, device=depth.device)
+    lo3, hi3 = ((ctypes.c_float * 3)(*[float(v) for v in a]) for a in box)
+    with TIMER.bracket("depth_cloud"):
+        check(lib.pm_depth_cloud_f32(_ptr(depth), B, M, H, W, _ptr(cam_pose), float(fx), float(fy), float(cx), float(cy),
+                                     ctypes.cast(lo3, ctypes.c_void_p), ctypes.cast(hi3, ctypes.c_void_p), cap, _ptr(xyz), _ptr(src),
+                                     _ptr(lengths), _stream()), "pm_depth_cloud_f32")
+    return xyz, src, lengths
+
+
+def cloud_gather_labeled(xyz, src, idx, seg, zero_label=0.0, out=None):
+    """Rows (x, y, z, label) of the sampled points of a depth_cloud (pm_cloud_gather_labeled_f32): xyz (B, ld, 3), src (B, ld) int32,
+    idx (B, K) int32 into them, seg: int32 labels per pixel, (B, ...) contiguous or a 2-D view (B, P) with unit inner stride.  The
+    label of point i is seg[b, src[b, i]], or zero_label for the point (0, 0, 0); an idx outside [0, ld) gives four NaN, a src
+    outside [0, P) a NaN label.  out: None (a fresh (B, 4K)) or a 2-D float32 view (B, >= 4K) with unit inner stride -- columns past
+    4K are left alone.  Returns out."""
+    for t_, name in ((xyz, "xyz"), (src, "src"), (idx, "idx"), (seg, "seg")):
+        if not torch.is_tensor(t_):
+            raise ValueError(f"{name}: expected a tensor, got {type(t_)}")
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or 0 in xyz.shape:
+        raise ValueError(f"xyz: expected (B, ld > 0, 3), got {tuple(xyz.shape)}")
+    _f32c(xyz, "xyz")
+    B, ld, _ = xyz.shape
+    if src.dtype != torch.int32 or not src.is_contiguous() or tuple(src.shape) != (B, ld):
+        raise ValueError(f"src: expected a contiguous int32 tensor ({B}, {ld}), got {src.dtype} {tuple(src.shape)}")
+    if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.dim() != 2 or idx.shape[0] != B or idx.shape[1] == 0:
+        raise ValueError(f"idx: expected a contiguous int32 tensor ({B}, K > 0), got {idx.dtype} {tuple(idx.shape)}")
+    K = idx.shape[1]
+    if seg.dtype != torch.int32 or seg.dim() < 2 or seg.shape[0] != B or 0 in seg.shape:
+        raise ValueError(f"seg: expected an int32 tensor ({B}, ...), got {seg.dtype} {tuple(seg.shape)}")
+    if seg.dim() == 2 and (seg.shape[1] == 1 or seg.stride(1) == 1) and (B == 1 or seg.stride(0) >= seg.shape[1]):
+        P, seg_stride = seg.shape[1], (seg.stride(0) if B > 1 else seg.shape[1])
+    elif seg.is_contiguous():
+        P = seg_stride = seg[0].numel()
+    else:
+        raise ValueError(f"seg: expected a contiguous tensor or a 2-D view with unit inner stride, got {tuple(seg.shape)} {seg.stride()}")
+    if P > 2 ** 31 - 1:
+        raise ValueError(f"seg: {P} pixels per environment, more than 2^31 - 1")
+    if out is not None:
+        _out_rows(out, B, 4 * K)
+    _one_device("cloud_gather_labeled", xyz, src, idx, seg, out)
+    out, ldo = _out_rows(out, B, 4 * K, xyz.device)
+    with TIMER.bracket("cloud_gather_labeled"):
+        check(lib.pm_cloud_gather_labeled_f32(_ptr(xyz), _ptr(src), B, ld, _ptr(idx), K, _ptr(seg), seg_stride, P, float(zero_label),
+                                              _ptr(out), ldo, _stream()), "pm_cloud_gather_labeled_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------- Conv3D students
 def conv3d_out(n, k, stride, pad):
     return (n + 2 * pad - k) // stride + 1
@@ -1634,12 +1707,14 @@ def mesh_tsdf_query_groups(fields, part_off, part_shape, part_bbox_min, part_vox
     return out
 
 
-def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None):
+def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None, labels=None):
     """The posed mesh point cloud (pm_mesh_pc_query_f32): pts (Q, 3) canonical surface points, part_of (Q) int32, pose_R (B, M, 3, 3),
     pose_T (B, M, 3); sel: None (every point, K = Q), (K) int32 shared by all environments or (B, K) int32 with unit inner stride.
     out: None (a fresh (B, 3K)) or a 2-D float32 view (B, >= 3K) with unit inner stride -- columns past 3K are left alone.
-    Returns out; out[b, 3k + j] = coordinate j of point pts[sel[.., k]] under the pose of its part in environment b."""
-    _one_device("mesh_pc_query", pts, part_of, pose_R, pose_T, sel, out)
+    Returns out; out[b, 3k + j] = coordinate j of point pts[sel[.., k]] under the pose of its part in environment b.
+    labels: None, or (M) float32, one number per pose slot: the rows are then 4K wide (pm_mesh_pc_query_labeled_f32), out[b, 4k + j]
+    the coordinates as above and out[b, 4k + 3] = labels[part_of[sel[.., k]]]."""
+    _one_device("mesh_pc_query", pts, part_of, pose_R, pose_T, sel, out, labels)
     for t_, name in ((pts, "pts"), (pose_R, "pose_R"), (pose_T, "pose_T")):
         _f32c(t_, name)
     if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
@@ -1660,6 +1735,15 @@ def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None):
             sel_stride = sel.stride(0) if B > 1 else K
             if sel.shape[0] != B or sel_stride < K:
                 raise ValueError(f"sel: expected ({B}, K) with row stride >= K, got {tuple(sel.shape)} {sel.stride()}")
+    if labels is not None:
+        _f32c(labels, "labels")
+        if tuple(labels.shape) != (M,):
+            raise ValueError(f"labels: expected ({M},), one number per pose slot, got {tuple(labels.shape)}")
+        out, ldo = _out_rows(out, B, 4 * K, pose_R.device)
+        with TIMER.bracket("mesh_pc_query_labeled"):
+            check(lib.pm_mesh_pc_query_labeled_f32(_ptr(pts), _ptr(part_of), Q, _ptr(pose_R), _ptr(pose_T), B, M, _ptr(sel), sel_stride,
+                                                   K, _ptr(out), ldo, _ptr(labels), _stream()), "pm_mesh_pc_query_labeled_f32")
+        return out
     out, ldo = _out_rows(out, B, 3 * K, pose_R.device)
     with TIMER.bracket("mesh_pc_query"):
         check(lib.pm_mesh_pc_query_f32(_ptr(pts), _ptr(part_of), Q, _ptr(pose_R), _ptr(pose_T), B, M, _ptr(sel), sel_stride, K,
