@@ -206,7 +206,7 @@ int pm_pointnet_enc_fwd_f32(const float* x, long ldx, int B, int P, int C, int s
                             void* stream);
 /* Screened tanh forward (csrc/pointnet_enc_screen.h): same contract as pm_pointnet_enc_fwd_f32 with act = PM_ACT_TANH and the
  * same fp32 result class.  Layers 1-2 are the dense kernel's (h2_save bit-identical); layer 3 is screened per 64-point tile on
- * split-bf16 MFMAs with a rigorous per-channel error bound, and only the points that can still be a channel's maximum get
+ * one fp16 MFMA product with a rigorous per-channel error bound, and only the points that can still be a channel's maximum get
  * their exact fp32 dot product; the mean is W3 * mean(h2) + b3.  `packed` as above (layer 2, and layer 3 of the dense
  * fallback); `packed_screen` = pm_pointnet_packed_screen_bytes() bytes written by pm_pointnet_pack_weights_screen from the
  * current W3 / b3 (16-byte aligned).  counters: NULL, or three device uint64 the kernel ADDS to (survivors evaluated, (wave,

@@ -340,7 +340,7 @@ class PointNet(_HipNet):
             raise NotImplementedError(f"PointNet precision '{self.precision}' / precision_bwd '{self.precision_bwd}' is a tanh "
                                       f"kernel; activation '{act}' runs on 'f32'")
         # 'screen' (not a reference key; environment PARTMANIP_PN_SCREEN=0|1 overrides it for A/B in one build): the 'f32' tanh
-        # forward screens layer 3 on split-bf16 MFMAs and finishes the pooling's winners in exact fp32
+        # forward screens layer 3 with one fp16 MFMA product (W3 rows scaled by exact powers of two) and finishes the pooling's winners in exact fp32
         # (csrc/pointnet_enc_screen.h) instead of running layer 3 densely; other activations always run the dense kernel
         # (their h2 is unbounded, the screen's error bound needs |h2| <= 1).  `screen_counters`: None, or a 3 x int64 device
         # tensor the screened kernel adds its survivor / fallback counts to (tests, tools/time_enc.py).

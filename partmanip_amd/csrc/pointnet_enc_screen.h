@@ -5,9 +5,10 @@
 // Layer 3 is linear and feeds a max and a mean over the cloud's points:
 //   mean_p(W3 h2[p] + b3) = W3 mean_p(h2[p]) + b3        one 256 x 512 matrix-vector product per cloud;
 //   max_p                                                 only the winning point of every channel matters.
-// Per 64-point tile the kernel computes an APPROXIMATE layer 3 on split-bf16 MFMAs (hi = bf16(x), lo = bf16(x - hi);
-// z~ = b3 + hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16: 192 MFMAs of 32 cycles per wave against 512 of 64),
-// and with a rigorous per-channel bound eps_c >= |z~ - z^| (z^ = the fp32 dot product below) keeps only the points
+// Per 64-point tile the kernel computes an APPROXIMATE layer 3 as ONE fp16 product (h16 = fp16(h2), w16 = fp16(2^s_c W3[c]),
+// both round-to-nearest-even; z~ = fmaf(sum_k w16 h16, 2^-s_c, b3) with the sum on v_mfma_f32_32x32x16_f16: 64 MFMAs of 32
+// cycles per wave against 512 of 64), and with a rigorous per-channel bound eps_c >= |z~ - z^| (z^ = the fp32 dot product
+// below) keeps only the points
 //   !(z~ < m~ - 2 eps_c)   and   !(z~ + eps_c <= vmax)           m~ = tile maximum of z~, vmax = running exact maximum
 // Both tests are written negated, so a NaN or infinite z~ / eps / vmax lands on the survivor side.  A skipped point p
 // has z^_p <= z~_p + eps < m~ - eps <= z^_q for the tile's q = argmax z~ (or z^_p <= vmax): it can neither beat nor tie.
@@ -19,37 +20,64 @@
 // fp32 layer 3 of pn_fwd_kernel for that tile instead: such a tile costs the dense layer 3 PLUS the screen it already ran,
 // at this kernel's two waves per SIMD (a batch of all-equal clouds is timed in profiles/round7_pointnet_screen.md).
 //
-// eps_c (ps_pack_kernel).  With |h| <= 1 under tanh, S = sum_k |w_ck| |h_k| <= ||W3[c]||_1 =: L.
-//   split:  x = hi + lo + d, |lo| <= 2^-9 |x| (1 + 2^-9), |d| <= 2^-18 |x|; the products dropped from w h are
-//           w_lo h_lo + d_w h + w d_h (+ higher order) <= 3 * 2^-18 (1 + 2^-8) |w||h|          -> 4 * 2^-18 L taken
-//   z~:     769 terms (bias + 3 x 256 exact bf16 products, sum of magnitudes <= (1 + 2^-8) L + |b3|) accumulated in fp32 in
-//           the matrix unit's own order; one rounding of at most 2^-23 relative per accumulation (covers round-to-nearest
-//           and truncation)                                                                    -> 1538 * 2^-24 (L + |b3|)
-//   z^:     256 fmaf + 3 butterfly adds + the bias add, round-to-nearest                       -> 260 * 2^-24 (L + |b3|)
-//   eps_c = (2^-16 + 2048 * 2^-24) * (L + |b3_c|) * (1 + 2^-10), evaluated in double and rounded up to float
-// (the last factor covers the rounding of L itself).  The CPU emulation of the screen used 3 * 2^-18 + 1100 * 2^-24 and saw
-// errors 200x below it.
+// eps_c (ps_pack_kernel).  With |h| <= 1 under tanh, S = sum_k |w_ck| |h_k| <= ||W3[c]||_1 =: L.  Row c is scaled by the exact
+// power of two 2^s (s = s_c: the row's largest finite magnitude lands in [2^14, 2^15), so no finite weight overflows fp16's
+// 65504; s <= 126, which is also what an all-zero / all-non-finite row gets); x' = 2^s w below, and everything up to the
+// un-scaling is in that domain.  The bound is written for a matrix unit that FLUSHES fp16 subnormal inputs; one that keeps
+// them only has smaller operand errors, so it covers both.
+// fp16 has 11 significant bits: round-to-nearest leaves up to 2^-11 RELATIVE (half an ulp of 2^-10), which over both operands
+// would be 2^-10 L.  Both halves are taken tighter, from what is known:
+//   w:      w' = w16 + r_w.  The pack step HAS the weights: R = sum_k rho_k with rho_k = |w' - w16| (exact in fp32) where w16 is
+//           normal, and max(|w'|, |w' - w16|) where it is subnormal or zero (kept, or flushed to zero), is the row's own
+//           rounding residual, whatever the conversion's rounding mode: |sum_k r_w h| <= R  (about 0.36 * 2^-11 2^s L for
+//           weights with random mantissas).  This also holds the flushed-subnormal weights; no separate absolute term.
+//   h:      h = h16 + r_h under v_cvt_pk_f16_f32, round to nearest even in the default mode (not the truncating v_cvt_pkrtz;
+//           the instruction is in the .s).  |h| <= 1: in [2^-1, 1) an ulp is 2^-11, so |r_h| <= 2^-12 ABSOLUTE there and
+//           less in every lower binade; 1 is exact; below 2^-14 the operand is kept or flushed, |r_h| <= 2^-14.  So
+//           |r_h| <= 2^-12 everywhere (also for a tanh that overshoots 1 by a few ulp: it rounds to 1), and
+//           |sum_k w16 r_h| <= 2^-12 S16,  S16 = sum_k |w16| <= (1 + 2^-11) 2^s L
+//   sum:    256 products of fp16 values, each exact in fp32 (11 x 11 bits), of total magnitude <= S16, accumulated in fp32
+//           from zero in the matrix unit's own order; one rounding of at most 2^-23 relative per accumulation (covers
+//           round-to-nearest and truncation); no product is below 2^-48, so nothing underflows      -> 513 * 2^-24 L
+//   z~:     fmaf(sum, 2^-s, b3): the product is exact, ONE rounding of |z~| <= (1 + 2^-10)(L + |b3|)  -> 2 * 2^-24 (L + |b3|)
+//   tests:  m~ - 2 eps and z~ + eps each round once, |.| <= (1 + 2^-9)(L + |b3|)                    -> 4 * 2^-24 (L + |b3|)
+//   z^:     256 fmaf + 3 butterfly adds + the bias add, round-to-nearest                            -> 260 * 2^-24 (L + |b3|)
+//   fp32 underflow of z~ and of the 260 steps of z^ (each <= 2^-126 if flushed)                     -> 2^-116       (absolute)
+//   eps_c = ((R + 2^-12 S16) 2^-s + 1024 * 2^-24 (L + |b3_c|)) (1 + 2^-10) + 2^-116, in double, rounded up to float
+// 779 of the 1024 units of 2^-24 are used above; the rest and the factor 1 + 2^-10 cover the roundings of the three sums
+// themselves, a 2^s w that underflows fp32 for s < 0 (<= 2^-132 L) and a tanh a few ulp above 1.  R, L, and with them eps_c,
+// are inf / NaN for a row that holds an inf / NaN: every test is then false and every point of the channel survives
+// (z~ = -inf, eps = inf: -inf < m~ - inf is false, -inf + inf = NaN <= vmax is false).  tests/test_pointnet_screen_bound.py
+// holds the formula against an emulation of z~ (subnormals kept and flushed, random and worst-sign accumulation orders,
+// operands at fp16 rounding midpoints with aligned signs).
+// For default-initialised weights eps_c is about 4.8e-4 (L + |b3|), 3.5 x the three-product split-bf16 screen's this replaces,
+// for a third of its MFMAs and half its LDS planes; results are the same bit for bit, since every survivor goes through the
+// one exact finish above.  Measured (profiles/round10_pointnet_screen_fp16.md): 6.3 survivors per (cloud, channel) on the
+// bench's cubes against 4.1 and the launch 3.35 -> 2.86 ms; posed mesh surface clouds, whose coplanar points are near-ties in
+// many channels, go 9.0 -> 29.6 survivors and 4.0 -> 5.6 ms: the wider band costs there more than the MFMAs it saves.
 //
 // Work-group: 8 waves own one cloud; wave w owns channels [64 w, 64 w + 64) in layer 3 and lane l of it keeps the running
-// (vmax, imax) of channel 64 w + l.  LDS: fp32 H tile 66.5 KB (H1, then H2) + bf16 hi / lo planes of H2 67.6 KB + survivor
-// list 4 KB + 4 KB = 142.5 KB: one work-group per CU, two waves per SIMD.
+// (vmax, imax) of channel 64 w + l.  LDS: fp32 H tile 66.5 KB (H1, then H2) + fp16 plane of H2 33.8 KB + survivor
+// list 8 KB + 4 KB = 112.6 KB: one work-group per CU, two waves per SIMD.
 #pragma once
 
-typedef __bf16 ps_bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 ps_f16x8 __attribute__((ext_vector_type(8)));
 
 #define PS_LDP (PN_C2 + 8)               // halfwords per plane row (528 B: 16 rows hit 16 distinct 16-B slots, as in pointnet_enc_bf3.hip)
-#define PS_CAP 128                       // survivors per wave and tile before the dense fallback (~100 cycles each against 32768 dense)
+#define PS_CAP 256                       // survivors per wave and tile before the dense fallback (~100 cycles each against 32768 dense;
+                                         // the first tile of a random cloud has 85 - 115 per wave on average, C = 6 ... 3: no running
+                                         // maximum prunes it yet)
 #define PS_NW 8
-#define PS_P3 (16 * 16 * 64 * 8)         // halfwords of one W3 plane: [nb 16][step 16][lane 64][8]
-// packed buffer (bytes): W3 hi plane | W3 lo plane | 8 KB pad (the operand stream reads one step past the end) | W3 row-major fp32 | eps[512]
-#define PS_OFF_P3H 0
-#define PS_OFF_P3L (2 * PS_P3)
-#define PS_OFF_W3 (4 * PS_P3 + 8192)
+#define PS_P3 (16 * 16 * 64 * 8)         // halfwords of the W3 plane: [nb 16][step 16][lane 64][8]
+// packed buffer (bytes): W3 fp16 plane (rows scaled by 2^s_c) | W3 row-major fp32 | eps[512] | 2^-s_c [512]
+#define PS_OFF_P3 0
+#define PS_OFF_W3 (2 * PS_P3)
 #define PS_OFF_EPS (PS_OFF_W3 + PN_C3 * PN_C2 * 4)
-#define PS_PACKED_BYTES (PS_OFF_EPS + PN_C3 * 4)
+#define PS_OFF_INV (PS_OFF_EPS + PN_C3 * 4)
+#define PS_PACKED_BYTES (PS_OFF_INV + PN_C3 * 4)
 #ifndef PS_ABLATE
-#define PS_ABLATE 0          // profiling only (wrong results, same launch; tools/build_ab.py): 1 = no layer 1, 2 = no layer-2 MFMAs, 4 = no tanh / split
-                             // arithmetic in the layer-2 epilogue, 8 = no plane stores after tile 0, 16 = no screen MFMAs, 32 = no select / scan (and so
+#define PS_ABLATE 0          // profiling only (wrong results, same launch; tools/build_ab.py): 1 = no layer 1, 2 = no layer-2 MFMAs, 4 = no tanh
+                             // in the layer-2 epilogue, 8 = no plane stores after tile 0, 16 = no screen MFMAs, 32 = no select / scan (and so
                              // no finish), 64 = no survivor finish, 128 = no h2_save copy.  Every stand-in changes what the screen sees: read the
                              // survivor / fallback counters next to each timing.  Measured (profiles/round8_pointnet_screen_overlap.md): 2, 4, 32, 64
                              // and 128 keep the survivor count (3.8 - 4.1 per cloud and channel) and price their part; 1, 8 and 16 quadruple it and
@@ -61,88 +89,111 @@ typedef __bf16 ps_bf16x8 __attribute__((ext_vector_type(8)));
 
 extern "C" size_t pm_pointnet_packed_screen_bytes(void) { return PS_PACKED_BYTES; }
 
-__device__ __forceinline__ unsigned ps_cvt_pk(float a, float b) {          // {bf16(a) | bf16(b) << 16}, RNE
+__device__ __forceinline__ unsigned ps_cvt_pk(float a, float b) {          // {fp16(a) | fp16(b) << 16}, RNE under the default mode
     unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));       // pure: the compiler may schedule and combine it
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));        // pure: the compiler may schedule and combine it
     return r;
 }
-__device__ __forceinline__ void ps_split(float x, unsigned short& hi, unsigned short& lo) {
-    const unsigned h = ps_cvt_pk(x, 0.f) & 0xffffu;
-    const float xh = __uint_as_float(h << 16);
-    hi = (unsigned short)h;
-    lo = (unsigned short)(ps_cvt_pk(x - xh, 0.f) & 0xffffu);
-}
 
-__global__ __launch_bounds__(256) void ps_pack_kernel(const float* __restrict__ W3, const float* __restrict__ b3,
-                                                       unsigned char* __restrict__ packed) {
-    const int i = blockIdx.x * 256 + threadIdx.x;                          // one (nb, step, lane, e) plane slot = one W3 element
-    if (i >= PS_P3) return;
-    unsigned short* Ph = (unsigned short*)(packed + PS_OFF_P3H);
-    unsigned short* Pl = (unsigned short*)(packed + PS_OFF_P3L);
-    float* Wr = (float*)(packed + PS_OFF_W3);
-    const int e = i & 7, lane = (i >> 3) & 63, li = lane & 31, lq = lane >> 5, step = (i >> 9) & 15, nb = i >> 13;
-    unsigned short h, l;
-    ps_split(W3[(nb * 32 + li) * PN_C2 + step * 16 + lq * 8 + e], h, l);
-    Ph[i] = h;
-    Pl[i] = l;
-    Wr[i] = W3[i];
-    if (i < 4096) ((unsigned short*)(packed + 4 * PS_P3))[i] = 0;
-    if (i < PN_C3) {
-        double L = 0.0;
-        for (int k = 0; k < PN_C2; ++k) L += fabs((double)W3[i * PN_C2 + k]);
-        const double ed = (0x1p-16 + 2048.0 * 0x1p-24) * (L + fabs((double)b3[i])) * (1.0 + 0x1p-10);
+// One block per W3 row c, one thread per element k: the row's largest finite magnitude and its L1 norm (double, a fixed tree)
+// give s_c and eps_c; the element goes to its slot of the fp16 plane, scaled, and to the row-major fp32 copy as it is.
+__global__ __launch_bounds__(PN_C2) void ps_pack_kernel(const float* __restrict__ W3, const float* __restrict__ b3,
+                                                         unsigned char* __restrict__ packed) {
+    __shared__ double Ls[PN_C2], Rs[PN_C2], Ss[PN_C2];
+    __shared__ float Ms[PN_C2];
+    const int c = blockIdx.x, k = threadIdx.x;
+    const float w = W3[c * PN_C2 + k];
+    const float aw = fabsf(w);
+    Ls[k] = (double)aw;
+    Ms[k] = aw < INFINITY ? aw : 0.f;                                      // inf and NaN do not take part in the scale
+    __syncthreads();
+    for (int o = PN_C2 / 2; o > 0; o >>= 1) {
+        if (k < o) {
+            Ls[k] += Ls[k + o];
+            Ms[k] = fmaxf(Ms[k], Ms[k + o]);
+        }
+        __syncthreads();
+    }
+    int ex = -200;                                                         // no finite non-zero weight: the clamp below decides
+    if (Ms[0] > 0.f) frexpf(Ms[0], &ex);                                   // max = m 2^ex, m in [0.5, 1)
+    const int s = min(15 - ex, 126);                                       // 2^s max in [2^14, 2^15); 2^s and 2^-s are normal floats (ex <= 128)
+    const float ws = ldexpf(w, s);
+    const _Float16 w16 = (_Float16)ws;
+    const float wf = (float)w16, d = fabsf(ws - wf);                       // the difference is exact in fp32
+    Rs[k] = (double)(fabsf(wf) < 0x1p-14f ? fmaxf(fabsf(ws), d) : d);      // a subnormal operand may be kept (d) or flushed (|w'|)
+    Ss[k] = (double)fabsf(wf);
+    __syncthreads();
+    for (int o = PN_C2 / 2; o > 0; o >>= 1) {
+        if (k < o) {
+            Rs[k] += Rs[k + o];
+            Ss[k] += Ss[k + o];
+        }
+        __syncthreads();
+    }
+    const int nb = c >> 5, li = c & 31, step = k >> 4, lq = (k >> 3) & 1, e = k & 7;
+    ((_Float16*)(packed + PS_OFF_P3))[(((nb * 16 + step) * 64) + lq * 32 + li) * 8 + e] = w16;
+    ((float*)(packed + PS_OFF_W3))[c * PN_C2 + k] = w;
+    if (k == 0) {
+        const double ed = ((Rs[0] + 0x1p-12 * Ss[0]) * ldexp(1.0, -s) + 1024.0 * 0x1p-24 * (Ls[0] + fabs((double)b3[c]))) * (1.0 + 0x1p-10) + 0x1p-116;
         float ef = (float)ed;
         if ((double)ef < ed) ef = __uint_as_float(__float_as_uint(ef) + 1);   // round up (a NaN or inf eps stays what it is: the test is false)
-        ((float*)(packed + PS_OFF_EPS))[i] = ef;
+        ((float*)(packed + PS_OFF_EPS))[c] = ef;
+        ((float*)(packed + PS_OFF_INV))[c] = ldexpf(1.f, -s);
     }
 }
 
 extern "C" int pm_pointnet_pack_weights_screen(const float* W3, const float* b3, void* packed, void* stream) {
     PM_REQUIRE(W3 && b3 && packed);
     if (((uintptr_t)packed & 15) != 0) return PM_EALIGN;
-    hipLaunchKernelGGL(ps_pack_kernel, dim3(PS_P3 / 256), dim3(256), 0, pm_stream(stream), W3, b3, (unsigned char*)packed);
+    hipLaunchKernelGGL(ps_pack_kernel, dim3(PN_C3), dim3(PN_C2), 0, pm_stream(stream), W3, b3, (unsigned char*)packed);
     PM_CHECK_LAUNCH();
     return PM_OK;
 }
 
-#define PS_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-__device__ __forceinline__ ps_bf16x8 ps_bf(const uint4& v) { return *(const ps_bf16x8*)&v; }
+#define PS_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
+__device__ __forceinline__ ps_f16x8 ps_h(const uint4& v) { return *(const ps_f16x8*)&v; }
 
-// acc[mb][nb] += A(64 rows, hi / lo planes in LDS) * B(packed hi / lo planes), K = 256 in 16 steps of 16: the operand
-// pipeline of pointnet_enc_bf3.hip (next step's B fetched before this step's MFMAs, pinned with sched_barrier).
-__device__ __forceinline__ void ps_stream(const unsigned short* __restrict__ Ah, const unsigned short* __restrict__ Al,
-                                          const uint4* __restrict__ Bh, const uint4* __restrict__ Bl, f32x16 (&acc)[2][2]) {
-    uint4 bh0[2], bl0[2], bh1[2], bl1[2];
+// acc[mb][nb] += A(64 rows, the fp16 plane in LDS) * B(the packed fp16 plane), K = 256 in 16 steps of 16, one MFMA per (mb, nb)
+// and step.  A step is 4 MFMAs (128 cycles a wave, 256 for the SIMD's two), far less than an L2 round trip, so B is fetched
+// THREE steps ahead (four register sets in a ring) and A one step ahead, pinned with sched_barrier as in pointnet_enc_bf3.hip;
+// the last three steps fetch nothing, so nothing is read past the plane.
+__device__ __forceinline__ void ps_stream(const unsigned short* __restrict__ A, const uint4* __restrict__ B, f32x16 (&acc)[2][2]) {
+    uint4 b0[2], b1[2], b2[2], b3[2], a0[2], a1[2];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
-        bh0[nb] = Bh[(size_t)(nb * 16) * 64];
-        bl0[nb] = Bl[(size_t)(nb * 16) * 64];
+        b0[nb] = B[(size_t)(nb * 16 + 0) * 64];
+        b1[nb] = B[(size_t)(nb * 16 + 1) * 64];
+        b2[nb] = B[(size_t)(nb * 16 + 2) * 64];
     }
-#define PS_STEP(S_, BHC, BLC, BHN, BLN)                                                        \
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) a0[mb] = *(const uint4*)(A + mb * 32 * PS_LDP);
+#define PS_STEP(S_, AC, AN, BC, BN, PFA, PFB)                                                  \
     {                                                                                          \
-        uint4 ah[2], al[2];                                                                    \
-        _Pragma("unroll") for (int mb = 0; mb < 2; ++mb) {                                     \
-            ah[mb] = *(const uint4*)(Ah + mb * 32 * PS_LDP + (S_) * 16);                       \
-            al[mb] = *(const uint4*)(Al + mb * 32 * PS_LDP + (S_) * 16);                       \
+        if (PFA) {                                                                             \
+            _Pragma("unroll") for (int mb = 0; mb < 2; ++mb)                                   \
+                AN[mb] = *(const uint4*)(A + mb * 32 * PS_LDP + ((S_) + 1) * 16);              \
         }                                                                                      \
-        _Pragma("unroll") for (int nb = 0; nb < 2; ++nb) {   /* next step (one step past the end on the last trip: padded) */ \
-            BHN[nb] = Bh[(size_t)(nb * 16 + (S_) + 1) * 64];                                   \
-            BLN[nb] = Bl[(size_t)(nb * 16 + (S_) + 1) * 64];                                   \
+        if (PFB) {                                                                             \
+            _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                                   \
+                BN[nb] = B[(size_t)(nb * 16 + (S_) + 3) * 64];                                 \
         }                                                                                      \
         __builtin_amdgcn_sched_barrier(0);                                                     \
         _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                                       \
-            _Pragma("unroll") for (int mb = 0; mb < 2; ++mb) {                                 \
-                acc[mb][nb] = PS_MFMA(ps_bf(ah[mb]), ps_bf(BHC[nb]), acc[mb][nb]);             \
-                acc[mb][nb] = PS_MFMA(ps_bf(ah[mb]), ps_bf(BLC[nb]), acc[mb][nb]);             \
-                acc[mb][nb] = PS_MFMA(ps_bf(al[mb]), ps_bf(BHC[nb]), acc[mb][nb]);             \
-            }                                                                                  \
+            _Pragma("unroll") for (int mb = 0; mb < 2; ++mb)                                   \
+                acc[mb][nb] = PS_MFMA(ps_h(AC[mb]), ps_h(BC[nb]), acc[mb][nb]);                \
         __builtin_amdgcn_sched_barrier(0);                                                     \
     }
 #pragma unroll 1
-    for (int s = 0; s < 16; s += 2) {
-        PS_STEP(s, bh0, bl0, bh1, bl1)
-        PS_STEP(s + 1, bh1, bl1, bh0, bl0)
+    for (int s = 0; s < 12; s += 4) {
+        PS_STEP(s, a0, a1, b0, b3, 1, 1)
+        PS_STEP(s + 1, a1, a0, b1, b0, 1, 1)
+        PS_STEP(s + 2, a0, a1, b2, b1, 1, 1)
+        PS_STEP(s + 3, a1, a0, b3, b2, 1, 1)
     }
+    PS_STEP(12, a0, a1, b0, b3, 1, 1)
+    PS_STEP(13, a1, a0, b1, b0, 1, 0)
+    PS_STEP(14, a0, a1, b2, b1, 1, 0)
+    PS_STEP(15, a1, a0, b3, b2, 0, 0)
 #undef PS_STEP
 }
 
@@ -208,22 +259,20 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
     long ldf, int32_t* __restrict__ argmax, float* __restrict__ h2_save, unsigned long long* __restrict__ counters) {
     constexpr int NT = PS_NW * 64;
     __shared__ __attribute__((aligned(16))) float H[PN_TM * PN_LD2];                  // H1 [64][132], then H2 [64][260]
-    __shared__ __attribute__((aligned(16))) unsigned short Hp[2 * PN_TM * PS_LDP];    // bf16 hi | lo planes of H2
+    __shared__ __attribute__((aligned(16))) unsigned short Hh[PN_TM * PS_LDP];        // fp16 plane of H2
     __shared__ __attribute__((aligned(16))) float Xs[PN_TM * PN_MAXC];
     __shared__ double red[16];
     __shared__ double cs[PN_C2];                                                      // column sums of h2 over the cloud
     __shared__ int skey[PS_NW][PS_CAP];                                               // survivors: (row << 6) | channel in wave
-    unsigned short* Hh = Hp;
-    unsigned short* Hl = Hp + PN_TM * PS_LDP;
 
     const int b = blockIdx.x, tid = threadIdx.x, lane0 = tid & 63, wave = tid >> 6;
     const float* xb = x + (long)b * ldx;
     const float4* P2v = (const float4*)(packed + PN_P2_OFF);
     const float4* P3v = (const float4*)(packed + PN_P3_OFF);
-    const uint4* S3h = (const uint4*)(packed_s + PS_OFF_P3H);
-    const uint4* S3l = (const uint4*)(packed_s + PS_OFF_P3L);
+    const uint4* S3 = (const uint4*)(packed_s + PS_OFF_P3);
     const float* W3r = (const float*)(packed_s + PS_OFF_W3);
     const float* epsg = (const float*)(packed_s + PS_OFF_EPS);
+    const float* invg = (const float*)(packed_s + PS_OFF_INV);
 
     float cen[3] = {0.f, 0.f, 0.f};
     if (sub_mean) cloud_centroid<NT>(xb, P, C, red, cen);
@@ -233,11 +282,12 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
     double csum = 0.0;                       // lanes < 32: column 32 wave + lane of h2
 
     // Per-lane constants of the tile loop, loaded once per cloud (they depend on the lane and the wave only; the addresses
-    // are those the loop used to recompute from the laundered lane id): 5 VGPRs, + 5 for the W1 row and b1 when C is 3 or 4.
+    // are those the loop used to recompute from the laundered lane id): 7 VGPRs, + 5 for the W1 row and b1 when C is 3 or 4.
     const int li0 = lane0 & 31;
     const float b2r = b2[wave * 32 + li0];
     const float b3r[2] = {b3[(wave * 2 + 0) * 32 + li0], b3[(wave * 2 + 1) * 32 + li0]};
     const float epsr[2] = {epsg[(wave * 2 + 0) * 32 + li0], epsg[(wave * 2 + 1) * 32 + li0]};
+    const float invr[2] = {invg[(wave * 2 + 0) * 32 + li0], invg[(wave * 2 + 1) * 32 + li0]};      // 2^-s_c
     float w1r[4] = {0.f, 0.f, 0.f, 0.f}, b1r = 0.f;
     if constexpr (CT == 3 || CT == 4) layer1_row<CT>(W1, b1, w1r, b1r);
 
@@ -272,17 +322,18 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
             PS_STAMP(2);
             __syncthreads();                 // every wave has finished reading H1 (and Xs)
             PS_STAMP(3);
-            // layer-2 epilogue: layer2_store's arithmetic, plus the bf16 planes and this tile's column sum
+            // layer-2 epilogue: layer2_store's arithmetic, plus the fp16 plane and this tile's column sum
             const int col = wave * 32 + li;
             const float b2c = b2r;
             float ts = 0.f;                  // fp32 within the tile, rows in increasing order
-            const bool planes = !(PS_ABLATE & 8) || tile == 0;      // ablated: the screen keeps reading tile 0's planes
+            const bool planes = !(PS_ABLATE & 8) || tile == 0;      // ablated: the screen keeps reading tile 0's plane
             // Lanes l and l ^ 1 hold columns col and col ^ 1 of the same rows: they swap one value of every row pair (r, r + 1), so
-            // the even lane holds both columns of row r and the odd lane both of row r + 1, and each stores its hi pair and its lo
-            // pair as one 32-bit word (v_cvt_pk_bf16_f32 rounds the two halves as it rounds one: the plane bytes are ps_split's).
+            // the even lane holds both columns of row r and the odd lane both of row r + 1, and each converts its pair with one
+            // v_cvt_pk_f16_f32 (which rounds the two halves as it rounds one) and stores it as one 32-bit word: with a single
+            // plane that is one conversion and one ds_write_b32 per lane and row pair, the fewest the accumulator layout allows
+            // (a lane holds ONE column; wider stores would need a four-lane exchange of three values for each one stored).
             const bool odd = (lane & 1) != 0;
             unsigned* Hh2 = (unsigned*)(Hh + (odd ? PS_LDP : 0) + (col & ~1));      // 4-byte aligned: PS_LDP and col & ~1 are even
-            unsigned* Hl2 = (unsigned*)(Hl + (odd ? PS_LDP : 0) + (col & ~1));
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -303,18 +354,7 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
                     const float own = odd ? v2.y : v2.x, send = odd ? v2.x : v2.y;
                     const float recv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(send), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]: lane ^ 1
                     const float a = odd ? recv : own, c = odd ? own : recv;         // columns col & ~1 and col | 1 of row0 + odd
-                    unsigned h2w, l2w;
-                    if (PS_ABLATE & 4) {
-                        h2w = (__float_as_uint(a) >> 16) | (__float_as_uint(c) & 0xffff0000u);
-                        l2w = 0;
-                    } else {
-                        h2w = ps_cvt_pk(a, c);
-                        l2w = ps_cvt_pk(a - __uint_as_float(h2w << 16), c - __uint_as_float(h2w & 0xffff0000u));
-                    }
-                    if (planes) {
-                        Hh2[row0 * (PS_LDP / 2)] = h2w;                             // word index of halfword row0 * PS_LDP
-                        Hl2[row0 * (PS_LDP / 2)] = l2w;
-                    }
+                    if (planes) Hh2[row0 * (PS_LDP / 2)] = ps_cvt_pk(a, c);         // word index of halfword row0 * PS_LDP
                 }
             ts += __shfl_xor(ts, 32, 64);    // the other 32 rows; both halves hold the same sum
             csum += (double)ts;              // fp64 across tiles
@@ -330,12 +370,6 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
 
         // ---- screen: z~ for 64 points x this wave's 64 channels ---------------------------------------------
         f32x16 acc[2][2];
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-            const float b3c = b3r[nb];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][nb][r] = acc[1][nb][r] = b3c;
-        }
         if (PS_ABLATE & 16) {                // stand-in that still differs from point to point: b3 + 64 words of H2
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
@@ -343,10 +377,10 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
                 for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        acc[mb][nb][r] += H[(mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * PN_LD2 + ((wave * 64 + nb * 32 + li) & 255)];
+                        acc[mb][nb][r] = b3r[nb] + H[(mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * PN_LD2 + ((wave * 64 + nb * 32 + li) & 255)];
         } else {
-            ps_stream(Hh + li * PS_LDP + lh * 8, Hl + li * PS_LDP + lh * 8, S3h + (size_t)(wave * 2 * 16) * 64 + lane,
-                      S3l + (size_t)(wave * 2 * 16) * 64 + lane, acc);
+            zero_acc<2, 2>(acc);
+            ps_stream(Hh + li * PS_LDP + lh * 8, S3 + (size_t)(wave * 2 * 16) * 64 + lane, acc);
         }
         PS_STAMP(6);
 
@@ -364,10 +398,14 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
             float m = -INFINITY;
+            const float iv = invr[nb], b3c = b3r[nb];
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) m = fmaxf(m, acc[mb][nb][r]);
+                for (int r = 0; r < 16; ++r) {
+                    if (!(PS_ABLATE & 16)) acc[mb][nb][r] = fmaf(acc[mb][nb][r], iv, b3c);      // z~: un-scaled, one rounding (in eps)
+                    m = fmaxf(m, acc[mb][nb][r]);
+                }
             m = fmaxf(m, __shfl_xor(m, 32, 64));
             const float e = epsr[nb];
             const float vm = __shfl(vmax, nb * 32 + li, 64);

@@ -1,7 +1,7 @@
 """In-kernel timeline of pn_fwd_screen_kernel (A/B build: python tools/build_ab.py psprof pointnet_enc.hip -DPS_PROFILE
 prints the library's path; PARTMANIP_HIP_LIB=<that path> python tools/ps_profile.py).  Ten cycle-counter stamps per wave and tile for work-groups
 0-3 (one cloud each, tiles 0-15): loop top | after layer 1 | after the layer-2 MFMA loop | after barrier 3 | after the layer-2
-epilogue (tanh, planes, next tile's points) | after barrier 4 | after the screen MFMA loop | after select / scan | after the
+epilogue (tanh, fp16 plane, next tile's points) | after barrier 4 | after the screen MFMA loop | after select / scan | after the
 survivor finish | after the h2_save copy.  A segment that ends behind a barrier holds the wait for the slowest wave; the MFMA
 segments end when the last MFMA is ISSUED, so their tail lands in the next segment.  The stamps themselves cost a few cycles
 each: read the shares.  PN_SAVE_H2=0 profiles the inference forward (no copy)."""
