@@ -1259,7 +1259,15 @@ int pm_exclusive_scan_i32(const int32_t* counts, int n, int32_t* base, int32_t* 
  *     (the head's [features | proprio] rows); backward dx[b*HW + r] = dy[b] / HW.
  *   pm_im2col2d_c1_f32: patch matrix of a single-channel image, x (B rows of stride ldx, H*W pixels each) -> dst
  *     (B*Ho*Wo, ldd), dst[.][kh*k + kw] = the pixel under tap (kh, kw) or 0 in the padding, columns k*k .. ldd-1 zeros (the stem's
- *     K = 49 is no multiple of 4, so it cannot be a gathered operand; it runs on the Linear kernels over this matrix). */
+ *     K = 49 is no multiple of 4, so it cannot be a gathered operand; it runs on the Linear kernels over this matrix).
+ *   pm_im2col2d_f32: the same for a planar C-channel image (`network.name: ResNet`, the RGB stem), x (B rows of stride ldx, C planes
+ *     of H*W each) -> dst[.][c*k*k + kh*k + kw], zero in the padding and in the columns C*k*k .. ldd-1.  The column order is that
+ *     of conv.weight viewed (Cout, C*k*k).  C = 1 gives pm_im2col2d_c1_f32's bits.  ldd: the Linear kernels' K-step is 32, so the
+ *     RGB stem rounds 147 up to 160.
+ *   pm_rgb_planes_f32: view v of a colour frame, rgb uint8 (B, V, h, w, 3), into the head of B float rows of stride ldo:
+ *     out[b*ldo + c*h*w + y*w + x] = (float) rgb[b][v][y][x][c] (raw 0..255, the reference's `rgb_img` row); columns >= 3*h*w are
+ *     not touched.  v outside [0, V), a non-positive size or ldo < 3*h*w -> PM_EINVAL.  Four pixels per thread (three dwords in,
+ *     three 16-byte stores) when h*w % 4 == 0, ldo % 4 == 0 and both pointers are 16-byte aligned, one pixel per thread otherwise. */
 size_t pm_bn2d_workspace_bytes(long rows, int C);
 int pm_bn2d_stats_f32(const float* x, long ldx, long rows, int C, float eps, float* mean, float* var, float* invstd,
                       float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, void* workspace,
@@ -1278,6 +1286,9 @@ int pm_pool2d_max3s2_bwd_f32(const float* dy, long lddy, const float* dy2, long 
 int pm_pool2d_avg_fwd_f32(const float* x, long ldx, int B, int HW, int C, float* y, long ldy, void* stream);
 int pm_pool2d_avg_bwd_f32(const float* dy, long lddy, int B, int HW, int C, float* dx, long lddx, void* stream);
 int pm_im2col2d_c1_f32(const float* x, long ldx, int B, int H, int W, int k, int stride, int pad, float* dst, int ldd, void* stream);
+int pm_im2col2d_f32(const float* x, long ldx, int B, int C, int H, int W, int k, int stride, int pad, float* dst, int ldd,
+                    void* stream);
+int pm_rgb_planes_f32(const uint8_t* rgb, int B, int V, int h, int w, int v, float* out, long ldo, void* stream);
 
 #ifdef __cplusplus
 }

@@ -169,6 +169,8 @@ SIGNATURES = {
     "pm_pool2d_avg_fwd_f32": (I, [P, L, I, I, I, P, L, P]),
     "pm_pool2d_avg_bwd_f32": (I, [P, L, I, I, I, P, L, P]),
     "pm_im2col2d_c1_f32": (I, [P, L, I, I, I, I, I, I, P, I, P]),
+    "pm_im2col2d_f32": (I, [P, L, I, I, I, I, I, I, I, P, I, P]),
+    "pm_rgb_planes_f32": (I, [P, I, I, I, I, I, P, L, P]),
     "pm_sa_supported": (I, [I, I, I, I]),
     "pm_sa_packed_elems": (Z, [I, I, I]),
     "pm_sa_pack_weights_f32": (I, [P, P, I, I, I, P, P]),

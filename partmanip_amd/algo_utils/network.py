@@ -1540,14 +1540,14 @@ class _BasicBlock(nn.Module):
 
 class _ResNet34(nn.Module):
     """Parameter container of the published ResNet-34 (He et al. 2016, table 1) without its classifier, under torchvision's names,
-    with a single-channel stem.  Initialisation as the reference gets it: Kaiming-normal (fan_out, ReLU) in every body convolution,
+    with an `in_ch`-channel stem (1: the depth image, 3: the colour image).  Initialisation as the reference gets it: Kaiming-normal (fan_out, ReLU) in every body convolution,
     nn.Conv2d's default in the replaced stem, batch-norm weight 1 and bias 0."""
 
     BLOCKS, WIDTHS = (3, 4, 6, 3), (64, 128, 256, 512)
 
-    def __init__(self):
+    def __init__(self, in_ch=1):
         super().__init__()
-        self.conv1 = nn.Conv2d(1, 64, 7, stride=2, padding=3, bias=False)
+        self.conv1 = nn.Conv2d(in_ch, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         cin = 64
         for l, (n, c) in enumerate(zip(self.BLOCKS, self.WIDTHS)):
@@ -1585,28 +1585,32 @@ class _BlockSaved(NamedTuple):            # what a BasicBlock keeps of a trainin
     wpd: Optional[torch.Tensor]
 
 
-class depthResNet(_HipNet):
-    """network.py:237-271: the depth-image student.  x[:, :72*128] is a (B, 1, 72, 128) depth image, the proprio tail is kept:
-    ResNet-34 (single-channel 7 x 7 / 2 stem - BN - ReLU - max pool 3 / 2 / 1 - BasicBlocks (3, 4, 6, 3) at (64, 128, 256, 512)
-    channels - global average pool) -> cat proprio -> Linear 128 - act - Linear 32 - act - Linear out.  `state_dict` keys are
-    torchvision's (`resnet34.*`, `final_mlp.{0,2,4}.*`), so a checkpoint of the reference loads.
+class _ImageResNet(_HipNet):
+    """What the two image students share (network.py:202-271): x[:, :IN_CH*72*128] is a (B, IN_CH, 72, 128) image, the proprio tail
+    is kept: ResNet-34 (IN_CH-channel 7 x 7 / 2 stem - BN - ReLU - max pool 3 / 2 / 1 - BasicBlocks (3, 4, 6, 3) at (64, 128, 256,
+    512) channels - global average pool) -> cat proprio -> Linear 128 - act - Linear 32 - act - Linear out.  `state_dict` keys are
+    torchvision's (`resnet34.*`, `final_mlp.{0,2,4}.*`), so a checkpoint of the reference loads.  IN_CH is the one difference
+    between the subclasses: everything after the stem's patch matrix is the same code.
 
     Activations are channels-last matrices (b*H*W rows, C).  The 3 x 3 and 1 x 1 convolutions are the gathered GEMMs of the sparse
     convolutions over cached 2-D patch tables (no patch matrix in HBM; the data gradient of a 3 x 3 layer gathers through the
-    transposed table, that of a 1 x 1 stride-2 shortcut scatters); the single-channel stem (K = 49) is a patch matrix
-    (pm_im2col2d_c1_f32) + the Linear kernels and needs no data gradient.  Batch norm, the pools: csrc/bn_pool2d.hip.
+    transposed table, that of a 1 x 1 stride-2 shortcut scatters); the stem (K = IN_CH * 49, no multiple of 4) is a patch matrix
+    + the Linear kernels and needs no data gradient: the image is data.  Batch norm, the pools: csrc/bn_pool2d.hip.
     Modes follow nn.Module.training as torch does: in training mode EVERY forward (the rollout's under no_grad too) normalises with
     batch statistics and updates the running statistics; in eval mode the forward reads the running statistics and writes nothing."""
 
     H, W = 288 // 4, 512 // 4
+    IN_CH = 1
 
     def __init__(self, input_dim, output_dim, net_cfg, proprio_shape):
         super().__init__()
-        if input_dim != self.H * self.W + proprio_shape:
-            raise ValueError(f"depthResNet: input_dim {input_dim} is not {self.H} * {self.W} + proprio {proprio_shape}")
+        name = type(self).__name__
+        if input_dim != self.IN_CH * self.H * self.W + proprio_shape:
+            raise ValueError(f"{name}: input_dim {input_dim} is not {'' if self.IN_CH == 1 else f'{self.IN_CH} * '}{self.H} * {self.W} "
+                             f"+ proprio {proprio_shape}")
         act = net_cfg['activation']
         code = _act_code(act, linear_only=True)
-        self.resnet34 = _ResNet34()
+        self.resnet34 = _ResNet34(self.IN_CH)
         self.proprio_shape = proprio_shape
         self.activation = get_activation(act)
         self.final_mlp = nn.Sequential(
@@ -1688,12 +1692,18 @@ class depthResNet(_HipNet):
     def hip_forward(self, x, out=None):
         B, dev = x.shape[0], x.device
         net = self.resnet34
-        HW = self.H * self.W
-        # stem: 7 x 7 / 2 on one channel = patch matrix (49 columns zero-padded to 64: whole K-steps) + Linear kernel
+        HW, K0 = self.H * self.W, self.IN_CH * 49
+        K0p = (K0 + 31) // 32 * 32
+        # stem: 7 x 7 / 2 = patch matrix (columns (c, kh, kw), conv1.weight's own order, zero-padded to whole K-steps of the Linear
+        # kernels, 32: 49 -> 64 on one channel, 147 -> 160 on three) + Linear kernel
         H1, W1 = (self.H + 6 - 7) // 2 + 1, (self.W + 6 - 7) // 2 + 1
-        cols = ops.im2col2d_c1(x[:, :HW], self.H, self.W, 7, 2, 3, torch.empty(B * H1 * W1, 64, device=dev))
-        w0 = torch.zeros(64, 64, device=dev)
-        w0[:, :49].copy_(net.conv1.weight.data.view(64, 49))
+        cols = torch.empty(B * H1 * W1, K0p, device=dev)
+        if self.IN_CH == 1:
+            ops.im2col2d_c1(x[:, :HW], self.H, self.W, 7, 2, 3, cols)
+        else:
+            ops.im2col2d(x[:, :self.IN_CH * HW], self.IN_CH, self.H, self.W, 7, 2, 3, cols)
+        w0 = torch.zeros(64, K0p, device=dev)
+        w0[:, :K0].copy_(net.conv1.weight.data.view(64, K0))
         z0 = torch.empty(B * H1 * W1, 64, device=dev)
         ops.linear_fwd(cols, w0, self._zero(dev), z0, ops.ACT_NONE)
         s0 = self._bn(net.bn1, z0, relu=True)
@@ -1732,7 +1742,7 @@ class depthResNet(_HipNet):
         mask, the max pool's winners as torch's `return_indices` gives them (int64), then the two ReLU masks of each block."""
         s = self._saved
         if s is None or not s["training"]:
-            raise RuntimeError("depthResNet.saved_signs: no training forward has run")
+            raise RuntimeError(f"{type(self).__name__}.saved_signs: no training forward has run")
         B = s["B"]
         H1, W1, H2, W2, pidx = s["pool"]
         nchw = lambda t, h, w: t.view(B, h, w, t.shape[1]).permute(0, 3, 1, 2)       # noqa: E731
@@ -1762,9 +1772,9 @@ class depthResNet(_HipNet):
     def hip_backward(self, dy):
         s = self._saved
         if s is None or not s["training"]:
-            raise RuntimeError("depthResNet.hip_backward: the last forward ran in eval mode (running statistics): call .train() first")
+            raise RuntimeError(f"{type(self).__name__}.hip_backward: the last forward ran in eval mode (running statistics): call .train() first")
         if self._views is None:
-            raise RuntimeError("depthResNet.hip_backward needs the owner's flat gradient views (ActorCritic.flat())")
+            raise RuntimeError(f"{type(self).__name__}.hip_backward needs the owner's flat gradient views (ActorCritic.flat())")
         B, dev = s["B"], dy.device
         ws = self._workspace(dev)
         zero = self._zero(dev)
@@ -1800,9 +1810,61 @@ class depthResNet(_HipNet):
         H1, W1, H2, W2, pidx = s["pool"]
         dy0 = ops.pool2d_max_bwd(d, pidx, B, H1, W1, torch.empty(B * H1 * W1, 64, device=dev), dy2=d2)
         dz0, _ = self._bn_bwd("resnet34.bn1", s["s0"], dy0, True, ws)
-        dw0 = torch.empty(64, 64, device=dev)
+        K0 = self.IN_CH * 49
+        dw0 = torch.empty(64, s["cols"].shape[1], device=dev)               # (64, K0 padded as the patch matrix is)
         ops.linear_bwd_weight(dz0, s["cols"], dw0, None, ws)                # the image is data: no gradient to it
-        self._views["resnet34.conv1.weight"].view(64, 49).copy_(dw0[:, :49])
+        self._views["resnet34.conv1.weight"].view(64, K0).copy_(dw0[:, :K0])   # columns (c, kh, kw): the weight's order, no permutation
+
+
+class depthResNet(_ImageResNet):
+    """network.py:237-271: the depth-image student (the `depth_img` mode): x[:, :72*128] is a (B, 1, 72, 128) depth image.  Its
+    single-channel stem (K = 49) is pm_im2col2d_c1_f32's patch matrix, zero-padded to 64 columns.  See _ImageResNet."""
+
+    IN_CH = 1
+
+
+_NO_IMAGENET = ("backbone 'ResNet' (reference network.py:202-234) starts from torchvision's pretrained ImageNet weights, which this "
+                "package neither ships nor fetches: set network.pretrained to the path of a local torchvision resnet34 state_dict "
+                "(torch.save(resnet34.state_dict(), path)), or to False for a random initialisation")
+
+
+class ResNet(_ImageResNet):
+    """network.py:202-234: the colour-image student (the `rgb_img` mode): x[:, :3*72*128] is a (B, 3, 72, 128) image in raw 0..255
+    values, as the reference feeds it.  Its stem (K = 147) is pm_im2col2d_f32's patch matrix, zero-padded to 160 columns, on the
+    Linear kernels; the rest is _ImageResNet.
+
+    net_cfg['pretrained'] must be given (the reference calls resnet34(pretrained=True), which downloads; nothing here does):
+      False  the depth student's initialisation (Kaiming fan-out in the body, nn.Conv2d's default in the stem);
+      PATH   a torchvision resnet34 state_dict under its bare keys (conv1.weight, bn1.*, layer1.0.conv1.weight, ...), loaded with
+             torch.load(PATH, map_location='cpu', weights_only=True) into `resnet34.*`; fc.weight / fc.bias are dropped, any other
+             missing or unexpected key or a shape mismatch is an error that names the keys."""
+
+    IN_CH = 3
+
+    def __init__(self, input_dim, output_dim, net_cfg, proprio_shape):
+        pre = net_cfg.get('pretrained', None)
+        if pre is None or pre is True:
+            raise NotImplementedError(_NO_IMAGENET)
+        super().__init__(input_dim, output_dim, net_cfg, proprio_shape)
+        if pre is not False:
+            self._load_pretrained(_os.fspath(pre))
+
+    def _load_pretrained(self, path):
+        if not _os.path.isfile(path):
+            raise FileNotFoundError(f"ResNet: network.pretrained names '{path}', which is not a file")
+        sd = torch.load(path, map_location='cpu', weights_only=True)
+        if not isinstance(sd, dict):
+            raise ValueError(f"ResNet: '{path}' holds a {type(sd).__name__}, not a state_dict")
+        sd = {k: v for k, v in sd.items() if k not in ("fc.weight", "fc.bias")}
+        own = self.resnet34.state_dict()
+        missing = [k for k in own if k not in sd]
+        unexpected = [k for k in sd if k not in own]
+        shapes = [f"{k}: {tuple(getattr(sd[k], 'shape', ()))} for {tuple(own[k].shape)}" for k in own
+                  if k in sd and (not torch.is_tensor(sd[k]) or tuple(sd[k].shape) != tuple(own[k].shape))]
+        if missing or unexpected or shapes:
+            raise ValueError(f"ResNet: '{path}' is not a torchvision resnet34 state_dict: missing keys {missing}, unexpected keys "
+                             f"{unexpected}, shape mismatches {shapes}")
+        self.resnet34.load_state_dict(sd, strict=True)
 
 
 def _out_of_scope(name, why):
@@ -1810,10 +1872,9 @@ def _out_of_scope(name, why):
         def __init__(self, *a, **k):
             raise NotImplementedError(
                 f"backbone '{name}' (reference network.py) is not implemented: {why}; MLP, PointNet, PointNet2, Conv3DNet, "
-                "SparseUNet and depthResNet are")
+                "SparseUNet, depthResNet and ResNet are")
     _Stub.__name__ = name
     return _Stub
 
 
 PoolConv3DNet = _out_of_scope("PoolConv3DNet", "the pooled-TSDF student is outside this build's hot-path scope (SURVEY.md §8f rank 4)")
-ResNet = _out_of_scope("ResNet", "the RGB student starts from pretrained ImageNet weights, which this package does not ship or fetch")

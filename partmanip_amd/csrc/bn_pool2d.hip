@@ -1,5 +1,6 @@
 // Batch normalisation, 3x3/2 max pool and global average pool over channels-last activations: what a 2-D residual network needs
-// beside its convolutions (`network.name: depthResNet`; the convolutions are the gathered GEMMs of gemm_f32.hip).
+// beside its convolutions (`network.name: depthResNet` and `ResNet`; the convolutions are the gathered GEMMs of gemm_f32.hip), the
+// stems' patch matrices, and the colour frame's way into an observation row.
 //
 // Every activation is a matrix (rows = b*H*W, C) with a row stride ld >= C, C % 4 == 0, 16-byte aligned: a lane owns FOUR
 // consecutive channels (one 16-byte access) and the lanes of a work-group that share a channel quad walk rows.  All kernels are
@@ -333,6 +334,74 @@ __global__ __launch_bounds__(BP_NT) void im2col2d_c1_kernel(const float* __restr
     }
 }
 
+// ---- patch matrix of a C-channel planar image (the RGB stem: K = 3*7*7 = 147) ------------------------------------------------------
+// dst[(b, oh, ow)][c*k*k + kh*k + kw] = x[b][c][oh*stride - pad + kh][ow*stride - pad + kw] (0 in the padding); columns C*k*k .. ldd-1
+// are zeros.  The column order (c, kh, kw) is that of conv.weight.view(Cout, C*k*k): the weight and its gradient are used as they lie.
+// One thread per (patch row, c, kh), as conv3d.hip's im2col3d_kernel: it decodes its indices once and copies the k taps along w
+// (contiguous in the image and in the patch row); one extra group per row zero-fills the pad columns.  ldd: the Linear kernels take
+// their fast path with whole K-steps of 32 (G2_TK, gemm2_f32.hip), so the caller rounds 147 up to 160 (the depth stem's 49 to 64).
+__global__ __launch_bounds__(BP_NT) void im2col2d_kernel(const float* __restrict__ x, long ldx, int C, int H, int W, int k, int stride,
+                                                          int pad, int Ho, int Wo, long total, float* __restrict__ dst, int ldd) {
+    const int kk = k * k, ncol = C * kk, gpr = C * k + 1;                                       // groups per row
+    for (long e = (long)blockIdx.x * BP_NT + threadIdx.x; e < total; e += (long)gridDim.x * BP_NT) {
+        const long row = e / gpr;
+        const int grp = (int)(e - row * gpr);
+        float* d = dst + row * ldd;
+        if (grp == C * k) {
+            for (int col = ncol; col < ldd; ++col) d[col] = 0.0f;
+            continue;
+        }
+        const int c = grp / k, kh = grp - c * k;
+        const int ow = (int)(row % Wo), oh = (int)((row / Wo) % Ho);
+        const long b = row / ((long)Wo * Ho);
+        const int ih = oh * stride - pad + kh, w0 = ow * stride - pad;
+        const bool ok = ih >= 0 && ih < H;
+        const float* src = x + b * ldx + ((long)c * H + (ok ? ih : 0)) * W;
+        d += c * kk + kh * k;
+        for (int kw = 0; kw < k; ++kw) {
+            const int iw = w0 + kw;
+            d[kw] = (ok && iw >= 0 && iw < W) ? src[iw] : 0.0f;
+        }
+    }
+}
+
+// ---- colour frame -> observation rows (the `rgb_img` mode: hand_base.py:344-353 puts camera v's image, permuted to (3, h, w), raw
+// 0..255, at the head of the row) -----------------------------------------------------------------------------------------------------
+// out[b*ldo + c*h*w + p] = (float) rgb[b][v][p][c], p = y*w + x; columns >= 3*h*w of a row are not touched.  Pure data movement.
+// Vector path: one thread converts four consecutive pixels -- three aligned dwords in (12 bytes = R0 G0 B0 R1 | G1 B1 R2 G2 |
+// B2 R3 G3 B3), one 16-byte store to each of the three planes.  It needs h*w % 4 == 0 (then every image starts on a dword and every
+// plane on 16 bytes), ldo % 4 == 0 and 16-byte aligned bases; the host picks the scalar kernel otherwise.
+__global__ __launch_bounds__(BP_NT) void rgb_planes_vec4_kernel(const uint8_t* __restrict__ rgb, int B, int V, int hw, int v,
+                                                                 float* __restrict__ out, long ldo) {
+    const int q4 = hw >> 2;
+    const long total = (long)B * q4;
+    for (long e = (long)blockIdx.x * BP_NT + threadIdx.x; e < total; e += (long)gridDim.x * BP_NT) {
+        const long b = e / q4;
+        const int p = (int)(e - b * q4) * 4;
+        const uint32_t* s = reinterpret_cast<const uint32_t*>(rgb + ((b * V + v) * hw + p) * 3);
+        const uint32_t d0 = s[0], d1 = s[1], d2 = s[2];
+        float* o = out + b * ldo + p;
+        bp_st4(o, make_float4((float)(d0 & 255u), (float)(d0 >> 24), (float)((d1 >> 16) & 255u), (float)((d2 >> 8) & 255u)));
+        bp_st4(o + hw, make_float4((float)((d0 >> 8) & 255u), (float)(d1 & 255u), (float)(d1 >> 24), (float)((d2 >> 16) & 255u)));
+        bp_st4(o + 2 * (long)hw, make_float4((float)((d0 >> 16) & 255u), (float)((d1 >> 8) & 255u), (float)(d2 & 255u), (float)(d2 >> 24)));
+    }
+}
+
+// the same definition, one thread per pixel: any h*w, any row stride, any alignment
+__global__ __launch_bounds__(BP_NT) void rgb_planes_scalar_kernel(const uint8_t* __restrict__ rgb, int B, int V, int hw, int v,
+                                                                   float* __restrict__ out, long ldo) {
+    const long total = (long)B * hw;
+    for (long e = (long)blockIdx.x * BP_NT + threadIdx.x; e < total; e += (long)gridDim.x * BP_NT) {
+        const long b = e / hw;
+        const int p = (int)(e - b * hw);
+        const uint8_t* s = rgb + ((b * V + v) * hw + p) * 3;
+        float* o = out + b * ldo + p;
+        o[0] = (float)s[0];
+        o[hw] = (float)s[1];
+        o[2 * (long)hw] = (float)s[2];
+    }
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 static inline unsigned bp_grid(long total) {
     const long g = (total + BP_NT - 1) / BP_NT;
@@ -464,6 +533,32 @@ extern "C" int pm_im2col2d_c1_f32(const float* x, long ldx, int B, int H, int W,
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     hipLaunchKernelGGL(im2col2d_c1_kernel, dim3(bp_grid((long)B * Ho * Wo * ldd)), dim3(BP_NT), 0, pm_stream(stream), x, ldx, B, H, W, k,
                        stride, pad, Ho, Wo, dst, ldd);
+    PM_CHECK_LAUNCH();
+    return PM_OK;
+}
+
+extern "C" int pm_im2col2d_f32(const float* x, long ldx, int B, int C, int H, int W, int k, int stride, int pad, float* dst, int ldd,
+                               void* stream) {
+    PM_REQUIRE(x && dst && B > 0 && C > 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0 && H + 2 * pad >= k && W + 2 * pad >= k);
+    PM_REQUIRE((long)C * k * k < 0x7fffffffL && ldd >= C * k * k && (long)C * H * W < 0x7fffffffL && ldx >= (long)C * H * W);
+    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+    const long total = (long)B * Ho * Wo * (C * k + 1);
+    hipLaunchKernelGGL(im2col2d_kernel, dim3(bp_grid(total)), dim3(BP_NT), 0, pm_stream(stream), x, ldx, C, H, W, k, stride, pad, Ho, Wo,
+                       total, dst, ldd);
+    PM_CHECK_LAUNCH();
+    return PM_OK;
+}
+
+extern "C" int pm_rgb_planes_f32(const uint8_t* rgb, int B, int V, int h, int w, int v, float* out, long ldo, void* stream) {
+    PM_REQUIRE(rgb && out && B > 0 && V > 0 && h > 0 && w > 0 && v >= 0 && v < V && (long)h * w < 0x7fffffffL / 3 && ldo >= 3L * h * w);
+    const int hw = h * w;
+    const bool vec = hw % 4 == 0 && ldo % 4 == 0 && bp_aligned16(rgb) && bp_aligned16(out);
+    if (vec)
+        hipLaunchKernelGGL(rgb_planes_vec4_kernel, dim3(bp_grid((long)B * (hw / 4))), dim3(BP_NT), 0, pm_stream(stream), rgb, B, V, hw, v,
+                           out, ldo);
+    else
+        hipLaunchKernelGGL(rgb_planes_scalar_kernel, dim3(bp_grid((long)B * hw)), dim3(BP_NT), 0, pm_stream(stream), rgb, B, V, hw, v, out,
+                           ldo);
     PM_CHECK_LAUNCH();
     return PM_OK;
 }

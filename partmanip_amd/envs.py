@@ -78,6 +78,19 @@ def depth_img_observer(cam):
     return _Observer(cam.num_view * cam.im_h * cam.im_w, lambda R, T, out: cam.render(R, T, out=out))
 
 
+def rgb_img_observer(cam, view=0):
+    """mesh2depth.DepthFromMesh -> 3 * im_h * im_w columns: the colour image of camera `view` as three float planes (3, im_h, im_w),
+    raw 0..255 (the `rgb_img` mode of hand_base.py:344-353, which takes camera 0 and permutes it so): one render_frame (rgb only)
+    and one ops.rgb_planes launch straight into the row.  The colours are this package's palette and headlight shading."""
+    view = int(view)
+    if not 0 <= view < cam.num_view:
+        raise ValueError(f"rgb_img_observer: view {view} outside [0, {cam.num_view})")
+
+    def write(R, T, out):
+        ops.rgb_planes(cam.render_frame(R, T, depth=False, seg=False, rgb=True).rgb, view, out)
+    return _Observer(3 * cam.im_h * cam.im_w, write)
+
+
 def depth_tsdf_observer(cam, volume):
     """mesh2depth.DepthFromMesh and a depth2tsdf.TSDFVolume with the same cameras registered -> resolution^3 columns: the rendered
     depth images integrated into the volume (the `depth_tsdf` mode of hand_base.py:325-327; integrate returns its own tensor, so
@@ -116,8 +129,8 @@ def frame_recorder(cam, env=0, view=0):
 
 class KinematicEnv:
     """task: GraspCubeTensors over sim = KinematicSim(free_body=True), or OpenDrawerTensors over KinematicSim(objects=...).
-    observers: {mode: pc_observer(...) / tsdf_observer(...) / depth_pc_observer(...) / depth_img_observer(...) / depth_tsdf_observer(...) /
-    depth_sparse_observer(...)}; with add_proprio_obs the proprio row is the
+    observers: {mode: pc_observer(...) / tsdf_observer(...) / depth_pc_observer(...) / depth_img_observer(...) / rgb_img_observer(...) /
+    depth_tsdf_observer(...) / depth_sparse_observer(...)}; with add_proprio_obs the proprio row is the
     tail of every such mode's row (for grasp_cube the first mode's tail is written by end_step(obs_out=) itself: no cat).
     num_obs reports the widths returned.  grasp_width: the grasp predicate's (grasp_cube); hold=False switches the rule off (the
     cube, or the drawer, then never moves), hold='always' sets the flag in every environment whatever the predicate says (the

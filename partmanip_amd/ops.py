@@ -1342,6 +1342,34 @@ def im2col2d_c1(x, H, W, k, stride, pad, dst):
     return dst
 
 
+def im2col2d(x, C, H, W, k, stride, pad, dst):
+    """Patch matrix of planar C-channel images: x (B, >= C*H*W) rows (the leading C*H*W columns are the C planes) -> dst (B*Ho*Wo,
+    ldd >= C*k*k) with columns (c, kh, kw) -- conv.weight.view(Cout, C*k*k)'s order -- zero in the padding and in the columns past
+    C*k*k."""
+    _one_device("im2col2d", x, dst)
+    ldx = _rows(x, "x")
+    _f32c(dst, "dst")
+    B = x.shape[0]
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if C < 1 or x.shape[1] < C * H * W or dst.dim() != 2 or dst.shape[0] != B * Ho * Wo or dst.shape[1] < C * k * k:
+        raise ValueError(f"im2col2d: x ({B}, >= {C * H * W}) and dst ({B * Ho * Wo}, >= {C * k * k}) expected, got {tuple(x.shape)}, "
+                         f"{tuple(dst.shape)}")
+    check(lib.pm_im2col2d_f32(_ptr(x), ldx, B, C, H, W, k, stride, pad, _ptr(dst), dst.shape[1], _stream()), "pm_im2col2d_f32")
+    return dst
+
+
+def rgb_planes(rgb, view, out):
+    """View `view` of a colour frame, rgb uint8 (B, V, h, w, 3) contiguous, as float planes at the head of the rows of out (B, >= 3*h*w):
+    out[b, c*h*w + y*w + x] = float(rgb[b, view, y, x, c]), raw 0..255; the columns past 3*h*w are not touched (pm_rgb_planes_f32)."""
+    _one_device("rgb_planes", rgb, out)
+    if rgb.dim() != 5 or rgb.shape[4] != 3 or rgb.dtype != torch.uint8 or not rgb.is_contiguous():
+        raise ValueError(f"rgb_planes: rgb: expected a contiguous uint8 (B, V, h, w, 3), got {rgb.dtype} {tuple(rgb.shape)}")
+    B, V, h, w = rgb.shape[:4]
+    out, ldo = _out_rows(out, B, 3 * h * w, rgb.device)
+    check(lib.pm_rgb_planes_f32(_ptr(rgb), B, V, h, w, int(view), _ptr(out), ldo, _stream()), "pm_rgb_planes_f32")
+    return out
+
+
 # `accumulate` of rows_gather_bwd (pm_rows_gather_bwd_f32): what dsrc holds when the call starts
 ACC_OVERWRITE = 0         # nothing: dsrc is overwritten
 ACC_ADD = 1               # a finished gradient: the (already multiplied) result is added to it
