@@ -14,7 +14,9 @@
 // has z^_p <= z~_p + eps < m~ - eps <= z^_q for the tile's q = argmax z~ (or z^_p <= vmax): it can neither beat nor tie.
 // Every survivor (p, c) is then evaluated exactly: eight lanes, lane j takes k = 4 j + 32 i + e (i = 0..7, e = 0..3) as
 // one fmaf chain in that order, the eight partial sums are combined by the xor-4, -2, -1 butterfly, and b3_c is added
-// last -- one fixed order, whatever the other survivors are.  The running maximum takes v when
+// last -- one fixed order, whatever the other survivors are.  A sum that is zero returns b3_c ITSELF, sign included: that
+// is the IEEE sum in every case but (+0) + (-0), which would be +0, so a zero row gives its bias back bit for bit (the
+// values stay numerically equal to what the plain add returns).  The running maximum takes v when
 // v > vmax || (v == vmax && p < imax), so survivor order cannot change the result and ties go to the lowest point.
 // A wave whose tile has more than PS_CAP survivors (degenerate clouds: all points equal, zero padding) runs the dense
 // fp32 layer 3 of pn_fwd_kernel for that tile instead: such a tile costs the dense layer 3 PLUS the screen it already ran,
@@ -55,10 +57,14 @@
 // one exact finish above.  Measured (profiles/round10_pointnet_screen_fp16.md): 6.3 survivors per (cloud, channel) on the
 // bench's cubes against 4.1 and the launch 3.35 -> 2.86 ms; posed mesh surface clouds, whose coplanar points are near-ties in
 // many channels, go 9.0 -> 29.6 survivors and 4.0 -> 5.6 ms: the wider band costs there more than the MFMAs it saves.
+// Since then the finish sums its lanes on DPP moves and hands each value over with one ds_max_u64 (ps_sum8, ps_best_pack
+// below; profiles/round11_pointnet_screen_finish.md): a pass of eight survivors 2 k -> 0.9 k cycles, the launch 2.89 ->
+// 2.53 ms, the mesh clouds 5.6 -> 3.8 ms, every output (as a number) and counter unchanged.
 //
-// Work-group: 8 waves own one cloud; wave w owns channels [64 w, 64 w + 64) in layer 3 and lane l of it keeps the running
-// (vmax, imax) of channel 64 w + l.  LDS: fp32 H tile 66.5 KB (H1, then H2) + fp16 plane of H2 33.8 KB + survivor
-// list 8 KB + 4 KB = 112.6 KB: one work-group per CU, two waves per SIMD.
+// Work-group: 8 waves own one cloud; wave w owns channels [64 w, 64 w + 64) in layer 3 and keeps their running (vmax, imax)
+// in LDS, one packed 64-bit word per channel (ps_best_pack) that the finish raises with ds_max_u64 and the select pass reads
+// back; lane l of it keeps pois of channel 64 w + l.  LDS: fp32 H tile 66.5 KB (H1, then H2) + fp16 plane of H2 33.8 KB +
+// survivor list 8 KB + running maxima 4 KB + 4 KB = 116 864 B: one work-group per CU, two waves per SIMD.
 #pragma once
 
 typedef _Float16 ps_f16x8 __attribute__((ext_vector_type(8)));
@@ -240,6 +246,61 @@ __device__ __forceinline__ void ps_point_store(float v, int sub_mean, const floa
     Xs[tid] = v;
 }
 
+// Lane-crossing moves of the select pass and the finish, on the VALU's DPP controls: no LDS round trip (a __shfl is a
+// ds_bpermute_b32 and a full wait for it).  Every lane of the wave is active where these are called.
+#define PS_DPP(old, src, ctrl, rows, banks) __builtin_amdgcn_update_dpp((old), (src), (ctrl), (rows), (banks), false)
+
+// u = s + s[lane ^ 4];  t = u + u[lane ^ 2];  t + t[lane ^ 1]: the finish's addition tree over a group of eight lanes.
+__device__ __forceinline__ float ps_sum8(float s) {
+    const int si = __float_as_int(s);
+    int t = PS_DPP(si, si, 0x114, 0xf, 0xa);             // row_shr:4 into banks 1 and 3: lanes 4-7 and 12-15 of a row take lane - 4
+    t = PS_DPP(t, si, 0x104, 0xf, 0x5);                  // row_shl:4 into banks 0 and 2: lanes 0-3 and 8-11 take lane + 4
+    s += __int_as_float(t);
+    s += __int_as_float(PS_DPP(0, __float_as_int(s), 0x4e, 0xf, 0xf));       // quad_perm [2,3,0,1]: lane ^ 2
+    s += __int_as_float(PS_DPP(0, __float_as_int(s), 0xb1, 0xf, 0xf));       // quad_perm [1,0,3,2]: lane ^ 1
+    return s;
+}
+
+// Inclusive prefix sum over the wave's 64 lanes: row_shr 1 / 2 / 4 / 8 inside each row of 16 (a lane without a source in its
+// row keeps the 0), then the row totals: row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3.
+__device__ __forceinline__ int ps_prefix64(int v) {
+    v += PS_DPP(0, v, 0x111, 0xf, 0xf);
+    v += PS_DPP(0, v, 0x112, 0xf, 0xf);
+    v += PS_DPP(0, v, 0x114, 0xf, 0xf);
+    v += PS_DPP(0, v, 0x118, 0xf, 0xf);
+    v += PS_DPP(0, v, 0x142, 0xa, 0xf);
+    v += PS_DPP(0, v, 0x143, 0xc, 0xf);
+    return v;
+}
+
+// The running maximum of a channel and its point, as ONE 64-bit integer that max() orders like the rule
+// v > vmax || (v == vmax && p < imax).  High word: the order-preserving image of the fp32 value (all bits flipped if the sign
+// is set, the sign bit flipped otherwise).  Low word: ((2^31 - 1 - p) << 1) | 1, so the lower point wins among equal values.
+// Signed zero: the rule takes +0 and -0 as equal and keeps the lower point WITH ITS SIGN, while the image puts -0 below +0,
+// and the finish can return either: its value is b3 itself where the eight-lane sum is zero (a zero row; or products that
+// all underflow) and sum + b3 otherwise, so it is -0 exactly where b3 is -0 and the sum is zero, and +0 where b3 is +0 and the
+// sum is zero or where a non-zero sum cancels b3: points of one channel with zeros of both signs need different b3 and so
+// cannot meet, but the fallback's values of the same channel (an MFMA chain from b3) can carry the other sign.  So
+// zero gets its own handling: -0 takes the image of +0 and clears bit 0 of the low word, which cannot change the order (equal
+// p is the same point, the same value) and gives the sign back on decoding.  NaN is never offered (the rule never takes it).
+// The dense fallback's values (an MFMA chain that starts from b3) go through the same slot, signed zeros included.
+#define PS_BEST_INIT 0x007fffffffffffffull                                   // (-inf, point 0): what vmax = -inf, imax = 0 was
+__device__ __forceinline__ unsigned long long ps_best_pack(float v, int p) {
+    const unsigned u = __float_as_uint(v);
+    const bool nz = u == 0x80000000u;
+    const unsigned hi = nz ? 0x80000000u : u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
+    const unsigned lo = ((0x7fffffffu - (unsigned)p) << 1) | (nz ? 0u : 1u);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ float ps_best_value(unsigned hi, unsigned lo) {   // lo = 1: a zero comes back as +0 (the select pass)
+    const unsigned u = (hi & 0x80000000u) ? hi ^ 0x80000000u : ~hi;
+    return __uint_as_float((lo & 1u) ? u : 0x80000000u);
+}
+__device__ __forceinline__ int ps_best_point(unsigned lo) { return (int)(0x7fffffffu - (lo >> 1)); }
+__device__ __forceinline__ void ps_best_max(unsigned long long* slot, float v, int p) {      // ds_max_u64, no return value
+    __hip_atomic_fetch_max(slot, ps_best_pack(v, p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 #ifdef PS_PROFILE   // A/B builds only (tools/ps_profile.py): cycle-counter stamps of work-groups 0-3 (one cloud each), tiles 0-15, every wave
 __device__ unsigned long long ps_prof[4 * 16 * PS_NW * 16];
 extern "C" int pm_debug_ps_prof_read(void* dst) {
@@ -264,6 +325,7 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
     __shared__ double red[16];
     __shared__ double cs[PN_C2];                                                      // column sums of h2 over the cloud
     __shared__ int skey[PS_NW][PS_CAP];                                               // survivors: (row << 6) | channel in wave
+    __shared__ unsigned long long best[PS_NW][64];                                    // running (maximum, point) of channel 64 wave + l: ps_best_pack
 
     const int b = blockIdx.x, tid = threadIdx.x, lane0 = tid & 63, wave = tid >> 6;
     const float* xb = x + (long)b * ldx;
@@ -277,8 +339,8 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
     float cen[3] = {0.f, 0.f, 0.f};
     if (sub_mean) cloud_centroid<NT>(xb, P, C, red, cen);
 
-    float vmax = -INFINITY, pois = 0.f;      // lane l: channel 64 wave + l.  pois: sum of the non-finite exact values seen
-    int imax = 0;
+    float pois = 0.f;                        // lane l: channel 64 wave + l.  pois: sum of the non-finite exact values seen
+    best[wave][lane0] = PS_BEST_INIT;        // only wave `wave` ever touches best[wave] before the epilogue: no barrier is needed for it
     double csum = 0.0;                       // lanes < 32: column 32 wave + lane of h2
 
     // Per-lane constants of the tile loop, loaded once per cloud (they depend on the lane and the wave only; the addresses
@@ -386,6 +448,8 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
 
         unsigned msk[2];
         float tmax[2];                       // PS_ABLATE & 64 only
+        // the running maxima of this lane's two channels: last written by this wave's finish of the tile before, two barriers ago
+        const unsigned bhi[2] = {(unsigned)(best[wave][li] >> 32), (unsigned)(best[wave][32 + li] >> 32)};
 #if (PS_ABLATE & 32) && defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {     // timing probe: the screen's results stay live without the compare / scan pass
@@ -408,7 +472,7 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
                 }
             m = fmaxf(m, __shfl_xor(m, 32, 64));
             const float e = epsr[nb];
-            const float vm = __shfl(vmax, nb * 32 + li, 64);
+            const float vm = ps_best_value(bhi[nb], 1u);
             const float thr = m - 2.f * e;
             unsigned k = 0;
 #pragma unroll
@@ -424,18 +488,14 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
         }
 #endif
         const int n = __popc(msk[0]) + __popc(msk[1]);
-        int incl = n;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
+        const int incl = ps_prefix64(n);
         const int total = __builtin_amdgcn_readlane(incl, 63);
         PS_STAMP(7);
 
         if (PS_ABLATE & 64) {
             // no finish: the running maximum follows the tile maxima of z~ instead, so that the second test keeps pruning
-            vmax = fmaxf(vmax, lh ? tmax[1] : tmax[0]);
+            const float tm = lh ? tmax[1] : tmax[0];
+            if (tm == tm) ps_best_max(&best[wave][lane], tm, 0);
             if (counters && lane == 0) atomicAdd(counters + 0, (unsigned long long)total);
         } else if (total <= PS_CAP) {
             // ---- survivors -> list -> exact fp32 values -> running maximum ------------------------------------
@@ -468,26 +528,24 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
                     s = fmaf(w.z, h.z, s);
                     s = fmaf(w.w, h.w, s);
                 }
-                s += __shfl_xor(s, 4, 64);
-                s += __shfl_xor(s, 2, 64);
-                s += __shfl_xor(s, 1, 64);
-                s += b3[wave * 64 + cl];
-                // All eight lanes of a group hold the same s (the butterfly's adds commute).  The pass's eight (value, key) pairs go
-                // to their channels' owner lanes through scalar registers, in list order as before (pois sums in that order).
+                s = ps_sum8(s);
+                const float b3s = b3[wave * 64 + cl];
+                s = s == 0.f ? b3s : s + b3s;                 // a zero sum of either sign: the bias itself (header)
+                // All eight lanes of a group hold the same s (the butterfly's adds commute); its first lane offers (s, point) to
+                // the channel's slot.  Two survivors of one channel in one pass meet in the atomic; max() does not depend on order.
+                const bool live = e < total;
+                if (live && j == 0 && s == s) ps_best_max(&best[wave][cl], s, tile * PN_TM + row);
+                // pois sums a channel's non-finite values in list order, in its owner lane: a pass that holds one (rare) hands
+                // its values over through scalar registers, as every pass used to.
+                if (__any(live && !(fabsf(s) < INFINITY))) {
 #pragma unroll
-                for (int gg = 0; gg < 8; ++gg)
-                    if (e0 + gg < total) {                    // wave-uniform
-                        const int kk = __builtin_amdgcn_readlane(key, gg * 8);
-                        const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), gg * 8));
-                        if ((kk & 63) == lane) {
-                            const int p = tile * PN_TM + (kk >> 6);
-                            if (!(fabsf(v) < INFINITY)) pois += v;
-                            if (v > vmax || (v == vmax && p < imax)) {
-                                vmax = v;
-                                imax = p;
-                            }
+                    for (int gg = 0; gg < 8; ++gg)
+                        if (e0 + gg < total) {                // wave-uniform
+                            const int kk = __builtin_amdgcn_readlane(key, gg * 8);
+                            const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), gg * 8));
+                            if ((kk & 63) == lane && !(fabsf(v) < INFINITY)) pois += v;
                         }
-                    }
+                }
             }
             if (counters) {
                 const unsigned long long h0 = __ballot(msk[0] != 0), h1 = __ballot(msk[1] != 0);
@@ -528,10 +586,7 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
                 }
                 if (lh == nb) {                               // the lane that owns channel 64 wave + 32 nb + li
                     pois += ps + os;
-                    if (bv > vmax || (bv == vmax && bp < imax)) {
-                        vmax = bv;
-                        imax = bp;
-                    }
+                    ps_best_max(&best[wave][lane], bv, bp);   // bv is never NaN: it starts at -inf and only v > bv replaces it
                 }
             }
             if (counters && lane == 0) atomicAdd(counters + 1, 1ull);
@@ -547,7 +602,9 @@ __global__ __launch_bounds__(PS_NW * 64, 2) void pn_fwd_screen_kernel(
     // A non-finite layer-3 value always survives the screen (its z~ is NaN or infinite), so pois is the sum of ALL of this
     // channel's non-finite values: NaN exactly when the dense kernel's column sum is (a NaN, or infinities of both signs),
     // which is when that kernel, like torch.max on a NaN, returns NaN.
-    float v = vmax;
+    const unsigned long long bq = best[ch >> 6][ch & 63];
+    float v = ps_best_value((unsigned)(bq >> 32), (unsigned)bq);
+    const int imax = ps_best_point((unsigned)bq);
     if (pois != pois) v = pois;
     feat[(long)b * ldf + ch] = v;
     argmax[(long)b * PN_C3 + ch] = imax;
