@@ -621,6 +621,55 @@ int pm_mesh_tsdf_query_groups_f32(const float* fields, const int64_t* part_off, 
                                   float oz, float sdf_trunc, const float* base, int base_per_env, float* out, long out_stride,
                                   int brick_skip, void* stream);
 
+/* ------------------------------------------------------------------ contact sensing: posed points against the part grids
+ * pm_mesh_sdf_points_f32 / pm_mesh_sdf_points_groups_f32: the signed distance, in metres, of NP points per environment to the grids
+ * that pm_mesh_tsdf_query_f32 / pm_mesh_tsdf_query_groups_f32 sample at the workspace lattice.  The part tables, pose_R, pose_T, B, M,
+ * p0, p1 and the group tables, t0, t1 mean what they mean there, with the same clamping and memory-safety rules.
+ *   pts               point n of environment b is the three floats at pts + b * pts_env_stride + 3 n; pts_env_stride = 0: one set
+ *                     of points shared by all environments
+ *   carrier (NP) int32         the pose slot in [0, M) whose body carries the point; -1: the point is given in the world frame
+ *   pt_id (NP) int32 or NULL   the id the point is reported under in seg_arg and that settles ties there (NULL: n itself); a
+ *                     negative id marks a padding point, which enters no segment result (its dist / arg are written like any other)
+ *   chunk_sphere (ceil(NP / 64), 4) float32 or NULL   (centre, radius), in the carrier's frame, of a ball that holds the points
+ *                     [64 c, 64 c + 64) of row c; read for a row only when cull != 0, a segment's 64-point run starts at 64 c and all
+ *                     its points share one carrier, so a caller that wants the cull sorts by carrier and pads runs to whole chunks
+ *   seg_off (NS + 1) int32     non-decreasing, seg_off[0] = 0, seg_off[NS] = NP: NS segments of points, one per sensing body; NS = 0
+ *                     (seg_off may be NULL): no segments
+ * Definition, every operation one correctly rounded fp32 operation, no contraction:
+ *   1. w_a = ((R[c,a,0] x_0 + R[c,a,1] x_1) + R[c,a,2] x_2) + T[c,a] with c the carrier; carrier -1: w = x.
+ *   2. every own ordinal of the environment inside [p0, p1) / [t0, t1) is sampled at w exactly as the TSDF entries sample it at a voxel
+ *      centre (d = w - T_p, q = ((d0 R0j + d1 R1j) + d2 R2j), u = (q - bbox_min) / voxel_size, valid iff u_a >= 1 and u_a - shape_a
+ *      <= -2 on all axes, the same trilinear association); an invalid sample is 1.
+ *   3. dist[b * ld_dist + n] = the minimum of the samples, NaN wins, starting from 1: metres, neither divided by a truncation nor
+ *      clamped.  arg[b * ld_dist + n] = the smallest ordinal that attains it, -1 if no sample was below 1.  arg may be NULL.
+ *   4. seg_min[b * NS + s] = the minimum of dist over the segment's points with id >= 0, NaN wins; seg_arg[b * NS + s] = the smallest
+ *      id that attains it (of the NaNs if there is one); an empty segment: 1 and -1.  Both may be NULL together; dist may be NULL
+ *      when they are not.
+ *   5. environment b comes out all-NaN (dist, seg_min) with arg = seg_arg = -1 iff a pose has a non-finite entry -- ungrouped: in any
+ *      of the M slots; grouped: in a slot that one of its own rows or a carrier names.  Other environments are untouched.
+ *   6. a carrier outside [-1, M) makes its point 1 / -1, and no pose is read through it.
+ *   7. cull != 0 lets a wave drop an ordinal for a whole chunk that its sphere cannot bring into the ordinal's valid box.  The output
+ *      with cull on and off is bit-identical, and so are two runs: no floating-point atomics, ordinary vector stores only.
+ * Memory safety: seg_off is cut to [0, NP] and made non-decreasing in the kernel (points that then lie in no segment are not
+ * written); everything else as the TSDF entries state.  Launch: one work-group of four waves per (segment, environment), or per 256
+ * points with NS = 0; lane = point; the sample loop's table and pose reads are scalar loads.
+ * PM_EINVAL (before any launch): a NULL table, pose, pts or carrier; B outside [1, 65535]; M <= 0 (grouped: M > 32768); p0 >= p1,
+ * p1 > M (grouped: the t0, t1, NG, NG_shared, G, max_group_grids and group-table conditions of pm_mesh_tsdf_query_groups_f32); NP
+ * outside [1, 2^30]; NS < 0; NS > 0 with a NULL seg_off; pts_env_stride neither 0 nor >= 3 NP; only one of seg_min, seg_arg; seg_min
+ * with NS = 0; neither dist nor seg_min; ld_dist < NP with dist or arg.  PM_ABI_VERSION stays 163 (no existing signature changed). */
+int pm_mesh_sdf_points_f32(const float* fields, const int64_t* part_off, const int32_t* part_shape, const float* part_bbox_min,
+                           const float* part_voxel_size, const float* pose_R, const float* pose_T, int B, int M, int p0, int p1,
+                           const float* pts, long pts_env_stride, const int32_t* carrier, const int32_t* pt_id,
+                           const float* chunk_sphere, int NP, const int32_t* seg_off, int NS, float* dist, long ld_dist, int32_t* arg,
+                           float* seg_min, int32_t* seg_arg, int cull, void* stream);
+int pm_mesh_sdf_points_groups_f32(const float* fields, const int64_t* part_off, const int32_t* part_shape, const float* part_bbox_min,
+                                  const float* part_voxel_size, const int32_t* grid_slot, int NG, int NG_shared,
+                                  const int32_t* group_off, int G, const int32_t* env_group, int max_group_grids, const float* pose_R,
+                                  const float* pose_T, int B, int M, int t0, int t1, const float* pts, long pts_env_stride,
+                                  const int32_t* carrier, const int32_t* pt_id, const float* chunk_sphere, int NP,
+                                  const int32_t* seg_off, int NS, float* dist, long ld_dist, int32_t* arg, float* seg_min,
+                                  int32_t* seg_arg, int cull, void* stream);
+
 /* ------------------------------------------------------------------ mesh bake (producer of the mesh-TSDF part grids)
  * utils/mesh2sdf.py:201-237 `TSDFfromMesh.mesh2sdf` without kaolin / ManifoldPlus: the signed-distance grid of one triangle mesh.
  * tri: (F, 3, 3) float32 corner positions (faces with two equal corners already dropped by the caller; a remaining zero-area

@@ -112,6 +112,8 @@ SIGNATURES = {
     "pm_tsdf_integrate_f32": (I, [P, P, P, I, I, L, L, F, F, P, P]),
     "pm_mesh_tsdf_query_f32": (I, [P, P, P, P, P, P, P, I, I, I, I, I, F, F, F, F, F, P, I, P, L, I, P]),
     "pm_mesh_tsdf_query_groups_f32": (I, [P, P, P, P, P, P, I, I, P, I, P, I, P, P, I, I, I, I, I, F, F, F, F, F, P, I, P, L, I, P]),
+    "pm_mesh_sdf_points_f32": (I, [P, P, P, P, P, P, P, I, I, I, I, P, L, P, P, P, I, P, I, P, L, P, P, P, I, P]),
+    "pm_mesh_sdf_points_groups_f32": (I, [P, P, P, P, P, P, I, I, P, I, P, I, P, P, I, I, I, I, P, L, P, P, P, I, P, I, P, L, P, P, P, I, P]),
     "pm_mesh_sdf_bake_workspace_bytes": (Z, [I]),
     "pm_mesh_sdf_bake_f32": (I, [P, I, I, I, I, F, F, F, F, F, I, P, P, Z, P]),
     "pm_mesh_pc_query_f32": (I, [P, P, I, P, P, I, I, P, L, I, P, L, P]),

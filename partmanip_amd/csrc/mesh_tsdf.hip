@@ -41,18 +41,15 @@
 // occupancy 8 waves / SIMD; <false> (brick test off, tests only): 30 VGPRs, 104 SGPRs, no scratch, occupancy 7.
 // mesh_tsdf_groups_kernel<true>: 58 VGPRs, 73 SGPRs, no scratch, no LDS, occupancy 8; <false>: 29 VGPRs, 71 SGPRs, occupancy 8.
 // Sharing the body left mesh_tsdf_kernel<true> at its registers and occupancy; <false> went from 31 to 30 VGPRs, occupancy unchanged.
+// Moving the sample into mesh_sdf_sample.h (mt_sample) left all four kernels' instructions as they were, line for line.
 // Measured A/B on one MI355X at B = 1024, res = 50, 12 parts (tools/time_mesh_tsdf.py), kept = the last of each line:
 // part loop with one brick test per (wave, part) 4.09 ms -> lane-parallel tests + ballot 2.25 ms -> branch-free test with every
 // table load up front 2.11 ms -> raw rcp / sqrt in the test 2.07 ms -> corner pairs as 8-byte gathers 1.94 ms.  That is 4 % of
 // the output-bandwidth floor: the time goes to the trilinear gathers (up to 64 distinct cache lines per load instruction).
-#include "common.h"
+#include "mesh_sdf_sample.h"                                 // mt_sample: the per-part sample, shared with mesh_sdf_points.hip
 
 #define MT_BRICK 4                                           // brick edge in voxels; 4^3 = one wave
 #define MT_WAVES 4                                           // bricks (waves) per work-group
-
-typedef float mt_f2 __attribute__((ext_vector_type(2), aligned(4)));
-__device__ __forceinline__ int mt_fin(float x) { return isfinite(x) ? 1 : 0; }
-__device__ __forceinline__ float mt_min_nan(float m, float v) { return (v < m || v != v) ? v : m; }   // torch.min: NaN wins
 
 // The body both kernels share.  GROUPS = false: ordinal p is part p, placed by pose slot p (every group argument is a constant the
 // compiler folds away).  GROUPS = true: the part tables are a grid library and environment b owns the ordinals t < n_ord -- row t
@@ -174,38 +171,10 @@ __device__ __forceinline__ void mt_body(
             }
             const float* R = Rb + slot * 9;
             const float* T = Tb + slot * 3;
-            const float r00 = R[0], r01 = R[1], r02 = R[2], r10 = R[3], r11 = R[4], r12 = R[5], r20 = R[6], r21 = R[7], r22 = R[8];
-            const float t0 = T[0], t1 = T[1], t2 = T[2];
-            const float mn0 = part_bbox_min[p * 3], mn1 = part_bbox_min[p * 3 + 1], mn2 = part_bbox_min[p * 3 + 2];
-            const float vs = part_voxel_size[p];
-            const int rx = part_shape[p * 3], ry = part_shape[p * 3 + 1], rz = part_shape[p * 3 + 2];
-            const long off = part_off[p];
-            const float d0 = sub_rn(cx, t0), d1 = sub_rn(cy, t1), d2 = sub_rn(cz, t2);
-            const float q0 = add_rn(add_rn(mul_rn(d0, r00), mul_rn(d1, r10)), mul_rn(d2, r20));
-            const float q1 = add_rn(add_rn(mul_rn(d0, r01), mul_rn(d1, r11)), mul_rn(d2, r21));
-            const float q2 = add_rn(add_rn(mul_rn(d0, r02), mul_rn(d1, r12)), mul_rn(d2, r22));
-            const float u0 = __fdiv_rn(sub_rn(q0, mn0), vs), u1 = __fdiv_rn(sub_rn(q1, mn1), vs), u2 = __fdiv_rn(sub_rn(q2, mn2), vs);
-            const int valid = (int)inside & (int)(u0 >= 1.0f) & (int)(sub_rn(u0, (float)rx) <= -2.0f) & (int)(u1 >= 1.0f) &
-                              (int)(sub_rn(u1, (float)ry) <= -2.0f) & (int)(u2 >= 1.0f) & (int)(sub_rn(u2, (float)rz) <= -2.0f);
-            float val = 1.0f;
-            if (valid) {                                     // 1 <= l_a <= r_a - 2: all eight corners inside the part's grid
-                const int l0 = (int)u0, l1 = (int)u1, l2 = (int)u2;
-                const float x = sub_rn(u0, (float)l0), y = sub_rn(u1, (float)l1), z = sub_rn(u2, (float)l2);
-                const float* f = fields + off + ((unsigned)(l0 * ry + l1) * (unsigned)rz + (unsigned)l2);
-                const unsigned sy = (unsigned)rz, sx = (unsigned)rz * (unsigned)ry;
-                // the two corners along z are neighbours in memory: one 8-byte load each (4-byte aligned) -- the gathers are what
-                // the kernel waits for (64 lanes x distinct cache lines per instruction), so four of them instead of eight
-                const mt_f2 c00 = *(const mt_f2*)f, c01 = *(const mt_f2*)(f + sy), c10 = *(const mt_f2*)(f + sx),
-                            c11 = *(const mt_f2*)(f + sx + sy);
-                const float f000 = c00.x, f001 = c00.y, f010 = c01.x, f011 = c01.y;
-                const float f100 = c10.x, f101 = c10.y, f110 = c11.x, f111 = c11.y;
-                const float zc = sub_rn(1.0f, z), yc = sub_rn(1.0f, y), xc = sub_rn(1.0f, x);
-                const float lo = add_rn(mul_rn(add_rn(mul_rn(f000, zc), mul_rn(f001, z)), yc),
-                                        mul_rn(add_rn(mul_rn(f010, zc), mul_rn(f011, z)), y));
-                const float hi = add_rn(mul_rn(add_rn(mul_rn(f100, zc), mul_rn(f101, z)), yc),
-                                        mul_rn(add_rn(mul_rn(f110, zc), mul_rn(f111, z)), y));
-                val = add_rn(add_rn(mul_rn(lo, xc), mul_rn(hi, x)), 0.0f);   // value * valid + 1 * !valid
-            }
+            const mt_part P = {R[0], R[1], R[2], R[3], R[4], R[5], R[6], R[7], R[8], T[0], T[1], T[2], part_bbox_min[p * 3],
+                               part_bbox_min[p * 3 + 1], part_bbox_min[p * 3 + 2], part_voxel_size[p], part_shape[p * 3],
+                               part_shape[p * 3 + 1], part_shape[p * 3 + 2], part_off[p]};
+            const float val = mt_sample(fields, P, cx, cy, cz, inside);
             m = mt_min_nan(m, val);
         }
     }

@@ -11,6 +11,9 @@ Not physics (kinematics.py says what the stand-in is).  What closes the grasp_cu
 (csrc/free_body.hip) under the GRASP PREDICATE, a stated choice like `near = 0.01` elsewhere and not a contact:
 hold = is_reached & (|p_l - p_r| <= grasp_width), from the last end_step, grasp_width = 0.055 (the 0.05 cube plus 0.005).  For
 open_drawer the predicate is the task's own extras['is_grasped'] > 0 and the rule is the hold rule of kinematics.py.
+KinematicEnv(contact=ContactSensor) senses, on every observation, how far the hand and the fingers are from the cube's or the
+cabinet's baked grids (contact.py; extras['contact_dist'] / ['in_contact'] / ['penetration']) and grasp='contact' latches the cube on
+finger contact instead of on the gap; it reports and resolves nothing.
 
 A returned observation stays valid until the second step after it (two sets of rows, used in turn): the runners store the previous
 observation after they have stepped."""
@@ -139,11 +142,30 @@ class KinematicEnv:
     runners pass such a path when `save_video` is set); without one the path is ignored.
     scene_rows (N, M) int32 on the device (rows of sim.rigid_body, -1 for an empty slot) with scene_C (MC, 3, 3) or None: observers
     and recorder are then handed the poses of these M bodies from one ops.body_pose_gather launch per step, in place of the task's
-    own parts (make_open_drawer_env(scene_meshes=) builds the table)."""
+    own parts (make_open_drawer_env(scene_meshes=) builds the table).
+    contact: None, or a contact.ContactSensor over the scene pose's slots: every observation then senses (one more launch per step,
+    no host synchronisation) and step()'s extras gain contact_dist (N, NB), the sensor's body distances in metres; in_contact (N, NB)
+    = contact_dist <= contact_margin; penetration (N) = max(0, -min_j contact_dist).  Contact sensing, not contact resolution: the
+    observation rows, rewards and flags are those of the same run without it.  grasp='contact' (grasp_cube only; needs a sensor
+    with bodies named 'lfinger' and 'rfinger'): the hold predicate is in_contact[lfinger] & in_contact[rfinger] of the last
+    observation, in place of the gap rule, one step late like it.  The defaults leave every earlier code path as it was."""
 
     def __init__(self, task, sim, observers=None, add_proprio_obs=False, grasp_width=GRASP_WIDTH, hold=True, random_reset=False,
-                 recorder=None, scene_rows=None, scene_C=None):
+                 recorder=None, scene_rows=None, scene_C=None, contact=None, contact_margin=0.002, grasp="gap"):
         self.task, self.sim = task, sim
+        if grasp not in ("gap", "contact"):
+            raise ValueError(f"grasp: expected 'gap' or 'contact', got {grasp!r}")
+        if grasp == "contact":
+            if not isinstance(task, GraspCubeTensors):
+                raise ValueError("grasp='contact': for grasp_cube only -- an open_drawer environment's target link differs per cabinet "
+                                 "and is not named anywhere, so there is no body to ask the fingers about")
+            if contact is None:
+                raise ValueError("grasp='contact': needs contact= (a contact.ContactSensor)")
+            if contact.names is None or not {"lfinger", "rfinger"} <= set(contact.names):
+                raise ValueError(f"grasp='contact': contact= needs segments named 'lfinger' and 'rfinger' (names=), got {contact.names}")
+            self._fingers = (contact.body("lfinger"), contact.body("rfinger"))
+        self.contact, self.contact_margin, self.grasp_rule = contact, float(contact_margin), grasp
+        self._contact_extras = {}
         self.recorder, self._scene_pose = recorder, None
         self.scene_rows, self.scene_C = scene_rows, scene_C
         if scene_rows is not None:
@@ -220,7 +242,19 @@ class KinematicEnv:
                 ob.write(R, T, rows[mode])
                 if self.add_proprio_obs and not (self.grasp and mode == first):
                     rows[mode][:, ob.width:].copy_(rows["proprio_state"])
+        if self.contact is not None:
+            self._sense()
         return dict(rows)
+
+    def _sense(self):
+        """The contact sensor on the scene pose the observers use: one launch, the three extras, and with grasp='contact' the hold
+        predicate of the next step.  It reports; nothing is pushed back or blocked."""
+        R, T = self.compute_scene_pose()
+        body = self.contact.sense(R, T, per_point=False).body_dist                # (N, NB)
+        touch = body <= self.contact_margin
+        self._contact_extras = {"contact_dist": body, "in_contact": touch, "penetration": torch.clamp(-body.min(dim=1)[0], min=0.0)}
+        if self.grasp_rule == "contact":
+            torch.logical_and(touch[:, self._fingers[0]], touch[:, self._fingers[1]], out=self._hold)
 
     def reset(self):
         """hand_base.reset: every environment starts over; the observation of the first frame.  progress_buf is 0 afterwards."""
@@ -255,7 +289,7 @@ class KinematicEnv:
         if save_image_path is not None and self.recorder is not None:
             R, T = self.compute_scene_pose()                              # the observers' pose where there are observers
             self.recorder(R, T, save_image_path)
-        return obs, task.rew_buf, task.reset_buf, dict(task.extras)
+        return obs, task.rew_buf, task.reset_buf, dict(task.extras, **self._contact_extras)
 
     def compute_scene_pose(self):
         """(rot (N, M, 3, 3), pos (N, M, 3)) of the last step, as the observers and the recorder get them: the task's own parts, or
@@ -284,7 +318,7 @@ def _scene(base_pose, dof):
 
 def make_grasp_cube_env(cfg_task, num_envs, device, urdf, dt, base_pose=None, dof=None, observers=None, add_proprio_obs=False,
                         grasp_width=GRASP_WIDTH, hold=True, max_velocity=None, free_body_pose=(0, 0, 0.025, 0, 0, 0, 1), rest_z=0.025,
-                        fall_speed=0.0, reset_range=0.15, recorder=None):
+                        fall_speed=0.0, reset_range=0.15, recorder=None, contact=None, contact_margin=0.002, grasp="gap"):
     """GraspCubeTensors + KinematicSim(free_body=True) around the robot of `urdf` (a path or a loaded tree; fixed or mobile, through
     tree.robot_kwargs()).  cfg_task: cfg/tasks/grasp_cube.yaml as a dict; base_pose (7), divided by its norm, and dof (the default
     joint positions; None: cfg_task['robot']['dof'], else mid-range) place the robot."""
@@ -301,7 +335,8 @@ def make_grasp_cube_env(cfg_task, num_envs, device, urdf, dt, base_pose=None, do
                        tips=(robot.ltip_rb_index, robot.rtip_rb_index), free_body_pose=free_body_pose, rest_z=rest_z, fall_speed=fall_speed,
                        reset_range=reset_range)
     return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, grasp_width=grasp_width, hold=hold,
-                        random_reset=bool(cfg_task.get("random_reset", False)), recorder=recorder)
+                        random_reset=bool(cfg_task.get("random_reset", False)), recorder=recorder, contact=contact,
+                        contact_margin=contact_margin, grasp=grasp)
 
 
 def scene_row_table(part_slot, rb_row0, obj_rb_row0, obj_bodies, max_bodies=None):
@@ -319,7 +354,7 @@ def scene_row_table(part_slot, rb_row0, obj_rb_row0, obj_bodies, max_bodies=None
 
 
 def make_open_drawer_env(cfg_task, num_envs, device, urdf, assets, dt, observers=None, add_proprio_obs=False, hold=True,
-                         max_velocity=None, recorder=None, scene_meshes=None):
+                         max_velocity=None, recorder=None, scene_meshes=None, contact=None, contact_margin=0.002, grasp="gap"):
     """OpenDrawerTensors + KinematicSim(objects=...) wired as INTEGRATION.md's loop: assets = load_drawer_assets(folders, scale),
     handed out as env % num_objs; the robot of `urdf` (the mobile Franka of the shipped config, or the fixed one).
     scene_meshes: None, or load_drawer_meshes(assets) -- the same list a DepthFromMesh(meshes=robot parts, groups=scene_meshes,
@@ -349,4 +384,4 @@ def make_open_drawer_env(cfg_task, num_envs, device, urdf, assets, dt, observers
         rows = torch.from_numpy(rows).to(device)
         C = None if task.part_C is None else task.part_C[:nr].contiguous()
     return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, hold=hold, recorder=recorder, scene_rows=rows,
-                        scene_C=C)
+                        scene_C=C, contact=contact, contact_margin=contact_margin, grasp=grasp)

@@ -33,6 +33,10 @@ The shared grids keep slots 0 .. S - 1; groups[k][j] is the grid dict of body j 
 whatever environment holds object k.  query_tsdf then takes (N, part_num, ...) poses with part_num = S + the largest body count --
 the table make_open_drawer_env(scene_meshes=) hands its observers -- and is one launch of pm_mesh_tsdf_query_groups_f32: an
 environment samples its own cabinet's grids only, and the NaN poses past its body count are never looked at.
+
+Beyond the reference: query_points(points, pose_R, pose_T, carrier=...) samples the same grids at arbitrary posed points and returns
+metres (pm_mesh_sdf_points_f32, csrc/mesh_sdf_points.hip; the per-part arithmetic is shared with the kernel above through
+csrc/mesh_sdf_sample.h).  contact.py builds the contact sensor on it.
 """
 import hashlib
 import os
@@ -185,6 +189,7 @@ class TSDFfromMesh:
         self.groups = groups is not None
         self._group_dicts = []
         self._scene = None
+        self._point_layouts = {}                              # query_points: (id(carrier), id(segments), NP) -> layout
         if self.groups:
             slot = list(range(len(self.sdf_dict_list)))
 
@@ -314,6 +319,64 @@ class TSDFfromMesh:
 
     query_tsdf_parallel = query_tsdf
     query_tsdf_naive = query_tsdf          # the reference's naive path cannot run (class docstring); same kernel
+
+    # ------------------------------------------------------------------------------------------------ posed points (contact.py)
+    def _sdf_points(self, pose_R, pose_T, pts, carrier, p0, p1, group_of=None, **kw):
+        """ops.mesh_sdf_points over this object's tables, ordinals [p0, p1) of _row_range: the grouped entry with groups=."""
+        eg = None
+        if self.groups:
+            eg = self._scene.for_call(ops.check_poses(pose_R, pose_T, self.part_num)[0], group_of)
+        elif group_of is not None:
+            raise ValueError("group_of: this object was built without groups=")
+        pose_R = pose_R.to(torch.float32).reshape(-1, self.part_num, 3, 3).contiguous()
+        pose_T = pose_T.to(torch.float32).reshape(-1, self.part_num, 3).contiguous()
+        tables = (self.sdf_field, self.sdf_field_off, self.sdf_field_res, self.sdf_bbox_min, self.sdf_voxel_size)
+        if eg is not None:
+            kw.update(grid_slot=self._grid_slot, NG_shared=self.num_shared, group_off=self._scene.group_off_dev, env_group=eg,
+                      max_group_grids=self.max_group_grids)
+        return ops.mesh_sdf_points(*tables, pose_R, pose_T, pts, carrier, p0, p1, **kw)
+
+    def query_points(self, points, pose_R, pose_T, carrier=None, parts=None, group_of=None, segments=None, return_arg=False,
+                     cull=True):
+        """The signed distance, in metres, of posed points to the part grids (one launch of pm_mesh_sdf_points_f32, with groups= of
+        the grouped entry): points (NP, 3) shared by all environments or (b, NP, 3); carrier: None (the points are in the world frame)
+        or (NP,) integers, the pose slot whose body carries each point (-1: world); parts (lo, hi): the ordinals sensed against
+        (default all: the parts, or with groups= an environment's own rows); segments: None or a list of point counts that sum to NP.
+        Returns dist (b, NP) -- the minimum over the ordinals of the trilinear sample, 1.0 where no grid's valid box holds the point;
+        a distance only within the grids' truncation band -- then, when asked for, arg (b, NP) int32 (the ordinal that attains it, -1
+        for none) and (seg_min (b, NS), seg_arg (b, NS) int32: each segment's minimum and the index of the point that attains it).
+        Points whose carriers are not sorted are sorted for the kernel and the results come back in the caller's order; that layout is
+        built once per (carrier, segments) pair of objects and kept (a list changed in place afterwards is not noticed)."""
+        from .contact import PointLayout, chunk_spheres
+        points = torch.as_tensor(points, dtype=torch.float32)
+        if points.dim() not in (2, 3) or points.shape[-1] != 3 or points.shape[-2] == 0:
+            raise ValueError(f"points: expected (NP > 0, 3) or (b, NP, 3), got {tuple(points.shape)}")
+        NP = int(points.shape[-2])
+        top = self._row_range()[1]
+        lo, hi = (0, top) if parts is None else (int(v) for v in parts)
+        if not 0 <= lo < hi <= top:
+            raise ValueError(f"parts: expected a non-empty ordinal range inside [0, {top}), got ({lo}, {hi})")
+        key = (id(carrier), id(segments), NP)
+        hit = self._point_layouts.get(key)
+        if hit is None or hit[0] is not carrier or hit[1] is not segments:
+            if carrier is not None:
+                c = np.asarray(carrier.cpu().numpy() if torch.is_tensor(carrier) else carrier)
+                if c.shape != (NP,) or c.dtype.kind not in "iu" or c.min() < -1 or c.max() >= self.part_num:
+                    raise ValueError(f"carrier: expected {NP} pose slots in [-1, {self.part_num}), got {c.dtype} {c.shape}")
+            lay = PointLayout(NP, carrier, segments)
+            if len(self._point_layouts) >= 8:
+                self._point_layouts.pop(next(iter(self._point_layouts)))
+            hit = self._point_layouts[key] = (carrier, segments, lay, lay.on(self.device))
+        lay, (src, pt_id, car, seg_off, pos) = hit[2], hit[3]
+        points = points.to(self.device)
+        pts = (points if lay.identity else points.index_select(-2, src)).contiguous()
+        sphere = chunk_spheres(pts) if cull and pts.dim() == 2 else None         # per-environment points are not culled
+        d, a, sm, sa = self._sdf_points(pose_R, pose_T, pts, car, lo, hi, group_of, pt_id=pt_id, chunk_sphere=sphere, seg_off=seg_off,
+                                        want_arg=return_arg, cull=cull)
+        if not lay.identity:
+            d, a = d.index_select(1, pos), None if a is None else a.index_select(1, pos)
+        out = (d,) + ((a,) if return_arg else ()) + (((sm, sa),) if segments is not None else ())
+        return out[0] if len(out) == 1 else out
 
     def query_tsdf_seperately(self, pose_R, pose_T, out_scene=None, out_obj=None, group_of=None):
         """(scene, obj): the parts before the last against the base field, and the last part (the object) alone against the

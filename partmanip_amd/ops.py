@@ -1654,7 +1654,9 @@ def _mesh_tsdf_tables(fields, part_off, part_shape, part_bbox_min, part_voxel_si
     """The table checks mesh_tsdf_query and mesh_tsdf_query_groups share.  The tables have one row per pose slot (M parts), or when
     `grouped` one per grid of a library (NG >= 1 grids, any M).  Returns (the tables' rows, B, M)."""
     _f32c(fields, "fields"), _f32c(part_bbox_min, "part_bbox_min"), _f32c(part_voxel_size, "part_voxel_size")
-    _f32c(pose_R, "pose_R"), _f32c(pose_T, "pose_T"), _f32c(base, "base")
+    _f32c(pose_R, "pose_R"), _f32c(pose_T, "pose_T")
+    if base is not None:                                      # the point query has no base field
+        _f32c(base, "base")
     n = part_off.numel()
     if part_off.dtype != torch.int64 or not part_off.is_contiguous() or (grouped and n == 0):
         raise ValueError("part_off: expected a contiguous int64 tensor" + (" of at least one row" if grouped else ""))
@@ -1733,6 +1735,101 @@ def mesh_tsdf_query_groups(fields, part_off, part_shape, part_bbox_min, part_vox
                                                 float(vox_size), ox, oy, oz, float(sdf_trunc), _ptr(base), per_env, _ptr(out), ldo,
                                                 1 if brick_skip else 0, _stream()), "pm_mesh_tsdf_query_groups_f32")
     return out
+
+
+def _host_i32(a, name, n, lo, hi, device):
+    """A host table (list, numpy, CPU tensor) of n integers in [lo, hi) -> int32 on `device`; a device tensor is checked for type and
+    length only (reading it would synchronise; the kernel cuts whatever it holds)."""
+    if torch.is_tensor(a) and a.is_cuda:
+        _i32c(a, name)
+        if tuple(a.shape) != (n,):
+            raise ValueError(f"{name}: expected ({n},), got {tuple(a.shape)}")
+        return a
+    v = np.asarray(a.numpy() if torch.is_tensor(a) else a)
+    if v.dtype.kind not in "iu" or v.shape != (n,) or (n and (v.min() < lo or v.max() >= hi)):
+        raise ValueError(f"{name}: expected {n} integers in [{lo}, {hi}), got {v.dtype} {v.shape}")
+    return torch.from_numpy(np.ascontiguousarray(v, dtype=np.int32)).to(device)
+
+
+def mesh_sdf_points(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, pts, carrier=None, p0=0, p1=None,
+                    pt_id=None, chunk_sphere=None, seg_off=None, want_dist=True, want_arg=False, dist=None, cull=True, grid_slot=None,
+                    NG_shared=None, group_off=None, env_group=None, max_group_grids=None):
+    """Signed distance, in metres, of posed points to the part grids (pm_mesh_sdf_points_f32; with grid_slot= the grouped entry
+    pm_mesh_sdf_points_groups_f32, whose tables are those of mesh_tsdf_query_groups).  Part tables and poses as mesh_tsdf_query.
+    pts (NP, 3) shared by all environments or (B, NP, 3); carrier: None (world points) or NP integers in [-1, M), the pose slot that
+    carries each point (-1: world); [p0, p1): the ordinals sampled.  pt_id: None or NP integers, the id a point is reported under in
+    seg_arg (negative: a padding point, in no segment result); chunk_sphere: None or (ceil(NP / 64), 4) float32, what the cull
+    reads (include/partmanip_hip.h); seg_off: None or NS + 1 non-decreasing integers from 0 to NP.  carrier / pt_id / seg_off on the
+    host are validated and copied; on the device they are checked for type and length only.  dist: None or a float32 view (B, >= NP)
+    with unit inner stride to write into.  Returns (dist (B, NP) or None, arg (B, NP) int32 or None, seg_min (B, NS) or None, seg_arg
+    (B, NS) int32 or None): dist unless want_dist is False, arg with want_arg, the segment pair with seg_off."""
+    grouped = grid_slot is not None
+    NG, B, M = _mesh_tsdf_tables(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, None, grouped=grouped)
+    dev = pose_R.device
+    if not torch.is_tensor(pts) or pts.dtype != torch.float32 or not pts.is_contiguous() or pts.dim() not in (2, 3) or \
+            pts.shape[-1] != 3 or pts.shape[-2] == 0 or (pts.dim() == 3 and pts.shape[0] != B):
+        raise ValueError(f"pts: expected a contiguous float32 (NP > 0, 3) or ({B}, NP, 3), got "
+                         f"{tuple(pts.shape) if torch.is_tensor(pts) else type(pts).__name__}")
+    NP = int(pts.shape[-2])
+    if NP > 2 ** 30:
+        raise ValueError(f"pts: at most 2^30 points, got {NP}")
+    stride = 3 * NP if pts.dim() == 3 else 0
+    carrier = torch.full((NP,), -1, dtype=torch.int32, device=dev) if carrier is None else _host_i32(carrier, "carrier", NP, -1, M, dev)
+    if pt_id is not None:
+        pt_id = _host_i32(pt_id, "pt_id", NP, -2 ** 31, 2 ** 31, dev)
+    NS = 0
+    if seg_off is not None:
+        if torch.is_tensor(seg_off) and seg_off.is_cuda:
+            _i32c(seg_off, "seg_off")
+            if seg_off.dim() != 1 or seg_off.numel() < 2:
+                raise ValueError(f"seg_off: expected (NS + 1 >= 2,), got {tuple(seg_off.shape)}")
+        else:
+            so = np.asarray(seg_off.numpy() if torch.is_tensor(seg_off) else seg_off)
+            if so.dtype.kind not in "iu" or so.ndim != 1 or so.size < 2 or so[0] != 0 or so[-1] != NP or (np.diff(so) < 0).any():
+                raise ValueError(f"seg_off: expected NS + 1 >= 2 non-decreasing integers from 0 to NP = {NP}, got {so.tolist() if so.ndim == 1 else so.shape}")
+            seg_off = torch.from_numpy(np.ascontiguousarray(so, dtype=np.int32)).to(dev)
+        NS = seg_off.numel() - 1
+    if chunk_sphere is not None:
+        _f32c(chunk_sphere, "chunk_sphere")
+        if tuple(chunk_sphere.shape) != ((NP + 63) // 64, 4):
+            raise ValueError(f"chunk_sphere: expected ({(NP + 63) // 64}, 4), got {tuple(chunk_sphere.shape)}")
+    if not want_dist and dist is None and not want_arg and NS == 0:
+        raise ValueError("want_dist=False: needs seg_off (nothing would be computed)")
+    if grouped:
+        grid_slot = _host_i32(grid_slot, "grid_slot", NG, 0, M, dev)
+        group_off, env_group, G, most = face_groups(group_off, env_group, NG, NG_shared, B, dev, max_group_grids,
+                                                    names=("NG", "NG_shared", "max_group_grids"))
+        top = int(NG_shared) + most
+    else:
+        if any(a is not None for a in (NG_shared, group_off, env_group, max_group_grids)):
+            raise ValueError("NG_shared / group_off / env_group / max_group_grids: need grid_slot=")
+        top = M
+    p0, p1 = int(p0), top if p1 is None else int(p1)
+    if not 0 <= p0 < p1 <= top:
+        raise ValueError(f"p0, p1: expected 0 <= p0 < p1 <= {top}, got {p0}, {p1}")
+    ld = NP
+    if dist is not None:
+        _out_rows(dist, B, NP, name="dist")
+    _one_device("mesh_sdf_points", fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, pts, carrier, pt_id,
+                chunk_sphere, seg_off, dist, grid_slot, group_off, env_group)
+    arg = seg_min = seg_arg = None
+    if want_dist or dist is not None:
+        dist, ld = _out_rows(dist, B, NP, dev, name="dist")
+    if want_arg:
+        arg = torch.empty(B, ld, dtype=torch.int32, device=dev)
+    if NS:
+        seg_min = torch.empty(B, NS, dtype=torch.float32, device=dev)
+        seg_arg = torch.empty(B, NS, dtype=torch.int32, device=dev)
+    head = (_ptr(fields), _ptr(part_off), _ptr(part_shape), _ptr(part_bbox_min), _ptr(part_voxel_size))
+    tail = (_ptr(pts), stride, _ptr(carrier), _ptr(pt_id), _ptr(chunk_sphere), NP, _ptr(seg_off), NS, _ptr(dist), ld, _ptr(arg),
+            _ptr(seg_min), _ptr(seg_arg), 1 if cull else 0, _stream())
+    with TIMER.bracket("mesh_sdf_points"):
+        if grouped:
+            check(lib.pm_mesh_sdf_points_groups_f32(*head, _ptr(grid_slot), NG, int(NG_shared), _ptr(group_off), G, _ptr(env_group), most,
+                                                    _ptr(pose_R), _ptr(pose_T), B, M, p0, p1, *tail), "pm_mesh_sdf_points_groups_f32")
+        else:
+            check(lib.pm_mesh_sdf_points_f32(*head, _ptr(pose_R), _ptr(pose_T), B, M, p0, p1, *tail), "pm_mesh_sdf_points_f32")
+    return dist, None if arg is None else arg[:, :NP], seg_min, seg_arg
 
 
 def mesh_pc_query(pts, part_of, pose_R, pose_T, sel=None, out=None, labels=None):
