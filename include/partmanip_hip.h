@@ -979,6 +979,71 @@ int pm_articulation_step_f32(const int32_t* parent, const int32_t* jtype, const 
                              const int32_t* rb_row0, long rb_stride, long rb_rows, const int32_t* dof_row0, long dof_stride, int N,
                              int nb, int nd, float* rigid_body, float* jac, void* stream);
 
+/* ------------------------------------------------------------------ contact blocking: a swept test of one kinematic step
+ * pm_articulation_sweep_f32 / pm_articulation_sweep_groups_f32 (csrc/articulation_sweep.hip): how far along this step can the robot
+ * go before one of its sensing points enters a target grid.  One launch, one work-group per environment; it writes no state.  A
+ * stated rule, not physics: nothing slides, bounces or is pushed -- the robot stops short of contact.
+ * Arguments, each meaning what it means in the entry it comes from:
+ *   pm_articulation_step_f32: the tree tables (anc_mask is not needed), dof_lo, dof_hi, vmax or NULL, dt, base_pose / base_stride,
+ *     dof_state / dof_rows / dof_row0 / dof_stride (ONLY READ here), targets / tgt_stride (required), reset or NULL, N, nb, nd;
+ *   pm_mesh_sdf_points(_groups)_f32: the part tables, (the group tables and max_group_grids,) pose_R, pose_T (the caller's scene
+ *     pose table, N x M slots), M, p0, p1 (t0, t1), pts, pts_env_stride, carrier, pt_id, chunk_sphere, NP, seg_off, NS >= 1, cull;
+ *   slot_body (M) int32   the robot-local body in [0, nb) whose frame places pose slot m; -1: the slot's pose is the table's;
+ *                         any other value: the slot's pose is NaN (what a row outside the rigid-body tensor gives the gather)
+ *   slot_C (MC <= M, 3, 3) or NULL with MC = 0   the part_C of pm_body_pose_gather_f32
+ *   S in [1, 63]          the number of parts the step is cut into
+ *   block_margin          the distance at or below which a candidate counts as contact
+ *   free_env (N) bytes or NULL   environments that are not guarded
+ * Outputs: sweep_dist (N, S + 1) float32, steps (N) int32, targets_out (N, nd) float32 (contiguous).
+ * Definition.  Every fp32 operation is one correctly rounded operation, no contraction.
+ *   1. q' = the drive rule of pm_articulation_step_f32, operation for operation: reset[b] set: clamp(t, lo, hi); else
+ *      clamp(q + clamp(t - q, -vmax dt, vmax dt), lo, hi), or clamp(t, lo, hi) with vmax NULL.  clamp passes a NaN through.
+ *   2. candidates k = 0 .. S:  a_k = (float)k / (float)S;  q_0 = clamp(q, lo, hi);  q_S = q';
+ *      q_k = clamp(q + a_k (q' - q), lo, hi) for 0 < k < S.
+ *   3. the candidate's pose table P_k = the caller's table, except that a slot m with slot_body[m] >= 0 takes the pose that
+ *      pm_body_pose_gather_f32 computes (part_C = slot_C) from the rigid-body row that pm_articulation_step_f32 writes for the joint
+ *      state q_k: the same float64 chain rounded once, quat_to_mat, the C product in the same association.
+ *   4. sweep_dist[b, k] = the minimum over the NS segments, NaN wins, of the seg_min that pm_mesh_sdf_points(_groups)_f32 returns on
+ *      P_k, by its rules 1 to 7 (the NaN-pose rule, padding ids, carriers outside [-1, M), cull on = cull off).
+ *   5. candidate k >= 1 is admissible iff D_k > block_margin or D_k >= D_{k-1} (D = sweep_dist[b]): a robot already in contact
+ *      may move away or along, never deeper.  A NaN is not admissible.
+ *   6. steps[b] = the largest K such that candidates 1 .. K are all admissible (0 if candidate 1 is not); forced to S where
+ *      reset[b] or free_env[b] is set (sweep_dist is written for those environments all the same).
+ *   7. targets_out[b] = q_steps[b].  Passed as the targets of pm_articulation_step_f32 with vmax NULL and the same reset, the
+ *      executed joint state is that candidate bit for bit (clamp is idempotent).
+ * So sweep_dist[:, k] has the bits of the three existing entries run one after the other on q_k, two runs give the same bits (no
+ * floating-point atomics, ordinary vector stores only), and an environment's outputs depend on its own rows only: not on N or on
+ * the block it lands in; a NaN target, joint or pose stays in its environment (a NaN candidate is not admissible: steps = 0 from
+ * a NaN target).  An environment whose DOF rows would not lie inside [0, dof_rows) reads none and is NaN throughout.
+ * Memory safety as in the two entries; no address is formed from an unchecked slot_body.  No synchronisation or allocation.
+ * PM_EINVAL (before any launch): what pm_articulation_step_f32 refuses of its arguments (with targets required and dt > 0), what
+ * pm_mesh_sdf_points(_groups)_f32 refuses of theirs (with NS >= 1 required), a NULL slot_body or output, MC outside [0, M], MC > 0
+ * with a NULL slot_C, S outside [1, 63], a NaN block_margin, or (S + 1) ((7 nb | 1) 8 + 4 nd) bytes of LDS above 57344 (the Franka's
+ * 13 bodies fit S = 63; 64 bodies and DOFs fit S = 13).  PM_ABI_VERSION stays 163 with these additions (no existing signature changed). */
+int pm_articulation_sweep_f32(const int32_t* parent, const int32_t* jtype, const int32_t* dof, const float* origin_q,
+                              const float* origin_t, const float* axis, const float* dof_lo, const float* dof_hi, const float* vmax,
+                              float dt, const float* base_pose, long base_stride, const float* dof_state, long dof_rows,
+                              const float* targets, long tgt_stride, const uint8_t* reset, const int32_t* dof_row0, long dof_stride,
+                              int N, int nb, int nd, const float* fields, const int64_t* part_off, const int32_t* part_shape,
+                              const float* part_bbox_min, const float* part_voxel_size, const float* pose_R, const float* pose_T, int M,
+                              int p0, int p1, const float* pts, long pts_env_stride, const int32_t* carrier, const int32_t* pt_id,
+                              const float* chunk_sphere, int NP, const int32_t* seg_off, int NS, int cull, const int32_t* slot_body,
+                              const float* slot_C, int MC, int S, float block_margin, const uint8_t* free_env, float* sweep_dist,
+                              int32_t* steps, float* targets_out, void* stream);
+int pm_articulation_sweep_groups_f32(const int32_t* parent, const int32_t* jtype, const int32_t* dof, const float* origin_q,
+                                     const float* origin_t, const float* axis, const float* dof_lo, const float* dof_hi,
+                                     const float* vmax, float dt, const float* base_pose, long base_stride, const float* dof_state,
+                                     long dof_rows, const float* targets, long tgt_stride, const uint8_t* reset,
+                                     const int32_t* dof_row0, long dof_stride, int N, int nb, int nd, const float* fields,
+                                     const int64_t* part_off, const int32_t* part_shape, const float* part_bbox_min,
+                                     const float* part_voxel_size, const int32_t* grid_slot, int NG, int NG_shared,
+                                     const int32_t* group_off, int G, const int32_t* env_group, int max_group_grids,
+                                     const float* pose_R, const float* pose_T, int M, int t0, int t1, const float* pts,
+                                     long pts_env_stride, const int32_t* carrier, const int32_t* pt_id, const float* chunk_sphere,
+                                     int NP, const int32_t* seg_off, int NS, int cull, const int32_t* slot_body, const float* slot_C,
+                                     int MC, int S, float block_margin, const uint8_t* free_env, float* sweep_dist, int32_t* steps,
+                                     float* targets_out, void* stream);
+
 /* ------------------------------------------------------------------ kinematic objects (a stand-in for the simulator's cabinets)
  * One articulated object per environment, each environment a tree of its own out of a library of K, posed into the flat
  * rigid_body (rb_rows, 13) and dof_state (dof_rows, 2) in one launch (csrc/articulation_objects.hip).  Kinematics only: no dynamics,

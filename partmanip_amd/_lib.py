@@ -133,6 +133,10 @@ SIGNATURES = {
                                     P, P, P]),
     "pm_open_drawer_reset_f32": (I, [P, P, P, I, I, I, I, I, P, P, I, P, F, F, P, P, P, P, L, P, P, P, P]),
     "pm_articulation_step_f32": (I, [P, P, P, P, P, P, P, P, P, P, F, P, L, P, L, P, L, P, P, L, L, P, L, I, I, I, P, P, P]),
+    "pm_articulation_sweep_f32": (I, [P, P, P, P, P, P, P, P, P, F, P, L, P, L, P, L, P, P, L, I, I, I, P, P, P, P, P, P, P, I, I, I, P, L, P, P, P,
+                                      I, P, I, I, P, P, I, I, F, P, P, P, P, P]),
+    "pm_articulation_sweep_groups_f32": (I, [P, P, P, P, P, P, P, P, P, F, P, L, P, L, P, L, P, P, L, I, I, I, P, P, P, P, P, P, I, I, P, I, P,
+                                             I, P, P, I, I, I, P, L, P, P, P, I, P, I, I, P, P, I, I, F, P, P, P, P, P]),
     "pm_articulation_objects_step_f32": (I, [P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, L, P, P, P, L, P, L, P, P, P, P, F, I, P]),
     "pm_free_body_step_f32": (I, [P, L, P, P, P, I, I, P, P, P, P, P, F, F, F, F, I, P]),
     "pm_voxel_grid0_f32": (I, [P, L, I, I, I, I, P, P, P, P]),

@@ -11,8 +11,20 @@ environment's own cabinet rows for open_drawer -- so the robot never senses itse
 
 What the numbers are.  A grid holds distances clamped to the bake's truncation, and a trilinear sample of it is a distance only
 within that band; outside every target's valid box the value is 1.0 ("far", the reference's own out-of-box value), not a distance.
-body_dist <= margin is therefore a contact test, and max(0, -body_dist) a penetration depth up to the truncation; nothing here
-pushes bodies apart, blocks a step or models friction (KinematicEnv(contact=) reports, it does not resolve).
+body_dist <= margin is therefore a contact test, and max(0, -body_dist) a penetration depth up to the truncation.  The sensor
+reports; nothing here pushes bodies apart or models friction.
+
+Contact blocking.  StepGuard(sensor, slot_body, slot_C, substeps=8, margin=0.0) is the one contact RESPONSE: handed to
+KinematicSim.step(guard=) (KinematicEnv(resolve='block') does that), it runs one launch of pm_articulation_sweep_f32
+(csrc/articulation_sweep.hip) before the articulation's: the step is cut into `substeps` parts, every part's joint state is posed and
+sensed with this sensor's points and targets, and the robot stops at the last part before the first that would bring a sensing
+point within `margin` of a target, or deeper into one it already touches.  A stated rule, not physics, and its limits are these:
+  - one fraction per environment: the WHOLE robot stops when any sensing body would touch;
+  - a target thinner than the distance a sensing point covers in one part can be stepped over between two candidates;
+  - contact is sticky: motion that lowers the distance below the margin is refused even when it is mostly tangential; motion that
+    keeps or raises the distance is admitted, so the robot can always back out;
+  - environments that are reset or held are not guarded (a held cube or drawer moves with the hand, the fingers keep closing);
+  - no self-collision, no ground plane, no friction, nothing slides and nothing is pushed.
 
 Layout.  The kernel's per-wave cull wants the 64 points of a wave to share one carrier and one bounding sphere, and its segment
 reduction wants a segment to start on a chunk boundary: PointLayout sorts each segment's points by carrier (stably) and pads every
@@ -158,3 +170,63 @@ class ContactSensor:
         if per_point and not self.layout.identity:
             d, a = d.index_select(1, self._pos), a.index_select(1, self._pos)
         return ContactReading(d, a, bd, bp)
+
+
+class StepGuard:
+    """Contact blocking for KinematicSim.step(guard=): the tables of one swept test per step and its three outputs.
+
+    sensor: a ContactSensor (its points, carriers, segments and targets are what is swept); slot_body: one integer per pose slot of
+    the sensor's table, the ROBOT-LOCAL body in [0, nb) whose frame places that slot, or -1 for a slot the robot does not place (the
+    cube, a cabinet's bodies: their pose is the table's); slot_C (MC, 3, 3) or None: the mesh-frame matrices of the first MC slots,
+    as ops.body_pose_gather takes them; substeps S in [1, 63]; margin: the distance at or below which a candidate is contact.
+    set_scene(pose_R, pose_T) hands over the scene pose the test reads for the slots the robot does not place (the caller's last
+    observation); sweep() is what KinematicSim.step calls.  After a step: sweep_dist (N, S + 1) the candidates' distances, steps (N)
+    int32 the parts taken, targets (N, nd) the joint state the robot was sent to.  The module docstring states the rule's limits."""
+
+    def __init__(self, sensor, slot_body, slot_C=None, substeps=8, margin=0.0):
+        M = int(sensor.tsdf.part_num)
+        sb = _ints(slot_body, "slot_body", M)
+        if sb.min() < -1:
+            raise ValueError(f"slot_body: expected robot bodies or -1, got {int(sb.min())}")
+        self.substeps, self.margin = int(substeps), float(margin)
+        if not 1 <= self.substeps <= 63:
+            raise ValueError(f"substeps: expected 1 .. 63 parts of a step, got {substeps}")
+        if self.margin != self.margin:
+            raise ValueError("margin: expected a number, got NaN")
+        self.sensor, self.device = sensor, sensor.device
+        self._slot_body_host = sb
+        self.slot_body = torch.from_numpy(sb.astype(np.int32)).to(self.device)
+        self.slot_C = None
+        if slot_C is not None:
+            C = torch.as_tensor(slot_C, dtype=torch.float32).to(self.device).contiguous()
+            if C.dim() != 3 or tuple(C.shape[1:]) != (3, 3) or C.shape[0] > M:
+                raise ValueError(f"slot_C: expected (MC <= {M}, 3, 3), got {tuple(C.shape)}")
+            self.slot_C = C
+        self._pose = None
+        self.sweep_dist = self.steps = self.targets = None
+
+    def set_scene(self, pose_R, pose_T, group_of=None):
+        """The scene pose (N, M, 3, 3) / (N, M, 3) the next sweep reads; the slots the robot places are ignored."""
+        self._pose = (pose_R, pose_T, group_of)
+
+    def sweep(self, sim, pos_act, reset=None, hold=None, cull=True):
+        """The sweep launch for sim's next step towards pos_act; returns the guarded targets (N, nd).  Environments with reset or
+        hold set take the whole step."""
+        if self._pose is None:
+            raise ValueError("StepGuard: set_scene(pose_R, pose_T) comes before the first guarded step")
+        nb = sim.art.num_bodies
+        if self._slot_body_host.max() >= nb:
+            raise ValueError(f"slot_body: expected bodies in [-1, {nb}), got {int(self._slot_body_host.max())}")
+        s = self.sensor
+        tables, R, T, groups = s.tsdf._point_tables(*self._pose)
+        N, nd = sim.num_envs, sim.art.num_dofs
+        if self.sweep_dist is None or self.sweep_dist.shape[0] != N or self.targets.shape[1] != nd:
+            f = dict(dtype=torch.float32, device=self.device)
+            self.sweep_dist = torch.empty(N, self.substeps + 1, **f)
+            self.steps = torch.empty(N, dtype=torch.int32, device=self.device)
+            self.targets = torch.empty(N, nd, **f)
+        sim.art.sweep(sim.dof_state, sim.base_pose, pos_act, sim.dt, *tables, R, T, s._pts, s._carrier, s._seg_off, self.slot_body,
+                      self.substeps, margin=self.margin, reset=reset, free=hold, vmax=sim.max_velocity, dof_row0=sim.dof_row0,
+                      slot_C=self.slot_C, p0=s.targets[0], p1=s.targets[1], pt_id=s._pt_id, chunk_sphere=s.chunk_sphere, cull=cull,
+                      sweep_dist=self.sweep_dist, steps=self.steps, targets_out=self.targets, **groups)
+        return self.targets

@@ -145,13 +145,23 @@ class KinematicEnv:
     own parts (make_open_drawer_env(scene_meshes=) builds the table).
     contact: None, or a contact.ContactSensor over the scene pose's slots: every observation then senses (one more launch per step,
     no host synchronisation) and step()'s extras gain contact_dist (N, NB), the sensor's body distances in metres; in_contact (N, NB)
-    = contact_dist <= contact_margin; penetration (N) = max(0, -min_j contact_dist).  Contact sensing, not contact resolution: the
+    = contact_dist <= contact_margin; penetration (N) = max(0, -min_j contact_dist).  Sensing alone resolves nothing (resolve= below): the
     observation rows, rewards and flags are those of the same run without it.  grasp='contact' (grasp_cube only; needs a sensor
     with bodies named 'lfinger' and 'rfinger'): the hold predicate is in_contact[lfinger] & in_contact[rfinger] of the last
-    observation, in place of the gap rule, one step late like it.  The defaults leave every earlier code path as it was."""
+    observation, in place of the gap rule, one step late like it.
+    resolve: None (the sensor reports and nothing is blocked) or 'block' (needs contact=): contact blocking.  Every step then runs
+    one more launch first (contact.StepGuard, csrc/articulation_sweep.hip): the step is cut into block_substeps parts and the robot
+    stops at the last part before a sensing point would come within block_margin of a target, or deeper into one it touches; the
+    test reads the scene pose of the last observation.  extras gain blocked (N) bool = the step was cut, and step_fraction (N)
+    float32 = parts taken / block_substeps.  The limits, as contact.py states them: one fraction per environment (the whole robot
+    stops when any sensing body would touch); a thin target can be stepped over between two candidates; contact is sticky (motion
+    that lowers the distance below the margin is refused even if mostly tangential, motion away is admitted); held and reset
+    environments are not guarded (a held cube or drawer moves with the hand); no self-collision, no friction, nothing is pushed.
+    The defaults leave every earlier code path as it was: the same launches, the same extras keys."""
 
     def __init__(self, task, sim, observers=None, add_proprio_obs=False, grasp_width=GRASP_WIDTH, hold=True, random_reset=False,
-                 recorder=None, scene_rows=None, scene_C=None, contact=None, contact_margin=0.002, grasp="gap"):
+                 recorder=None, scene_rows=None, scene_C=None, contact=None, contact_margin=0.002, grasp="gap", resolve=None,
+                 block_substeps=8, block_margin=0.0):
         self.task, self.sim = task, sim
         if grasp not in ("gap", "contact"):
             raise ValueError(f"grasp: expected 'gap' or 'contact', got {grasp!r}")
@@ -165,6 +175,11 @@ class KinematicEnv:
                 raise ValueError(f"grasp='contact': contact= needs segments named 'lfinger' and 'rfinger' (names=), got {contact.names}")
             self._fingers = (contact.body("lfinger"), contact.body("rfinger"))
         self.contact, self.contact_margin, self.grasp_rule = contact, float(contact_margin), grasp
+        if resolve not in (None, "block"):
+            raise ValueError(f"resolve: expected None or 'block', got {resolve!r}")
+        if resolve == "block" and contact is None:
+            raise ValueError("resolve='block': needs contact= (a contact.ContactSensor): its points and targets are what is swept")
+        self.resolve, self._guard = resolve, None
         self._contact_extras = {}
         self.recorder, self._scene_pose = recorder, None
         self.scene_rows, self.scene_C = scene_rows, scene_C
@@ -200,6 +215,15 @@ class KinematicEnv:
         self._gap = torch.zeros(N, **f)
         if not self.grasp:
             self._pos_act_all = torch.zeros(sim.D, **f)
+        if resolve == "block":
+            from .contact import StepGuard
+            nb = sim.art.num_bodies
+            if scene_rows is not None:
+                row0 = sim.rb_row0.cpu().numpy() if sim.flat else np.arange(N) * sim.rigid_body.shape[1]
+                slot_body, C = guard_slot_body(nb, scene_rows=scene_rows.cpu().numpy(), rb_row0=row0), scene_C
+            else:
+                slot_body, C = guard_slot_body(nb, part_body=(task.part_body if self.grasp else task.part_slot).cpu().numpy()), task.part_C
+            self._guard = StepGuard(contact, slot_body, C, substeps=block_substeps, margin=block_margin)
 
     def __getattr__(self, name):                              # only reached for names the env itself does not hold
         if name in FORWARDED:
@@ -248,7 +272,7 @@ class KinematicEnv:
 
     def _sense(self):
         """The contact sensor on the scene pose the observers use: one launch, the three extras, and with grasp='contact' the hold
-        predicate of the next step.  It reports; nothing is pushed back or blocked."""
+        predicate of the next step.  It reports; blocking is the guard's (resolve='block'), one launch before the step."""
         R, T = self.compute_scene_pose()
         body = self.contact.sense(R, T, per_point=False).body_dist                # (N, NB)
         touch = body <= self.contact_margin
@@ -279,17 +303,26 @@ class KinematicEnv:
         step is written there as a PNG; that copies an image to the host and so synchronises, on those steps only."""
         task, sim = self.task, self.sim
         hold = self._hold if self._fixed_hold is None else self._fixed_hold
+        if self._guard is not None:
+            # the scene as the last observation saw it: _sense() gathered and cached it, so in steady state this issues no launch
+            # (a step() taken before any reset() would pose whatever rigid_body holds)
+            self._guard.set_scene(*self.compute_scene_pose())
         if self.grasp:
             pos_act, reset = task.begin_step(actions, sim.dof_state, sim.jacobian)
-            sim.step(pos_act, reset, hold=hold, u=self._u())
+            sim.step(pos_act, reset, hold=hold, u=self._u(), guard=self._guard)
         else:
             _, reset = task.begin_step(actions, sim.jacobian, sim.dof_state, sim.root, self._pos_act_all)
-            sim.step(task.pos_act, reset, hold=hold)
+            sim.step(task.pos_act, reset, hold=hold, guard=self._guard)
         obs = self._observe()
         if save_image_path is not None and self.recorder is not None:
             R, T = self.compute_scene_pose()                              # the observers' pose where there are observers
             self.recorder(R, T, save_image_path)
-        return obs, task.rew_buf, task.reset_buf, dict(task.extras, **self._contact_extras)
+        extras = dict(task.extras, **self._contact_extras)
+        if self._guard is not None:
+            g = self._guard
+            extras["blocked"] = g.steps < g.substeps
+            extras["step_fraction"] = g.steps.to(torch.float32) / g.substeps
+        return obs, task.rew_buf, task.reset_buf, extras
 
     def compute_scene_pose(self):
         """(rot (N, M, 3, 3), pos (N, M, 3)) of the last step, as the observers and the recorder get them: the task's own parts, or
@@ -308,6 +341,25 @@ class KinematicEnv:
         return {"rot": rot.cpu().numpy(), "pos": pos.cpu().numpy()}
 
 
+def guard_slot_body(nb, scene_rows=None, rb_row0=None, part_body=None):
+    """The slot_body table of a contact.StepGuard, on the host: for every pose slot of the scene pose the robot-local body in [0, nb)
+    that places it, or -1.  From scene_rows (N, M) (rows of the flat rigid-body tensor, -1 for an empty slot) and rb_row0 (N) (each
+    environment's first robot row): the row minus rb_row0, -1 where that falls outside the robot's nb rows; the environments must
+    agree (the robot's slots are the same columns everywhere).  Or from part_body (M), the task's posed-part list over an
+    environment's own rows (the robot's come first): entries outside [0, nb) become -1."""
+    if scene_rows is not None:
+        rows, row0 = np.asarray(scene_rows, dtype=np.int64), np.asarray(rb_row0, dtype=np.int64).reshape(-1)
+        if rows.ndim != 2 or row0.shape != (rows.shape[0],):
+            raise ValueError(f"scene_rows / rb_row0: expected (N, M) and (N,), got {rows.shape} and {row0.shape}")
+        rel = rows - row0[:, None]
+        sb = np.where((rows >= 0) & (rel >= 0) & (rel < nb), rel, -1)
+        if (sb != sb[:1]).any():
+            raise ValueError("scene_rows: the robot's bodies must sit in the same slots of every environment")
+        return sb[0].astype(np.int32)
+    part = np.asarray(part_body, dtype=np.int64).reshape(-1)
+    return np.where((part >= 0) & (part < nb), part, -1).astype(np.int32)
+
+
 def _scene(base_pose, dof):
     bp = np.asarray((0, 0, 0, 0, 0, 0, 1) if base_pose is None else base_pose, dtype=np.float64).reshape(-1)
     if bp.size != 7:
@@ -318,7 +370,8 @@ def _scene(base_pose, dof):
 
 def make_grasp_cube_env(cfg_task, num_envs, device, urdf, dt, base_pose=None, dof=None, observers=None, add_proprio_obs=False,
                         grasp_width=GRASP_WIDTH, hold=True, max_velocity=None, free_body_pose=(0, 0, 0.025, 0, 0, 0, 1), rest_z=0.025,
-                        fall_speed=0.0, reset_range=0.15, recorder=None, contact=None, contact_margin=0.002, grasp="gap"):
+                        fall_speed=0.0, reset_range=0.15, recorder=None, contact=None, contact_margin=0.002, grasp="gap", resolve=None,
+                        block_substeps=8, block_margin=0.0):
     """GraspCubeTensors + KinematicSim(free_body=True) around the robot of `urdf` (a path or a loaded tree; fixed or mobile, through
     tree.robot_kwargs()).  cfg_task: cfg/tasks/grasp_cube.yaml as a dict; base_pose (7), divided by its norm, and dof (the default
     joint positions; None: cfg_task['robot']['dof'], else mid-range) place the robot."""
@@ -336,7 +389,8 @@ def make_grasp_cube_env(cfg_task, num_envs, device, urdf, dt, base_pose=None, do
                        reset_range=reset_range)
     return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, grasp_width=grasp_width, hold=hold,
                         random_reset=bool(cfg_task.get("random_reset", False)), recorder=recorder, contact=contact,
-                        contact_margin=contact_margin, grasp=grasp)
+                        contact_margin=contact_margin, grasp=grasp, resolve=resolve, block_substeps=block_substeps,
+                        block_margin=block_margin)
 
 
 def scene_row_table(part_slot, rb_row0, obj_rb_row0, obj_bodies, max_bodies=None):
@@ -354,7 +408,8 @@ def scene_row_table(part_slot, rb_row0, obj_rb_row0, obj_bodies, max_bodies=None
 
 
 def make_open_drawer_env(cfg_task, num_envs, device, urdf, assets, dt, observers=None, add_proprio_obs=False, hold=True,
-                         max_velocity=None, recorder=None, scene_meshes=None, contact=None, contact_margin=0.002, grasp="gap"):
+                         max_velocity=None, recorder=None, scene_meshes=None, contact=None, contact_margin=0.002, grasp="gap",
+                         resolve=None, block_substeps=8, block_margin=0.0):
     """OpenDrawerTensors + KinematicSim(objects=...) wired as INTEGRATION.md's loop: assets = load_drawer_assets(folders, scale),
     handed out as env % num_objs; the robot of `urdf` (the mobile Franka of the shipped config, or the fixed one).
     scene_meshes: None, or load_drawer_meshes(assets) -- the same list a DepthFromMesh(meshes=robot parts, groups=scene_meshes,
@@ -384,4 +439,5 @@ def make_open_drawer_env(cfg_task, num_envs, device, urdf, assets, dt, observers
         rows = torch.from_numpy(rows).to(device)
         C = None if task.part_C is None else task.part_C[:nr].contiguous()
     return KinematicEnv(task, sim, observers=observers, add_proprio_obs=add_proprio_obs, hold=hold, recorder=recorder, scene_rows=rows,
-                        scene_C=C, contact=contact, contact_margin=contact_margin, grasp=grasp)
+                        scene_C=C, contact=contact, contact_margin=contact_margin, grasp=grasp, resolve=resolve,
+                        block_substeps=block_substeps, block_margin=block_margin)

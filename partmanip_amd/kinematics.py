@@ -6,8 +6,9 @@
     sim.set_dof_state(robot.default_dof_pos)
     rigid_body, dof_state, jacobian = sim.step(pos_act, reset)     # what the task steps call the simulator's three tensors
 
-It is not physics: no dynamics, no contact, no gravity; the joints follow their position targets (exactly, or at most max_velocity
-fast) inside their limits.  Rows of the tensors that are not the robot's (the cube, a cabinet) belong to the caller and are never
+It is not physics: no dynamics, no contact forces, no gravity; the joints follow their position targets (exactly, or at most
+max_velocity fast) inside their limits.  The one contact rule is opt-in and blocks, it does not push: step(guard=) stops the whole
+robot at the last of S parts of the step before a sensing point would enter a target (contact.StepGuard).  Rows of the tensors that are not the robot's (the cube, a cabinet) belong to the caller and are never
 written after construction, unless one of the two scenes below is asked for.
 
 With `free_body=True` and tips=(ltip, rtip) every environment also holds one free rigid body (the cube of grasp_cube: the last body
@@ -72,6 +73,13 @@ class Articulation:
         """ops.articulation_step on this tree; every tensor is the caller's."""
         ops.articulation_step(*self._tables(), base_pose, dof_state, targets=targets, reset=reset, vmax=vmax, dt=dt,
                               rigid_body=rigid_body, jac=jacobian, rb_row0=rb_row0, dof_row0=dof_row0)
+
+    def sweep(self, dof_state, base_pose, targets, dt, *sensing, reset=None, free=None, vmax=None, dof_row0=None, **kw):
+        """ops.articulation_sweep on this tree: the swept contact test of the step from dof_state towards targets, which writes no
+        state.  `sensing` and the other keywords are that function's arguments from `fields` on (contact.StepGuard holds them).
+        Returns (sweep_dist, steps, targets_out)."""
+        return ops.articulation_sweep(*self._tables(), base_pose, dof_state, targets, dt, *sensing, reset=reset, free=free, vmax=vmax,
+                                      dof_row0=dof_row0, **kw)
 
     def forward(self, dof_state, base_pose, rigid_body=None, jacobian=None, rb_row0=None, dof_row0=None):
         """Pure forward kinematics of dof_state (N, nd, 2), which is only read: (rigid_body (N, nb, 13), jacobian (N, nb - 1, 6, nd)),
@@ -363,17 +371,28 @@ class KinematicSim:
         self._free_body_step(None, ~self._no_flags, u)
         return self.rigid_body, self.dof_state, self.jacobian
 
-    def step(self, pos_act, reset=None, hold=None, u=None):
+    def step(self, pos_act, reset=None, hold=None, u=None, guard=None):
         """One launch: the joints move towards pos_act (N, nd), environments with reset set snap to it at rest; returns
         (rigid_body, dof_state, jacobian), updated in place.  With objects= a second launch on the same stream then poses every
         environment's object from root[:, 1, :7] and its DOF rows as they stand (a task reset has already written them).  hold (N)
         bool / uint8, or None: where set (and reset is not) the object's target joint follows the tips' mean velocity of THIS step
         (the hold rule); where not, it keeps its position at zero velocity; None: the objects' DOF rows are only read.
         With free_body= the second launch is the free body's (ops.free_body_step): hold (None: nowhere) latches and carries it, reset
-        puts it back at free_body_pose, moved by u (N, 3) in [0, 1) where given (xy inside +-reset_range and a yaw)."""
+        puts it back at free_body_pose, moved by u (N, 3) in [0, 1) where given (xy inside +-reset_range and a yaw).
+        guard: None, or a contact.StepGuard (contact blocking).  One more launch first: the swept test of this step
+        (ops.articulation_sweep) cuts it into guard.substeps parts and finds, per environment, the last part the robot can reach
+        without a sensing point coming within guard.margin of a target or deeper into one; the articulation launch then runs on
+        guard.targets with no rate limit (the sweep has applied it), so the joints stop at that candidate bit for bit.  Environments
+        with reset or hold set are not guarded (a held cube or drawer moves with the hand).  The whole robot stops, nothing slides or
+        is pushed, and the rule sees the scene as guard's pose table has it (the caller's last observation).  None: exactly the
+        launches above."""
         if u is not None and not self.free_body:
             raise ValueError("u needs free_body=")
-        self.art.step(self.dof_state, self.base_pose, targets=pos_act, reset=reset, vmax=self.max_velocity, dt=self.dt,
+        vmax = self.max_velocity
+        if guard is not None:
+            pos_act = guard.sweep(self, pos_act, reset, hold)
+            vmax = None
+        self.art.step(self.dof_state, self.base_pose, targets=pos_act, reset=reset, vmax=vmax, dt=self.dt,
                       rigid_body=self.rigid_body, jacobian=self.jacobian, rb_row0=self.rb_row0, dof_row0=self.dof_row0)
         if self.objects is not None:
             self._objects_step(reset, hold)

@@ -321,8 +321,9 @@ class TSDFfromMesh:
     query_tsdf_naive = query_tsdf          # the reference's naive path cannot run (class docstring); same kernel
 
     # ------------------------------------------------------------------------------------------------ posed points (contact.py)
-    def _sdf_points(self, pose_R, pose_T, pts, carrier, p0, p1, group_of=None, **kw):
-        """ops.mesh_sdf_points over this object's tables, ordinals [p0, p1) of _row_range: the grouped entry with groups=."""
+    def _point_tables(self, pose_R, pose_T, group_of=None):
+        """What a point query over this object's tables takes: (the five part tables, pose_R, pose_T as contiguous float32, the group
+        keywords of ops.mesh_sdf_points -- empty without groups=)."""
         eg = None
         if self.groups:
             eg = self._scene.for_call(ops.check_poses(pose_R, pose_T, self.part_num)[0], group_of)
@@ -331,10 +332,16 @@ class TSDFfromMesh:
         pose_R = pose_R.to(torch.float32).reshape(-1, self.part_num, 3, 3).contiguous()
         pose_T = pose_T.to(torch.float32).reshape(-1, self.part_num, 3).contiguous()
         tables = (self.sdf_field, self.sdf_field_off, self.sdf_field_res, self.sdf_bbox_min, self.sdf_voxel_size)
+        kw = {}
         if eg is not None:
-            kw.update(grid_slot=self._grid_slot, NG_shared=self.num_shared, group_off=self._scene.group_off_dev, env_group=eg,
+            kw = dict(grid_slot=self._grid_slot, NG_shared=self.num_shared, group_off=self._scene.group_off_dev, env_group=eg,
                       max_group_grids=self.max_group_grids)
-        return ops.mesh_sdf_points(*tables, pose_R, pose_T, pts, carrier, p0, p1, **kw)
+        return tables, pose_R, pose_T, kw
+
+    def _sdf_points(self, pose_R, pose_T, pts, carrier, p0, p1, group_of=None, **kw):
+        """ops.mesh_sdf_points over this object's tables, ordinals [p0, p1) of _row_range: the grouped entry with groups=."""
+        tables, pose_R, pose_T, groups = self._point_tables(pose_R, pose_T, group_of)
+        return ops.mesh_sdf_points(*tables, pose_R, pose_T, pts, carrier, p0, p1, **kw, **groups)
 
     def query_points(self, points, pose_R, pose_T, carrier=None, parts=None, group_of=None, segments=None, return_arg=False,
                      cull=True):

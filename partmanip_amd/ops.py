@@ -1751,18 +1751,11 @@ def _host_i32(a, name, n, lo, hi, device):
     return torch.from_numpy(np.ascontiguousarray(v, dtype=np.int32)).to(device)
 
 
-def mesh_sdf_points(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, pts, carrier=None, p0=0, p1=None,
-                    pt_id=None, chunk_sphere=None, seg_off=None, want_dist=True, want_arg=False, dist=None, cull=True, grid_slot=None,
-                    NG_shared=None, group_off=None, env_group=None, max_group_grids=None):
-    """Signed distance, in metres, of posed points to the part grids (pm_mesh_sdf_points_f32; with grid_slot= the grouped entry
-    pm_mesh_sdf_points_groups_f32, whose tables are those of mesh_tsdf_query_groups).  Part tables and poses as mesh_tsdf_query.
-    pts (NP, 3) shared by all environments or (B, NP, 3); carrier: None (world points) or NP integers in [-1, M), the pose slot that
-    carries each point (-1: world); [p0, p1): the ordinals sampled.  pt_id: None or NP integers, the id a point is reported under in
-    seg_arg (negative: a padding point, in no segment result); chunk_sphere: None or (ceil(NP / 64), 4) float32, what the cull
-    reads (include/partmanip_hip.h); seg_off: None or NS + 1 non-decreasing integers from 0 to NP.  carrier / pt_id / seg_off on the
-    host are validated and copied; on the device they are checked for type and length only.  dist: None or a float32 view (B, >= NP)
-    with unit inner stride to write into.  Returns (dist (B, NP) or None, arg (B, NP) int32 or None, seg_min (B, NS) or None, seg_arg
-    (B, NS) int32 or None): dist unless want_dist is False, arg with want_arg, the segment pair with seg_off."""
+def _sdf_point_args(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, pts, carrier, p0, p1, pt_id,
+                     chunk_sphere, seg_off, grid_slot, NG_shared, group_off, env_group, max_group_grids, point_output=True):
+    """The argument checks mesh_sdf_points and articulation_sweep share (the tables, the points and their side tables, the ordinal
+    range, the group tables).  Returns (grouped, NG, B, M, dev, NP, stride, carrier, pt_id, seg_off, NS, grid_slot, group_off,
+    env_group, G, most, p0, p1) with the host tables copied to the device."""
     grouped = grid_slot is not None
     NG, B, M = _mesh_tsdf_tables(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, None, grouped=grouped)
     dev = pose_R.device
@@ -1793,7 +1786,7 @@ def mesh_sdf_points(fields, part_off, part_shape, part_bbox_min, part_voxel_size
         _f32c(chunk_sphere, "chunk_sphere")
         if tuple(chunk_sphere.shape) != ((NP + 63) // 64, 4):
             raise ValueError(f"chunk_sphere: expected ({(NP + 63) // 64}, 4), got {tuple(chunk_sphere.shape)}")
-    if not want_dist and dist is None and not want_arg and NS == 0:
+    if not point_output and NS == 0:
         raise ValueError("want_dist=False: needs seg_off (nothing would be computed)")
     if grouped:
         grid_slot = _host_i32(grid_slot, "grid_slot", NG, 0, M, dev)
@@ -1803,10 +1796,28 @@ def mesh_sdf_points(fields, part_off, part_shape, part_bbox_min, part_voxel_size
     else:
         if any(a is not None for a in (NG_shared, group_off, env_group, max_group_grids)):
             raise ValueError("NG_shared / group_off / env_group / max_group_grids: need grid_slot=")
-        top = M
+        top, G, most = M, 0, 0
     p0, p1 = int(p0), top if p1 is None else int(p1)
     if not 0 <= p0 < p1 <= top:
         raise ValueError(f"p0, p1: expected 0 <= p0 < p1 <= {top}, got {p0}, {p1}")
+    return grouped, NG, B, M, dev, NP, stride, carrier, pt_id, seg_off, NS, grid_slot, group_off, env_group, G, most, p0, p1
+
+
+def mesh_sdf_points(fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, pts, carrier=None, p0=0, p1=None,
+                    pt_id=None, chunk_sphere=None, seg_off=None, want_dist=True, want_arg=False, dist=None, cull=True, grid_slot=None,
+                    NG_shared=None, group_off=None, env_group=None, max_group_grids=None):
+    """Signed distance, in metres, of posed points to the part grids (pm_mesh_sdf_points_f32; with grid_slot= the grouped entry
+    pm_mesh_sdf_points_groups_f32, whose tables are those of mesh_tsdf_query_groups).  Part tables and poses as mesh_tsdf_query.
+    pts (NP, 3) shared by all environments or (B, NP, 3); carrier: None (world points) or NP integers in [-1, M), the pose slot that
+    carries each point (-1: world); [p0, p1): the ordinals sampled.  pt_id: None or NP integers, the id a point is reported under in
+    seg_arg (negative: a padding point, in no segment result); chunk_sphere: None or (ceil(NP / 64), 4) float32, what the cull
+    reads (include/partmanip_hip.h); seg_off: None or NS + 1 non-decreasing integers from 0 to NP.  carrier / pt_id / seg_off on the
+    host are validated and copied; on the device they are checked for type and length only.  dist: None or a float32 view (B, >= NP)
+    with unit inner stride to write into.  Returns (dist (B, NP) or None, arg (B, NP) int32 or None, seg_min (B, NS) or None, seg_arg
+    (B, NS) int32 or None): dist unless want_dist is False, arg with want_arg, the segment pair with seg_off."""
+    (grouped, NG, B, M, dev, NP, stride, carrier, pt_id, seg_off, NS, grid_slot, group_off, env_group, G, most, p0, p1) = _sdf_point_args(
+        fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, pts, carrier, p0, p1, pt_id, chunk_sphere, seg_off,
+        grid_slot, NG_shared, group_off, env_group, max_group_grids, point_output=want_dist or dist is not None or want_arg)
     ld = NP
     if dist is not None:
         _out_rows(dist, B, NP, name="dist")
@@ -2257,18 +2268,12 @@ def _rows_of(t_, name, width, N, n, row0):
     return t_.shape[0], 0
 
 
-def articulation_step(parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, base_pose, dof_state, targets=None,
-                      reset=None, vmax=None, dt=0.0, rigid_body=None, jac=None, rb_row0=None, dof_row0=None):
-    """One step of the kinematic articulation in one launch (pm_articulation_step_f32, include/partmanip_hip.h).  The tree tables
-    (nb) / (nb, 4) / (nb, 3) and anc_mask (nb) int64 come from kinematics.Articulation, which validates them; dof_lo, dof_hi, vmax
-    (nd); base_pose (7) or (N, 7); dof_state (N, >= nd, 2), or flat (D, 2) with dof_row0 (N) int32, updated in place when targets
-    (N, nd) is given (reset (N) bool / uint8 then snaps an environment to its clamped target); rigid_body (N, >= nb, 13) or flat
-    (B, 13) with rb_row0; jac (N, nb - 1, 6, nd).  rigid_body and jac may be None (skipped)."""
-    _one_device("articulation_step", parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, base_pose, dof_state,
-                targets, reset, vmax, rigid_body, jac, rb_row0, dof_row0)
+def _articulation_args(who, parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, vmax, base_pose, dof_state, dof_row0):
+    """The tree, limit, base-pose and DOF-row checks articulation_step and articulation_sweep share.  Returns (nb, nd, N, the base
+    pose's stride, the rows of dof_state, its rows per environment)."""
     nb, nd = parent.numel(), dof_lo.numel()
     if not (1 <= nb <= 64 and 1 <= nd <= 64):
-        raise ValueError(f"articulation_step: {nb} bodies / {nd} DOFs outside [1, 64]")
+        raise ValueError(f"{who}: {nb} bodies / {nd} DOFs outside [1, 64]")
     for t_, name in ((parent, "parent"), (jtype, "jtype"), (dof, "dof")):
         _vec(t_, name, nb, torch.int32)
     _vec(anc_mask, "anc_mask", nb, torch.int64)
@@ -2293,6 +2298,20 @@ def articulation_step(parent, jtype, dof, origin_q, origin_t, axis, anc_mask, do
     if not N:
         raise ValueError(f"dof_state: expected (N, >= {nd}, 2) or flat (D, 2) with dof_row0, got {tuple(dof_state.shape)}")
     dof_rows, ldd = _rows_of(dof_state, "dof_state", 2, N, nd, dof_row0)
+    return nb, nd, N, lbase, dof_rows, ldd
+
+
+def articulation_step(parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, base_pose, dof_state, targets=None,
+                      reset=None, vmax=None, dt=0.0, rigid_body=None, jac=None, rb_row0=None, dof_row0=None):
+    """One step of the kinematic articulation in one launch (pm_articulation_step_f32, include/partmanip_hip.h).  The tree tables
+    (nb) / (nb, 4) / (nb, 3) and anc_mask (nb) int64 come from kinematics.Articulation, which validates them; dof_lo, dof_hi, vmax
+    (nd); base_pose (7) or (N, 7); dof_state (N, >= nd, 2), or flat (D, 2) with dof_row0 (N) int32, updated in place when targets
+    (N, nd) is given (reset (N) bool / uint8 then snaps an environment to its clamped target); rigid_body (N, >= nb, 13) or flat
+    (B, 13) with rb_row0; jac (N, nb - 1, 6, nd).  rigid_body and jac may be None (skipped)."""
+    _one_device("articulation_step", parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, base_pose, dof_state,
+                targets, reset, vmax, rigid_body, jac, rb_row0, dof_row0)
+    nb, nd, N, lbase, dof_rows, ldd = _articulation_args("articulation_step", parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo,
+                                                         dof_hi, vmax, base_pose, dof_state, dof_row0)
     rb_rows, ldr = _rows_of(rigid_body, "rigid_body", 13, N, nb, rb_row0) if rigid_body is not None else (0, 0)
     if jac is not None:
         _shape_f32c(jac, "jac", (N, nb - 1, 6, nd))
@@ -2311,6 +2330,79 @@ def articulation_step(parent, jtype, dof, origin_q, origin_t, axis, anc_mask, do
                                            _ptr(dof_state), dof_rows, _ptr(targets), ldt, _ptr(reset), _ptr(rb_row0), ldr, rb_rows,
                                            _ptr(dof_row0), ldd, N, nb, nd, _ptr(rigid_body), _ptr(jac), _stream()),
               "pm_articulation_step_f32")
+
+
+def articulation_sweep(parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, base_pose, dof_state, targets, dt, fields,
+                       part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, pts, carrier, seg_off, slot_body, substeps,
+                       margin=0.0, reset=None, free=None, vmax=None, dof_row0=None, slot_C=None, p0=0, p1=None, pt_id=None,
+                       chunk_sphere=None, cull=True, grid_slot=None, NG_shared=None, group_off=None, env_group=None,
+                       max_group_grids=None, sweep_dist=None, steps=None, targets_out=None):
+    """The swept contact test of one kinematic step in one launch (pm_articulation_sweep_f32; with grid_slot= the grouped entry;
+    include/partmanip_hip.h states the rule): how many of `substeps` parts of the step from dof_state towards targets the robot can
+    take before a sensing point comes within `margin` of a target grid, or deeper into one.  The tree tables, limits, vmax, base_pose,
+    dof_state (only read), targets (N, nd), reset and dof_row0 as articulation_step; the part tables, pose_R / pose_T (N, M, ...: the
+    scene pose as it stands), pts, carrier, pt_id, chunk_sphere, seg_off (required), [p0, p1), cull and the group tables as
+    mesh_sdf_points.  slot_body: M integers, the robot body in [0, nb) that places pose slot m or -1 for a slot the table places (on
+    the host: validated and copied; on the device: type and length only); slot_C (MC <= M, 3, 3) or None: body_pose_gather's part_C;
+    free (N) bool / uint8 or None: environments that are not guarded.  sweep_dist (N, substeps + 1) float32, steps (N) int32,
+    targets_out (N, nd) float32: None (fresh) or contiguous tensors to write.  Returns (sweep_dist, steps, targets_out); nothing
+    else is written."""
+    nb, nd, N, lbase, dof_rows, ldd = _articulation_args("articulation_sweep", parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo,
+                                                         dof_hi, vmax, base_pose, dof_state, dof_row0)
+    if targets is None:
+        raise ValueError("targets: the sweep needs the step's targets (N, nd)")
+    ldt = _row_view(targets, "targets", N, nd)
+    if not float(dt) > 0:
+        raise ValueError(f"dt: expected a positive step, got {dt}")
+    for t_, name in ((reset, "reset"), (free, "free")):
+        if t_ is not None:
+            _flags(t_, name, N)
+    S = int(substeps)
+    if not 1 <= S <= 63:
+        raise ValueError(f"substeps: expected 1 .. 63 parts of a step, got {substeps}")
+    margin = float(margin)
+    if margin != margin:
+        raise ValueError("margin: expected a number, got NaN")
+    if seg_off is None:
+        raise ValueError("seg_off: the sweep needs the sensing bodies' segments")
+    (grouped, NG, B, M, dev, NP, stride, carrier, pt_id, seg_off, NS, grid_slot, group_off, env_group, G, most, p0, p1) = _sdf_point_args(
+        fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, pts, carrier, p0, p1, pt_id, chunk_sphere, seg_off,
+        grid_slot, NG_shared, group_off, env_group, max_group_grids)
+    if B != N:
+        raise ValueError(f"pose_R / pose_T: expected the {N} environments of the articulation, got {B}")
+    slot_body = _host_i32(slot_body, "slot_body", M, -1, nb, dev)
+    MC = 0
+    if slot_C is not None:
+        _f32c(slot_C, "slot_C")
+        if slot_C.dim() != 3 or tuple(slot_C.shape[1:]) != (3, 3) or slot_C.shape[0] > M:
+            raise ValueError(f"slot_C: expected (MC <= {M}, 3, 3), got {tuple(slot_C.shape)}")
+        MC = slot_C.shape[0]
+    lds = (S + 1) * (((7 * nb) | 1) * 8 + 4 * nd)
+    if lds > 57344:
+        raise ValueError(f"substeps: {S} parts of a {nb}-body chain need {lds} bytes of LDS, above 57344")
+    f = dict(dtype=torch.float32, device=dev)
+    sweep_dist = torch.empty(N, S + 1, **f) if sweep_dist is None else sweep_dist
+    steps = torch.empty(N, dtype=torch.int32, device=dev) if steps is None else steps
+    targets_out = torch.empty(N, nd, **f) if targets_out is None else targets_out
+    _shape_f32c(sweep_dist, "sweep_dist", (N, S + 1))
+    _vec(steps, "steps", N, torch.int32)
+    _shape_f32c(targets_out, "targets_out", (N, nd))
+    _one_device("articulation_sweep", parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, base_pose, dof_state,
+                targets, reset, free, vmax, dof_row0, fields, part_off, part_shape, part_bbox_min, part_voxel_size, pose_R, pose_T, pts,
+                carrier, pt_id, seg_off, chunk_sphere, slot_body, slot_C, grid_slot, group_off, env_group, sweep_dist, steps, targets_out)
+    head = (_ptr(parent), _ptr(jtype), _ptr(dof), _ptr(origin_q), _ptr(origin_t), _ptr(axis), _ptr(dof_lo), _ptr(dof_hi), _ptr(vmax),
+            float(dt), _ptr(base_pose), lbase, _ptr(dof_state), dof_rows, _ptr(targets), ldt, _ptr(reset), _ptr(dof_row0), ldd, N, nb, nd,
+            _ptr(fields), _ptr(part_off), _ptr(part_shape), _ptr(part_bbox_min), _ptr(part_voxel_size))
+    tail = (_ptr(pose_R), _ptr(pose_T), M, p0, p1, _ptr(pts), stride, _ptr(carrier), _ptr(pt_id), _ptr(chunk_sphere), NP, _ptr(seg_off), NS,
+            1 if cull else 0, _ptr(slot_body), _ptr(slot_C if MC else None), MC, S, margin, _ptr(free), _ptr(sweep_dist), _ptr(steps),
+            _ptr(targets_out), _stream())
+    with TIMER.bracket("articulation_sweep"):
+        if grouped:
+            check(lib.pm_articulation_sweep_groups_f32(*head, _ptr(grid_slot), NG, int(NG_shared), _ptr(group_off), G, _ptr(env_group), most,
+                                                       *tail), "pm_articulation_sweep_groups_f32")
+        else:
+            check(lib.pm_articulation_sweep_f32(*head, *tail), "pm_articulation_sweep_f32")
+    return sweep_dist, steps, targets_out
 
 
 def articulation_objects_step(body_off, dof_off, parent, jtype, dof, origin_q, origin_t, axis, anc_mask, dof_lo, dof_hi, max_nb, max_nd,
